@@ -18,6 +18,13 @@ work.  Multi-GPU: environments are sharded over ranks (replicas, no data-path co
 weak scaling); the auxiliary ``heis20`` object times the 20-qubit Heisenberg <H> with Pauli
 terms sharded over the ranks and ONE RCCL all-reduce of the partial energies.
 
+A plain run sets up, warms up, times the --steps launches of the headline kernel and prints the JSON line
+(`value` env-steps/s over all ranks, `ms_per_step` wall milliseconds of one timed step).  --full adds the
+auxiliary objects (warm start, gate sweep, noisy / trainable / exact-channel launches, the episodes, heis20,
+the MPS -> PQC fits and the CPU baselines).  --dump-outputs DIR writes what the last timed step returned to
+its caller (per-environment energies, optimised angles and evaluation counts) as DIR/<name>.npy in float64;
+the inputs are seeded, so two builds can be compared output for output.
+
 Launch: under torchrun (RANK / LOCAL_RANK / WORLD_SIZE in the environment) every process is one rank.
 Started plainly with --gpus N > 1 and no WORLD_SIZE, this process spawns the N ranks itself
 (`python -m torch.distributed.run ...` as a child, before anything here touches the GPU) and exits
@@ -421,6 +428,26 @@ def launch_selftest(args, rank, world):
         dist.destroy_process_group()
 
 
+DUMP_BUDGET = 60 * 10 ** 6      # array bytes written by --dump-outputs (index arrays of samples included): < 64 MB with headers
+
+
+def dump_outputs(out_dir, arrays, rank, world):
+    """--dump-outputs: one float64 .npy per array (suffixed with the rank when there are several).  Should the arrays
+    outgrow DUMP_BUDGET, every array is replaced by the same fraction of its entries, drawn with a fixed seed, and
+    <name>_index.npy records which entries those are."""
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    arrays = {k: np.asarray(v, np.float64).ravel() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    keep = 1.0 if total <= DUMP_BUDGET else DUMP_BUDGET / (2.0 * total)      # value + index per sampled entry
+    for name, a in arrays.items():
+        if keep < 1.0:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, max(1, int(a.size * keep)), replace=False))
+            np.save(os.path.join(out_dir, f"{name}_index{sfx}.npy"), idx.astype(np.float64))
+            a = a[idx]
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), a)
+
+
 def src_sha16():
     """Hash of the kernel sources: a counter file describes ONE build (instruction counts are properties of the code),
     so every profiles/pmc_*.json carries the hash of the sources it was measured on and is ignored when they moved on."""
@@ -806,8 +833,15 @@ def main():
     ap.add_argument("--no-trainable12", action="store_true")
     ap.add_argument("--no-dm", action="store_true")
     ap.add_argument("--no-mps2qc-stream", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also the auxiliary objects of the line (warm start, gate sweep, noisy12, "
+                    "trainable8/12, dm12, episode, episode8, heis20, mps2qc, mps2qc_stream, cpu_baseline; each can be left out "
+                    "with its --no-* option); without it only the headline launches are timed")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned (energy, "
+                    "x_opt, nfev per environment) as DIR/<name>.npy in float64")
     args = ap.parse_args()
-    if args.only == "headline":
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.only == "headline" or not args.full:
         args.headline_only = True
     if args.headline_only:
         args.no_cpu_baseline = args.no_heis20 = args.no_mps2qc = args.no_sweep = args.no_episode = args.no_noisy = args.no_trainable8 = args.no_episode8 = True
@@ -828,11 +862,12 @@ def main():
 
     # Host threads on ONE L3 domain, before anything creates the HIP runtime's helper threads (tensorrl_qas_amd/affinity.py:
     # a loop of ~10 us launches otherwise runs up to 5 x slower on the pool's two-socket hosts, from process to process;
-    # VQE_CPU_BIND=0 switches it off).  The BLAS pool of the CPU baseline is started first, with the full CPU mask.
+    # VQE_CPU_BIND=0 switches it off).  The BLAS pool of the CPU baseline (--full) is started first, with the full CPU mask.
     global ALL_CPUS
     if hasattr(os, "sched_getaffinity"):
         ALL_CPUS = set(os.sched_getaffinity(0))
-        _ = np.ones((512, 512)) @ np.ones((512, 512))
+        if not args.no_cpu_baseline:
+            _ = np.ones((512, 512)) @ np.ones((512, 512))
     import importlib.util
     _spec = importlib.util.spec_from_file_location("vqe_affinity", os.path.join(ROOT, "tensorrl-qas_amd", "affinity.py"))
     _aff = importlib.util.module_from_spec(_spec)
@@ -916,7 +951,9 @@ def main():
     dt = float(tt.item())
     # kernel duration (HIP events on the launch stream) of the last step, and its work
     k_ms = eng.last_kernel_ms()
-    _, f, nfev = eng.batch_fetch(want_x=False)
+    x_last, f, nfev = eng.batch_fetch(want_x=args.dump_outputs is not None)
+    if args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, {"energy": f, "x_opt": x_last, "nfev": nfev}, rank, world)
     evals_per_launch = int(nfev.sum()) + B          # + the final post-action evaluation
     T, Tx = ham.n_terms, ham.n_xgroups
     bytes_per_eval = (2 ** n) * 16 * (2 * (G - 1) + T)          # 2^n*16*(2G+T)

@@ -6,7 +6,7 @@ What is recorded (data only - inputs and expected outputs, never reference sourc
 
 * ``ham_<case>.npz``   - the shipped Hamiltonian fixtures of dmrg-to-qc/mol_data reduced to
   ``paulis, weights, eigvals`` (+ the dense matrix for the tiny LiH-4q case that ships no
-  Pauli list) and the init circuit of dmrg-to-qc/init_state_circ as a gate table
+  Pauli list, and for TFIM-6q, whose matrix pins the npz writer's qubit order) and the init circuit of dmrg-to-qc/init_state_circ as a gate table
   (name id, qubits, angle) parsed from the QASM twin of the QPY file the reference loads
   (environment_qulacs_TN_notin_agent.py:79-84,126-131).
 * ``known_answers.json`` - E(TN_state) with the bit-reversed dense H (the quantity printed
@@ -82,7 +82,7 @@ def data_fixtures():
                         eigvals=d["eigvals"], energy_shift=d["energy_shift"])
     d = np.load(f"{REF}/dmrg-to-qc/mol_data/tfim_j1_h0.001_6q.npz")
     np.savez_compressed(f"{HERE}/ham_tfim_6q.npz", n=6, paulis=d["paulis"], weights=d["weights"],
-                        eigvals=d["eigvals"])
+                        eigvals=d["eigvals"], hamiltonian=d["hamiltonian"])
     json.dump(known, open(f"{HERE}/known_answers.json", "w"), indent=1, sort_keys=True)
 
 

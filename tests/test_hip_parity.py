@@ -714,6 +714,45 @@ def test_bench_workload_parity(tq):
         assert 1 <= nfev[i] <= 150
 
 
+def test_bench_plain_run_dumps_its_last_step(tq, tmp_path):
+    """`bench.py` without --full: the line of the headline launches alone (no auxiliary object), `steps` timed steps,
+    `value` = environments / `ms_per_step`; --dump-outputs holds the last step's per-environment results, whose
+    energies the oracle reproduces at the dumped (float32-rounded) angles."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n, B, G = 12, 32, 64
+    out = tmp_path / "dump"
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--envs", str(B), "--dump-outputs", str(out)], capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["metric"] == "VQE env-steps/sec" and line["unit"] == "env-steps/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "f64" and line["steps"] == 2 and line["warmup"] == 1
+    assert abs(line["value"] - B / (line["ms_per_step"] * 1e-3)) <= 1e-9 * line["value"]
+    assert not {"warm_start", "gate_sweep", "noisy12", "trainable8", "trainable12", "dm12", "episode", "episode8", "heis20",
+                "mps2qc", "mps2qc_stream", "cpu_baseline"} & set(line)
+    f, x, nfev = (np.load(out / f"{k}.npy") for k in ("energy", "x_opt", "nfev"))
+    assert f.dtype == x.dtype == nfev.dtype == np.float64 and f.shape == nfev.shape == (B,)
+    assert line["energy_checksum"] == float(np.sum(f))
+    H = tq.hamiltonian.synthetic_lih12()
+    psi0 = tq.hamiltonian.brickwork_state(n, 12)
+    b = bench.make_batch(tq, n, B, G, 1000)
+    assert x.shape == b["theta"].shape and np.all((nfev >= 1) & (nfev <= 1000))
+    kind = b["kind"].reshape(B, G); q0 = b["q0"].reshape(B, G); q1 = b["q1"].reshape(B, G); pidx = b["pidx"].reshape(B, G)
+    for i in range(0, B, 8):
+        xi = x[b["par_off"][i]:b["par_off"][i + 1]]
+        assert np.array_equal(xi, xi.astype(np.float32).astype(np.float64))
+        psi = vo.run_circuit(psi0, kind[i], q0[i], q1[i], pidx[i], xi)
+        assert abs(vo.energy_pauli(psi, H.xmask, H.zmask, H.coeff) - f[i]) < E_TOL
+
+
 def test_heisenberg_20q_config(tq):
     """BASELINE config 4 at full size (20 qubits, 77 terms, 20 X-mask groups): the closed-form
     energy of |0...0> (19 ZZ bonds + 20 Z = 39), a random-circuit energy against the oracle,

@@ -2,8 +2,8 @@
 # Everything the bench line and profiles/ need, in one GPU call (about 12 minutes):
 #   1. PMC passes of every kernel of the bench line (tools/pmc_collect.py) -> profiles/pmc_<key>.json
 #   2. PMC passes of the 20-qubit streaming batch -> profiles/pmc_heis20.json
-#   3. rocprofv3 --kernel-trace --stats of the default bench command -> <tag>_bench_kernel_stats.csv, <tag>_bench_under_rocprof.json
-#   4. the default bench command on its own      -> <tag>_bench.json
+#   3. rocprofv3 --kernel-trace --stats of the --full bench command -> <tag>_bench_kernel_stats.csv, <tag>_bench_under_rocprof.json
+#   4. the --full bench command on its own       -> <tag>_bench.json
 # Results land in gpurun_out/prof_<tag>/ (copy them into profiles/).
 # usage: tools/profile_all.sh <tag> [pmc|bench|all]   (two GPU calls of <= 20 minutes: "pmc" first, then "bench")
 TAG=${1:-rXX}
@@ -29,12 +29,12 @@ cd /tmp && export TMPDIR=/tmp
 # (a) the timed launches alone: the kernel's average duration here is what roofline.kernel_ms (HIP events) must agree with
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_headline -- python3 $REPO/bench.py --steps 5 --warmup 1 --headline-only > $OUT/${TAG}_bench_headline_under_rocprof.json 2> $OUT/stats_headline.err || echo "headline stats pass failed"
 for f in $OUT/stats_headline/*/*kernel_stats.csv; do cp $f $OUT/${TAG}_bench_headline_kernel_stats.csv; done
-# (b) the default command with all auxiliaries (the same kernel also serves the sweep / episode launches there)
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $REPO/bench.py > $OUT/${TAG}_bench_under_rocprof.json 2> $OUT/stats.err || echo "stats pass failed"
+# (b) the --full command with all auxiliaries (the same kernel also serves the sweep / episode launches there)
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $REPO/bench.py --full > $OUT/${TAG}_bench_under_rocprof.json 2> $OUT/stats.err || echo "stats pass failed"
 for f in $OUT/stats/*/*kernel_stats.csv; do cp $f $OUT/${TAG}_bench_kernel_stats.csv; done
 echo "stats done"
 cd $REPO
-timeout -k 10 600 python3 bench.py > $OUT/${TAG}_bench.json 2> $OUT/bench.err || echo "bench failed"
+timeout -k 10 600 python3 bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/bench.err || echo "bench failed"
 python3 - "$OUT" "$TAG" <<'PY'
 import json, sys, csv
 out, tag = sys.argv[1], sys.argv[2]

@@ -154,6 +154,16 @@ int vqe_set_circuit(vqe_t* h, int n_gates, const int32_t* kind, const int32_t* q
 int vqe_energy(vqe_t* h, const double* theta, double* energy);
 int vqe_energy_batch(vqe_t* h, int batch, const double* theta /* batch x n_params */,
                      double* energy /* batch */);
+/* Energy and its gradient dE/dtheta of the circuit set by vqe_set_circuit at `batch` parameter vectors, by the
+ * adjoint method (one forward sweep, lambda = H psi, one backward sweep; the cost does not grow with the number of
+ * parameters).  grad[b * P + j] sums over every gate with parameter index j (0 for a parameter no gate uses).
+ * replaces: the finite-difference gradient scipy.optimize.minimize builds for a gradient method when the reference
+ * passes no `jac` (environment_qulacs_TN_notin_agent.py:452-482 with optim_alg = BFGS, L-BFGS-B, ...): P + 1
+ * sequential get_exp_val calls per gradient.  1 <= n <= 13 (LDS-resident path; n >= 14: VQE_EINVAL).  Refused with
+ * VQE_ESTATE while Pauli noise (p1 or p2 > 0), the exact channel noise mode, shot noise or an amplitude shard is set
+ * on the handle.  On a term-sharded handle energy and gradient are the shard's partial sums. */
+int vqe_energy_grad_batch(vqe_t* h, int batch, const double* theta /* batch x P */,
+                          double* energy /* batch */, double* grad /* batch x P */);
 /* replaces: circuit.update_quantum_state(state); state.get_vector()  (:84-85) */
 int vqe_get_state(vqe_t* h, const double* theta, double* amps_re_im /* 2 * 2^n */);
 /* replaces: scipy.optimize.minimize(cost, x0, method='COBYLA', options={'maxiter': m})
@@ -194,6 +204,13 @@ int vqe_batch_set_new_gate(vqe_t* h, const int32_t* new_gate /* batch, or NULL *
 int vqe_batch_run_env_step(vqe_t* h, double rhobeg, double rhoend, int maxfun);
 int vqe_batch_fetch(vqe_t* h, double* x /* sum of n_params, may be NULL */,
                     double* f /* batch */, int32_t* nfev /* batch, may be NULL */);
+/* vqe_energy_grad_batch for the resident batch of vqe_batch_load (circuits of different lengths and parameter
+ * counts): energies land where vqe_batch_run_energy puts them (vqe_batch_fetch's f), the gradients are copied back
+ * by vqe_batch_fetch_grad in the layout of vqe_batch_fetch's x.  replaces: the finite-difference gradients of B
+ * independent scipy.optimize.minimize calls with a gradient method (environment_qulacs_TN_notin_agent.py:452-482);
+ * same n range and refusals as vqe_energy_grad_batch. */
+int vqe_batch_run_energy_grad(vqe_t* h);
+int vqe_batch_fetch_grad(vqe_t* h, double* grad /* sum of n_params, layout of vqe_batch_fetch's x */);
 /* the optimiser's result before the float32 rounding of vqe_batch_run_env_step
  * (scipy's result.x, stored by the reference as env.opt_ang_save, :288); same layout as x */
 int vqe_batch_fetch_xopt(vqe_t* h, double* x /* sum of n_params */);

@@ -56,6 +56,7 @@ SIGNATURES = {
     "vqe_set_circuit": (C.c_int, [vp, C.c_int, c_i32p, c_i32p, c_i32p, c_i32p, C.c_int]),
     "vqe_energy": (C.c_int, [vp, c_f64p, c_f64p]),
     "vqe_energy_batch": (C.c_int, [vp, C.c_int, c_f64p, c_f64p]),
+    "vqe_energy_grad_batch": (C.c_int, [vp, C.c_int, c_f64p, c_f64p, c_f64p]),
     "vqe_get_state": (C.c_int, [vp, c_f64p, c_f64p]),
     "vqe_minimize_cobyla": (C.c_int, [vp, c_f64p, C.c_double, C.c_double, C.c_int, c_f64p, c_f64p, c_i32p]),
     "vqe_batch_load": (C.c_int, [vp, C.c_int, c_i64p, c_i32p, c_i32p, c_i32p, c_i32p, c_i64p, c_f64p]),
@@ -66,6 +67,8 @@ SIGNATURES = {
     "vqe_batch_run_env_step": (C.c_int, [vp, C.c_double, C.c_double, C.c_int]),
     "vqe_batch_fetch": (C.c_int, [vp, c_f64p, c_f64p, c_i32p]),
     "vqe_batch_fetch_xopt": (C.c_int, [vp, c_f64p]),
+    "vqe_batch_run_energy_grad": (C.c_int, [vp]),
+    "vqe_batch_fetch_grad": (C.c_int, [vp, c_f64p]),
     "vqe_batch_energy_devptr": (C.c_int, [vp, C.POINTER(vp)]),
     "vqe_batch_copy_energy": (C.c_int, [vp, vp]),
     "vqe_batch_set_trace": (C.c_int, [vp, C.c_int]),

@@ -4,6 +4,7 @@
 #include "vqe_device.h"
 #include "vqe_stream.h"
 #include "vqe_dm.h"
+#include "vqe_grad.h"
 
 #include <algorithm>
 #include <cmath>
@@ -115,6 +116,14 @@ struct vqe_handle {
   int comm_world = 0;
   StreamWork sw;  // streaming-path work buffers
   uint64_t gen = 0;   // bumped whenever a resident batch / Hamiltonian shard / noise setting changes (plans of vqe_tile.h)
+  // adjoint gradient (vqe_grad.h): unit-free table set of this handle's shard, built on the first gradient request
+  uint64_t ham_ver = 0, grad_ham_ver = ~0ull;
+  DevBuf<uint32_t> g_gx;
+  DevBuf<int64_t> g_off;
+  DevBuf<int32_t> g_cplx;
+  DevBuf<double> g_tab, d_grad;
+  DevBuf<double2> g_lam;
+  GradHam gham{};
 };
 
 #ifdef VQE_STAMPS
@@ -350,6 +359,7 @@ int choose_fixed_bits(int n, int sel, int F, const std::vector<uint32_t>& act, s
 int build_hamiltonian(vqe_t* h) {
   const int n = h->n;
   ++h->gen;
+  ++h->ham_ver;
   const std::vector<int> owner = assign_groups(h->gx_all, h->group_terms, h->lds_path, h->shard_world);
   std::vector<int> mine;
   for (size_t g = 0; g < owner.size(); ++g) if (owner[g] == h->shard_rank) mine.push_back((int)g);
@@ -1306,6 +1316,117 @@ int run(vqe_t* h, int which, double rhobeg, double rhoend, int maxfun) {
   return VQE_OK;
 }
 
+// ---- adjoint gradient (vqe_grad.h) -----------------------------------------------------------
+// The unit-free table set of k_lds_energy_grad: every X-mask group of this handle's shard (the same partition as
+// build_hamiltonian) in the logical index, T[q] = D_x(p0) = sum_k c_k i^{#Y} (-1)^{popc(p0 & z_k)} over the pair
+// representatives p0 = insert0(q, hb(x)) (complex entries only for groups with an odd number of Y factors), the
+// diagonal group over all indices.  Rebuilt when the Hamiltonian or its shard changed.
+int build_grad_tables(vqe_t* h) {
+  if (h->grad_ham_ver == h->ham_ver) return VQE_OK;
+  const int n = h->n;
+  const size_t dim = (size_t)1 << n;
+  const std::vector<int> owner = assign_groups(h->gx_all, h->group_terms, h->lds_path, h->shard_world);
+  std::vector<uint32_t> gx;
+  std::vector<int64_t> off;
+  std::vector<int32_t> cplx;
+  std::vector<double> tab;
+  for (size_t g = 0; g < owner.size(); ++g) {
+    if (owner[g] != h->shard_rank) continue;
+    const uint32_t x = h->gx_all[g];
+    bool im = false;
+    for (int k : h->group_terms[g]) im |= h->hci[k] != 0.0;
+    const size_t len = x == 0 ? dim : dim / 2;
+    const int hb = x == 0 ? 0 : 31 - __builtin_clz(x);
+    gx.push_back(x);
+    off.push_back((int64_t)tab.size());
+    cplx.push_back(im ? 1 : 0);
+    const size_t base = tab.size();
+    tab.resize(base + (im ? 2 * len : len), 0.0);
+    double* t = tab.data() + base;
+    for (int k : h->group_terms[g]) {
+      const uint32_t z = (uint32_t)h->hz[k];
+      for (size_t q = 0; q < len; ++q) {
+        const uint32_t p0 = x == 0 ? (uint32_t)q : (uint32_t)(((q >> hb) << (hb + 1)) | (q & (((size_t)1 << hb) - 1)));
+        const double sgn = (__builtin_popcount(p0 & z) & 1) ? -1.0 : 1.0;
+        if (im) { t[2 * q] += sgn * h->hcr[k]; t[2 * q + 1] += sgn * h->hci[k]; }
+        else t[q] += sgn * h->hcr[k];
+      }
+    }
+  }
+  int rc;
+  if ((rc = upload(h, h->g_gx, gx.data(), gx.size()))) return rc;
+  if ((rc = upload(h, h->g_off, off.data(), off.size()))) return rc;
+  if ((rc = upload(h, h->g_cplx, cplx.data(), cplx.size()))) return rc;
+  if ((rc = upload(h, h->g_tab, tab.data(), tab.size()))) return rc;
+  HIP_TRY(h, hipStreamSynchronize(h->stream));  // host vectors go out of scope
+  h->gham = GradHam{(int)gx.size(), h->g_gx.p, h->g_off.p, h->g_cplx.p, h->g_tab.p};
+  h->grad_ham_ver = h->ham_ver;
+  return VQE_OK;
+}
+
+// What the adjoint kernel cannot serve: a gradient of a stochastic trajectory is of no use to an optimiser, and the
+// streaming path (n >= 14) has no adjoint kernel.  Checked before anything is loaded, so a refused call leaves the
+// handle as it was.
+int grad_refusal(vqe_t* h) {
+  if (!h->lds_path) return fail(h, VQE_EINVAL, "energy gradients are computed for n_qubits <= 13 (LDS-resident path) only");
+  if (h->noise.p1 > 0.0 || h->noise.p2 > 0.0)
+    return fail(h, VQE_ESTATE, "energy gradients of Pauli-noise trajectories are refused (set p1 = p2 = 0)");
+  if (h->noise_mode == 1) return fail(h, VQE_ESTATE, "energy gradients are not available in the exact channel noise mode");
+  if (h->noise.shot_sigma != 0.0) return fail(h, VQE_ESTATE, "energy gradients with shot noise are refused (set sigma_total = 0)");
+  if (h->amp_world > 1) return fail(h, VQE_ESTATE, "energy gradients of an amplitude shard are refused");
+  return VQE_OK;
+}
+
+template <int N>
+int launch_grad(vqe_t* h, const BatchArgs& A) {
+  constexpr int NW = Geo<N>::NW;
+  bool lam_global = N >= 13;
+  size_t lds = grad_lds_bytes(N, lam_global, A.max_ops, A.max_params, NW);
+  if (!lam_global && lds > (size_t)h->lds_per_cu) {      // psi + lambda + ops do not fit: lambda moves to global memory
+    lam_global = true;
+    lds = grad_lds_bytes(N, true, A.max_ops, A.max_params, NW);
+  }
+  if (lds > (size_t)h->lds_per_cu) return fail(h, VQE_EINVAL, "circuit too large for the adjoint gradient kernel (gates + parameters)");
+  const int wg_per_cu = std::max(1, (int)(h->lds_per_cu / lds));
+  const void* fn = lam_global ? (const void*)k_lds_energy_grad<N, true> : (const void*)k_lds_energy_grad<N, false>;
+  HIP_TRY(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  h->last_wg_per_cu = std::min(8, wg_per_cu);
+  int grid = A.batch;
+  if (lam_global) {
+    grid = std::min(A.batch, h->cu_count * wg_per_cu);
+    HIP_TRY(h, h->g_lam.reserve((size_t)grid << N));
+  }
+  HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
+  if (lam_global)
+    hipLaunchKernelGGL((k_lds_energy_grad<N, true>), dim3(grid), dim3(Geo<N>::NT), lds, h->stream, A, h->gham, h->d_grad.p, h->g_lam.p);
+  else
+    hipLaunchKernelGGL((k_lds_energy_grad<N, false>), dim3(grid), dim3(Geo<N>::NT), lds, h->stream, A, h->gham, h->d_grad.p,
+                       (double2*)nullptr);
+  HIP_TRY(h, hipGetLastError());
+  HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
+  return VQE_OK;
+}
+
+int run_grad(vqe_t* h) {
+  int rc;
+  if ((rc = grad_refusal(h))) return rc;
+  HIP_TRY(h, hipSetDevice(h->dev));
+  if ((rc = build_grad_tables(h))) return rc;
+  HIP_TRY(h, h->d_grad.reserve((size_t)h->total_params + 1));
+  const BatchArgs A = make_args(h);
+  h->last_run_dm = false;
+  switch (h->n) {
+#define C(N) case N: return launch_grad<N>(h, A);
+#ifdef VQE_ONLY_N
+    C(VQE_ONLY_N)
+#else
+    C(1) C(2) C(3) C(4) C(5) C(6) C(7) C(8) C(9) C(10) C(11) C(12) C(13)
+#endif
+#undef C
+  }
+  return fail(h, VQE_EINVAL, "energy gradients are computed for n_qubits <= 13 (LDS-resident path) only");
+}
+
 }  // namespace
 
 // =========================================================================================
@@ -1755,6 +1876,39 @@ int vqe_batch_run_energy(vqe_t* h) {
   int rc = ready(h);
   if (rc) return rc;
   return run(h, 0, 0, 0, 0);
+}
+
+int vqe_energy_grad_batch(vqe_t* h, int batch, const double* theta, double* energy, double* grad) {
+  if (!h) return VQE_EINVAL;
+  if (batch < 1 || !energy || (h->circ_params > 0 && (!theta || !grad))) return fail(h, VQE_EINVAL, "bad arguments");
+  int rc;
+  if ((rc = grad_refusal(h))) return rc;
+  HIP_TRY(h, hipSetDevice(h->dev));
+  if ((rc = load_single(h, batch, theta))) return rc;
+  if ((rc = ready(h))) return rc;
+  if ((rc = run_grad(h))) return rc;
+  HIP_TRY(h, hipMemcpyAsync(energy, h->d_f.p, (size_t)batch * 8, hipMemcpyDeviceToHost, h->stream));
+  if (h->total_params) HIP_TRY(h, hipMemcpyAsync(grad, h->d_grad.p, (size_t)h->total_params * 8, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return VQE_OK;
+}
+
+int vqe_batch_run_energy_grad(vqe_t* h) {
+  int rc = ready(h);
+  if (rc) return rc;
+  return run_grad(h);
+}
+
+int vqe_batch_fetch_grad(vqe_t* h, double* grad) {
+  if (!h) return VQE_EINVAL;
+  if (h->batch <= 0) return fail(h, VQE_ESTATE, "no batch loaded");
+  if (!grad && h->total_params) return fail(h, VQE_EINVAL, "grad is NULL");
+  if (h->d_grad.cap < (size_t)h->total_params + 1) return fail(h, VQE_ESTATE, "vqe_batch_run_energy_grad has not been called");
+  HIP_TRY(h, hipSetDevice(h->dev));
+  if (h->total_params)
+    HIP_TRY(h, hipMemcpyAsync(grad, h->d_grad.p, (size_t)h->total_params * 8, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return VQE_OK;
 }
 
 int vqe_batch_run_reduction(vqe_t* h) {

@@ -206,6 +206,22 @@ class VQEEngine:
         self._chk(self._lib.vqe_energy_batch(self._h, th.shape[0], _p(th, c_f64p), _p(out, c_f64p)))
         return out
 
+    def energy_grad(self, theta):
+        """(E, dE/dtheta) at one parameter vector by the adjoint method on the GPU (n <= 13)."""
+        th = _f64(theta)
+        if th.size != self._P:
+            raise ValueError("theta has the wrong length")
+        e, g = self.energy_grad_batch(th.reshape(1, -1))
+        return float(e[0]), g[0]
+
+    def energy_grad_batch(self, thetas):
+        """Energies [B] and gradients [B, P] of the circuit at B parameter vectors (adjoint method)."""
+        th = _f64(thetas).reshape(-1, self._P) if self._P else np.zeros((len(thetas), 0))
+        e = np.empty(th.shape[0], np.float64)
+        g = np.empty((th.shape[0], self._P), np.float64)
+        self._chk(self._lib.vqe_energy_grad_batch(self._h, th.shape[0], _p(th, c_f64p), _p(e, c_f64p), _p(g, c_f64p)))
+        return e, g
+
     def get_state(self, theta) -> np.ndarray:
         th = _f64(theta)
         if th.size != self._P:
@@ -278,6 +294,16 @@ class VQEEngine:
         self._chk(self._lib.vqe_batch_fetch(self._h, _p(x, c_f64p) if want_x else C.cast(None, c_f64p),
                                             _p(f, c_f64p), _p(nfev, c_i32p)))
         return x, f, nfev
+
+    def batch_run_energy_grad(self):
+        """Energies and gradients of the resident batch (energies: batch_fetch's f, gradients: batch_fetch_grad)."""
+        self._chk(self._lib.vqe_batch_run_energy_grad(self._h))
+
+    def batch_fetch_grad(self) -> np.ndarray:
+        """Gradients of the last batch_run_energy_grad, concatenated in the layout of batch_fetch's x."""
+        g = np.empty(self._total_params, np.float64)
+        self._chk(self._lib.vqe_batch_fetch_grad(self._h, _p(g, c_f64p)))
+        return g
 
     def batch_fetch_xopt(self):
         x = np.empty(self._total_params, np.float64)

@@ -27,6 +27,31 @@ from .utils import curricula, utils
 _CHAIN_MODELS = ("heisenberg", "tfim_j1_h0.05")   # file names without geometry (reference :78,:122)
 
 
+# scipy.optimize.minimize methods by what they need from the cost function (the reference passes optim_alg from the
+# config straight to minimize, environment_qulacs_TN_notin_agent.py:452-482)
+_GRADIENT_METHODS = ("cg", "bfgs", "l-bfgs-b", "tnc", "slsqp", "newton-cg")
+_GRADIENT_FREE_METHODS = ("nelder-mead", "powell")
+_HESSIAN_METHODS = ("dogleg", "trust-ncg", "trust-krylov", "trust-exact", "trust-constr")
+
+
+def optimizer_kind(optim_alg) -> str:
+    """How CircuitEnv.step runs ``optim_alg`` (host only, needs no device):
+    "device_cobyla" - COBYLA, the whole loop on the GPU (one fused launch per step);
+    "host_gradient" - a scipy gradient method driven on the host with the adjoint gradient of the GPU as ``jac``;
+    "host_gradient_free" - a scipy method that needs energies only, evaluated on the GPU.
+    Raises NotImplementedError for methods that need a Hessian and for names scipy does not know."""
+    name = str(optim_alg).lower()
+    if name == "cobyla":
+        return "device_cobyla"
+    if name in _GRADIENT_METHODS:
+        return "host_gradient"
+    if name in _GRADIENT_FREE_METHODS:
+        return "host_gradient_free"
+    if name in _HESSIAN_METHODS:
+        raise NotImplementedError(f"optim_alg = {optim_alg!r} needs a Hessian, which the engine does not compute")
+    raise NotImplementedError(f"unknown optim_alg {optim_alg!r}")
+
+
 class EnvSpec:
     """Everything derived from the config that does not change over episodes."""
 
@@ -153,8 +178,10 @@ class CircuitEnvBase:
             self.optim_method = None
         if self.optim_method not in (None, "scipy_each_step"):
             raise NotImplementedError("only method = scipy_each_step is live in the reference (SURVEY 3.3 quirk 6)")
-        if self.optim_method and self.optim_alg != "COBYLA":
-            raise NotImplementedError("the device optimiser implements COBYLA (every shipped cfg uses it)")
+        self.optimizer_kind = optimizer_kind(self.optim_alg) if self.optim_method else None
+        if self.optimizer_kind not in (None, "device_cobyla") and (self.NOISY or self.phys_noise or self.n_shots):
+            raise NotImplementedError("noisy and finite-shot environments run COBYLA only (the device optimiser); "
+                                      f"optim_alg = {self.optim_alg!r} is refused")
 
     # ---- engine set-up ---------------------------------------------------------------------
     def _make_engine(self, device):
@@ -323,12 +350,46 @@ class CircuitEnvBase:
         eng = self.engine
         eng.batch_load([circ], [ang])
         eng.batch_set_new_gate([new_idx])
+        if self.optim_method == "scipy_each_step" and self.optimizer_kind != "device_cobyla":
+            return self._step_host_optimizer(next_state, circ, ang, new_idx, action, train_flag)
         if self.optim_method == "scipy_each_step":
             eng.batch_run_env_step(1.0, 1e-4, int(self.global_iters))
             x, f, nfev = eng.batch_fetch()
             x_opt = self._strip_new(circ, new_idx, eng.batch_fetch_xopt())
             return self._post_step(next_state, circ, x, x_opt, float(f[0]), int(nfev[0]), action, train_flag)
         raise NameError("opt_ang")   # what the reference does for any other method
+
+    def _step_host_optimizer(self, next_state, circ, ang, new_idx, action, train_flag):
+        """scipy_each_step with a method other than COBYLA (reference step() :283-291, scipy_optim :452-482): scipy
+        minimises the energy of the circuit WITHOUT the new gate from the committed angles; gradient methods get the
+        adjoint gradient of the GPU as ``jac``.  The optimum is rounded to float32 and the energy of the full circuit
+        at those angles is the step's energy.  A pre-action circuit without parameters is evaluated once, as on the
+        device path (scipy would refuse an empty x0 for most methods)."""
+        import scipy.optimize
+        eng = self.engine
+        p_new = int(circ.pidx[new_idx]) if new_idx >= 0 else -1
+        if new_idx >= 0:
+            keep = np.arange(len(circ)) != new_idx
+            pidx = circ.pidx[keep].copy()
+            if p_new >= 0:
+                pidx[pidx > p_new] -= 1
+            pre = _circ.Circuit(circ.kind[keep], circ.q0[keep], circ.q1[keep], pidx, circ.n_params - (p_new >= 0))
+        else:
+            pre = circ
+        x0 = np.delete(np.asarray(ang, np.float64), p_new) if p_new >= 0 else np.asarray(ang, np.float64)
+        eng.set_circuit(pre)
+        if x0.size == 0:
+            x_opt, nfev = x0, 1
+        else:
+            grad = self.optimizer_kind == "host_gradient"
+            res = scipy.optimize.minimize(eng.energy_grad if grad else eng.energy, x0, method=self.optim_alg,
+                                          jac=True if grad else None, options={"maxiter": self.global_iters})
+            x_opt, nfev = np.asarray(res.x, np.float64), int(res.nfev)
+        x_full = np.insert(x_opt, p_new, ang[p_new]) if p_new >= 0 else x_opt.copy()
+        x_full = x_full.astype(np.float32).astype(np.float64)      # the state tensor's dtype (reference :480)
+        eng.set_circuit(circ)
+        energy = eng.energy(x_full)
+        return self._post_step(next_state, circ, x_full, x_opt, float(energy), nfev, action, train_flag)
 
     @staticmethod
     def _strip_new(circ, new_idx, x):

@@ -79,6 +79,9 @@ class VecCircuitEnv:
         if not issubclass(env_cls, CircuitEnvBase):
             raise TypeError("env_cls must be one of the CircuitEnv classes of this package")
         first = env_cls(conf, device, seed=seed)
+        if first.optimizer_kind not in (None, "device_cobyla"):
+            raise NotImplementedError(f"VecCircuitEnv runs the device COBYLA of batch_run_env_step only; optim_alg = "
+                                      f"{first.optim_alg!r} is served by CircuitEnv")
         self.engine = first.engine
         self._proto = first
         self.num_envs = num_envs

@@ -1,0 +1,282 @@
+"""GPU: adjoint energy gradients (k_lds_energy_grad, vqe_energy_grad_batch / vqe_batch_run_energy_grad) against exact
+parameter shift on the CPU oracle, and the gradient-based optim_alg path of CircuitEnv."""
+import numpy as np
+import pytest
+
+import vqe_oracle as vo
+from helpers import fermionic_hamiltonian, random_gates, random_hamiltonian, random_state
+
+pytestmark = pytest.mark.gpu
+
+
+def _engine(n, ham, psi0, circ):
+    import tensorrl_qas_amd as tq
+    eng = tq.VQEEngine(n, 0)
+    eng.set_init_state(psi0)
+    eng.set_hamiltonian(*ham)
+    eng.set_circuit(circ)
+    return eng
+
+
+def _circuit(kind, q0, q1, pidx, P):
+    import tensorrl_qas_amd as tq
+    return tq.Circuit(kind, q0, q1, pidx, P)
+
+
+def _oracle_energy(psi0, kind, q0, q1, pidx, th, ham):
+    return vo.energy_pauli(vo.run_circuit(psi0, kind, q0, q1, pidx, th), *ham)
+
+
+def _shift_grad(psi0, kind, q0, q1, pidx, th, ham):
+    """Exact parameter shift, gate by gate: dE/dtheta_j = sum over the gates g with parameter j of
+    (E(theta_g + pi/2) - E(theta_g - pi/2)) / 2, each gate given its own copy of the angle."""
+    P = th.size
+    grad = np.zeros(P)
+    rot = [g for g in range(kind.size) if kind[g] in (1, 2, 3)]
+    # one private parameter per rotation gate, so that shared parameters are shifted one gate at a time
+    own = np.array([-1] * kind.size, np.int32)
+    for i, g in enumerate(rot):
+        own[g] = i
+    base = np.array([th[pidx[g]] for g in rot])
+    for i, g in enumerate(rot):
+        tp, tm = base.copy(), base.copy()
+        tp[i] += np.pi / 2
+        tm[i] -= np.pi / 2
+        d = 0.5 * (_oracle_energy(psi0, kind, q0, q1, own, tp, ham) - _oracle_energy(psi0, kind, q0, q1, own, tm, ham))
+        grad[pidx[g]] += d
+    return grad
+
+
+def _hamiltonians(n, rng):
+    hs = [random_hamiltonian(n, 6 + 2 * n, rng, real=False)]
+    if n >= 4:
+        hs.append(fermionic_hamiltonian(n, n_hop=2 * n, n_quad=n, rng=rng, dressed=2))
+    return hs
+
+
+@pytest.mark.parametrize("n", [1, 2, 4, 8, 10, 12, 13])
+def test_grad_parity(n):
+    rng = np.random.default_rng(100 + n)
+    G = {1: 8, 2: 14, 4: 30, 8: 50, 10: 40, 12: 36, 13: 24}[n]
+    kind, q0, q1, pidx, th = random_gates(n, G, rng, p_cnot=0.3 if n > 1 else 0.0)
+    psi0 = random_state(n, rng)
+    for which, ham in enumerate(_hamiltonians(n, rng)):
+        eng = _engine(n, ham, psi0, _circuit(kind, q0, q1, pidx, th.size))
+        if which == 1 and n >= 8:      # the fermionic sum is held partly as units by vqe_energy
+            assert eng.hamiltonian_layout()["units"] > 0
+        e, g = eng.energy_grad(th)
+        g_ref = _shift_grad(psi0, kind, q0, q1, pidx, th, ham)
+        scale = max(1.0, float(np.abs(ham[2]).sum()))
+        assert np.abs(g - g_ref).max() <= 1e-10 * scale, (n, np.abs(g - g_ref).max())
+        assert abs(e - eng.energy(th)) <= 1e-10
+        assert abs(e - _oracle_energy(psi0, kind, q0, q1, pidx, th, ham)) <= 1e-10 * scale
+
+
+def test_grad_shared_and_unused_parameters():
+    n = 5
+    rng = np.random.default_rng(7)
+    psi0 = random_state(n, rng)
+    ham = random_hamiltonian(n, 20, rng, real=False)
+    # parameter 0 drives an RY on q1 and an RX on q3, parameter 2 drives no gate
+    kind = np.array([2, 0, 1, 3, 0, 2], np.int32)
+    q0 = np.array([1, 1, 3, 0, 3, 4], np.int32)
+    q1 = np.array([-1, 2, -1, -1, 0, -1], np.int32)
+    pidx = np.array([0, -1, 0, 1, -1, 3], np.int32)
+    th = np.array([0.7, -1.1, 2.0, 0.4])
+    eng = _engine(n, ham, psi0, _circuit(kind, q0, q1, pidx, 4))
+    e, g = eng.energy_grad(th)
+    g_ref = _shift_grad(psi0, kind, q0, q1, pidx, th, ham)
+    assert g[2] == 0.0
+    assert np.abs(g - g_ref).max() <= 1e-10 * max(1.0, np.abs(ham[2]).sum())
+    # the shared parameter's gradient is the sum of its two gates' (finite difference of the shared angle agrees)
+    h = 1e-5
+    tp, tm = th.copy(), th.copy()
+    tp[0] += h
+    tm[0] -= h
+    fd = (_oracle_energy(psi0, kind, q0, q1, pidx, tp, ham) - _oracle_energy(psi0, kind, q0, q1, pidx, tm, ham)) / (2 * h)
+    assert abs(g[0] - fd) < 1e-7
+
+
+@pytest.mark.parametrize("n", [6, 12])
+def test_grad_batch_entry_points(n):
+    import tensorrl_qas_amd as tq
+    rng = np.random.default_rng(31 + n)
+    psi0 = random_state(n, rng)
+    ham = fermionic_hamiltonian(n, n_hop=2 * n, n_quad=n, rng=rng, dressed=1)
+    circs, thetas = [], []
+    for b in range(7):
+        kind, q0, q1, pidx, th = random_gates(n, 5 + 9 * b, rng)
+        circs.append(tq.Circuit(kind, q0, q1, pidx, th.size))
+        thetas.append(th)
+    eng = tq.VQEEngine(n, 0)
+    eng.set_init_state(psi0)
+    eng.set_hamiltonian(*ham)
+    eng.batch_load(circs, thetas)
+    eng.batch_run_energy_grad()
+    _, f, _ = eng.batch_fetch(want_x=False)
+    gcat = eng.batch_fetch_grad()
+    off = 0
+    for c, th, fb in zip(circs, thetas, f):
+        eng.set_circuit(c)
+        e1, g1 = eng.energy_grad(th)
+        assert abs(fb - e1) <= 1e-12
+        assert np.abs(gcat[off:off + th.size] - g1).max(initial=0.0) <= 1e-12
+        off += th.size
+    assert off == gcat.size
+    # energy_grad_batch agrees with energy_batch
+    c = circs[-1]
+    eng.set_circuit(c)
+    ths = np.stack([thetas[-1] + 0.1 * k for k in range(5)])
+    e, g = eng.energy_grad_batch(ths)
+    assert g.shape == (5, c.n_params)
+    assert np.abs(e - eng.energy_batch(ths)).max() <= 1e-10
+
+
+def test_grad_term_shards_sum():
+    n = 10
+    rng = np.random.default_rng(5)
+    kind, q0, q1, pidx, th = random_gates(n, 40, rng)
+    psi0 = random_state(n, rng)
+    ham = fermionic_hamiltonian(n, n_hop=14, n_quad=8, rng=rng, dressed=2)
+    circ = _circuit(kind, q0, q1, pidx, th.size)
+    full = _engine(n, ham, psi0, circ)
+    e, g = full.energy_grad(th)
+    parts = []
+    for r in range(2):
+        eng = _engine(n, ham, psi0, circ)
+        eng.set_term_shard(r, 2)
+        parts.append(eng.energy_grad(th))
+    assert abs(parts[0][0] + parts[1][0] - e) <= 1e-12
+    assert np.abs(parts[0][1] + parts[1][1] - g).max() <= 1e-12
+
+
+def test_grad_refusals_leave_the_handle_usable():
+    import tensorrl_qas_amd as tq
+    n = 6
+    rng = np.random.default_rng(9)
+    kind, q0, q1, pidx, th = random_gates(n, 20, rng)
+    psi0 = random_state(n, rng)
+    ham = random_hamiltonian(n, 12, rng)
+    circ = _circuit(kind, q0, q1, pidx, th.size)
+    e_ref = _oracle_energy(psi0, kind, q0, q1, pidx, th, ham)
+
+    def refused(setup, undo):
+        eng = _engine(n, ham, psi0, circ)
+        setup(eng)
+        with pytest.raises(tq.VQEError):
+            eng.energy_grad(th)
+        undo(eng)
+        assert abs(eng.energy(th) - e_ref) <= 1e-10
+        eng.energy_grad(th)
+
+    refused(lambda e: e.set_noise(0.01, 0.0, 1), lambda e: e.set_noise(0.0, 0.0, 1))
+    refused(lambda e: e.set_noise_mode(1), lambda e: e.set_noise_mode(0))
+    refused(lambda e: e.set_shot_noise(0.1, 3), lambda e: e.set_shot_noise(0.0, 3))
+    # n = 14 (streaming path): no adjoint kernel, a loud error
+    n14 = 14
+    k14, a14, b14, p14, t14 = random_gates(n14, 10, rng)
+    h14 = random_hamiltonian(n14, 6, rng)
+    e14 = _engine(n14, h14, random_state(n14, rng), _circuit(k14, a14, b14, p14, t14.size))
+    with pytest.raises(tq.VQEError):
+        e14.energy_grad(t14)
+    assert np.isfinite(e14.energy(t14))
+
+
+# ---- environments: scipy_each_step with optim_alg other than COBYLA -----------------------------------------------
+@pytest.fixture(scope="module")
+def data_root(tmp_path_factory):
+    from helpers import make_data_root
+    return make_data_root(str(tmp_path_factory.mktemp("dmrg-to-qc")))
+
+
+def _state_energy(state, n, psi0, ham):
+    k, a, b, p, th = vo.ansatz_from_state(np.asarray(state), n)
+    return vo.energy_pauli(vo.run_circuit(psi0, k, a, b, p, th), *ham)
+
+
+def _oracle_step(prev_state, state, n, psi0, ham, method, iters, gradient):
+    """The reference's step restated on the oracle: scipy with the same method minimises the pre-action circuit (with
+    the parameter-shift gradient as jac for gradient methods), the optimum is rounded to float32 and the full circuit
+    is evaluated at those angles."""
+    import scipy.optimize
+    import torch
+    k, a, b, p, th = vo.ansatz_from_state(prev_state.numpy(), n)
+    fun = lambda x: vo.energy_pauli(vo.run_circuit(psi0, k, a, b, p, x), *ham)
+
+    def fun_jac(x):
+        g = np.empty(x.size)
+        for j in range(x.size):
+            tp, tm = x.copy(), x.copy()
+            tp[j] += np.pi / 2
+            tm[j] -= np.pi / 2
+            g[j] = 0.5 * (fun(tp) - fun(tm))
+        return fun(x), g
+
+    if th.size == 0:
+        x = th
+    else:
+        x = scipy.optimize.minimize(fun_jac if gradient else fun, th, method=method, jac=True if gradient else None,
+                                    options={"maxiter": iters}).x
+    s = state.clone()
+    rot = prev_state[:, n:n + 3] == 1
+    ang = s[:, n + 3:]
+    ang[rot] = torch.tensor(x, dtype=torch.float)
+    return _state_energy(s.numpy(), n, psi0, ham)
+
+
+def _episode(env, script, n, psi0, ham, method, iters, gradient, tol=1e-8):
+    from tensorrl_qas_amd.environments.utils.utils import dictionary_of_actions
+    table = dictionary_of_actions(n)
+    env.reset()
+    for ai in script:
+        prev = env.state.clone()
+        env.step(table[ai])
+        e_ref = _oracle_step(prev, env.state, n, psi0, ham, method, iters, gradient)
+        assert abs(env.energy - e_ref) <= tol, (method, ai, env.energy, e_ref)
+        assert abs(env.energy - _state_energy(env.state.numpy(), n, psi0, ham)) <= 1e-10
+        assert env.nfev >= 1
+
+
+@pytest.mark.parametrize("method", ["L-BFGS-B", "BFGS", "Nelder-Mead"])
+def test_fixed_env_host_optimizers(data_root, method):
+    import torch
+    from helpers import load_case, oracle_init_state, reference_config
+    from tensorrl_qas_amd.environments.environment_qulacs_TN_notin_agent import CircuitEnv
+    conf = reference_config("TensorRL_fixed/H2O8q_TNbond2", data_root)
+    conf["non_local_opt"]["global_iters"] = 40
+    conf["non_local_opt"]["optim_alg"] = method
+    case = load_case("H2O_8q")
+    env = CircuitEnv(conf, torch.device("cuda:0"))
+    assert env.optimizer_kind == ("host_gradient_free" if method == "Nelder-Mead" else "host_gradient")
+    n = env.num_qubits
+    ham = (*vo.pauli_masks(case["paulis"], n, reverse=False), case["weights"])
+    # CNOT(0->1), RY(q1), RX(q1), CNOT(1->3), RZ(q3), RY(q0)
+    script = [0, 56 + 1 * 3 + 1, 56 + 1 * 3 + 0, 7 + 1, 56 + 3 * 3 + 2, 56 + 0 * 3 + 1]
+    _episode(env, script, n, oracle_init_state(case), ham, method, 40, method != "Nelder-Mead")
+
+
+def test_trainable_env_lbfgsb(data_root):
+    import torch
+    from helpers import load_case, reference_config
+    from tensorrl_qas_amd.environments.environment_qulacs import CircuitEnv
+    conf = reference_config("TensorRL_trainable/H2O8q_TNbond2", data_root)
+    conf["non_local_opt"]["global_iters"] = 6
+    conf["non_local_opt"]["optim_alg"] = "L-BFGS-B"
+    case = load_case("H2O_8q")
+    env = CircuitEnv(conf, torch.device("cuda:0"))
+    n = env.num_qubits
+    ham = (*vo.pauli_masks(case["paulis"], n, reverse=True), case["weights"])
+    zero = np.eye(1, 2 ** n)[0].astype(complex)
+    script = [56 + 2 * 3 + 1, 3, 56 + 5 * 3 + 0, 56 + 2 * 3 + 2, 8 + 4, 56 + 7 * 3 + 1]
+    _episode(env, script, n, zero, ham, "L-BFGS-B", 6, True)
+
+
+def test_vec_env_refuses_host_optimizers(data_root):
+    import torch
+    from helpers import reference_config
+    from tensorrl_qas_amd.environments.environment_qulacs_TN_notin_agent import CircuitEnv
+    from tensorrl_qas_amd.environments.vec_env import VecCircuitEnv
+    conf = reference_config("TensorRL_fixed/H2O8q_TNbond2", data_root)
+    conf["non_local_opt"]["optim_alg"] = "L-BFGS-B"
+    with pytest.raises(NotImplementedError):
+        VecCircuitEnv(CircuitEnv, conf, torch.device("cuda:0"), 2)

@@ -97,6 +97,10 @@ int vqe_hamiltonian_terms(vqe_t* h, int32_t* n_terms, int32_t* n_xgroups);
  * if there is a diagonal group.  The reference has no counterpart: its get_exp_val multiplies
  * by the dense matrix (VQE_qulacs_TN_notin_RL.py:86). */
 int vqe_hamiltonian_layout(vqe_t* h, int32_t out[4]);
+/* LDS bank conflicts of the unit path's ds_read_b128 (model: four groups of 16 lanes per wave): out = {mean, worst}
+ * number of a group's lanes that share one 16-byte slot with the plain state layout, then {mean, worst} with the bank
+ * swizzle the handle chose (1 = conflict free; the identity where no swizzle applies). */
+int vqe_unit_bank_score(vqe_t* h, double out[4]);
 /* Evaluate only the X-mask groups owned by `rank` of `world` (Pauli-term sharding; the
  * caller sums the partial energies of all ranks, e.g. one RCCL all-reduce). */
 int vqe_set_term_shard(vqe_t* h, int rank, int world);

@@ -64,9 +64,11 @@ struct vqe_handle {
   DevBuf<int32_t> d_tab_r, d_tab_i;
 
   DevBuf<int32_t> d_term_off;
-  DevBuf<uint32_t> d_urec;   // unit path (HamDev::urec / utab)
+  DevBuf<uint32_t> d_urec;   // unit path (HamDev::urec / uaddr / utab)
+  DevBuf<uint32_t> d_uaddr;
   DevBuf<double> d_utab;
   HamDev ham{};
+  double unit_score[4] = {1.0, 1.0, 1.0, 1.0};   // bank swizzle: mean / worst slot depth of the unit reads, identity then chosen
   NoiseCfg noise{0.0, 0.0, 0ull, 0ull, 0.0};
 
   // single circuit
@@ -355,6 +357,85 @@ int choose_fixed_bits(int n, int sel, int F, const std::vector<uint32_t>& act, s
   return patterns;
 }
 
+// LDS bank swizzle of the register path (HamDev::swz).  ds_read_b128 serves a wavefront in four groups of 16 lanes -
+// (lane bit 5, parity of lane bits 2..4) - and a group is conflict free when its 16 lanes hit 16 different 16-byte
+// slots modulo 256 B, i.e. 16 different values of index bits 0..3.  The lanes of a unit differ in its free index bits;
+// where a low index bit is a hole of the unit (a fixed or the selector bit) the plain layout stacks a group 2, 4 or 8
+// deep.  S XORs bits 0..3 with a linear code of bits 4..7: codes c[k] for bit 4+k, coordinate descent from the
+// identity and from the best fixed code of all four-hole patterns of 12 bits, scored by the sum over units, waves and
+// lane groups of the deepest stack of one slot.  `addr`: the units' member addresses (canonical index << 4) in the
+// [trip][thread][unit of the trip] layout.  Returns the swz table and the scores (mean and worst slot depth, 1 =
+// conflict free) of the identity and of the chosen map.
+struct SwzChoice { uint64_t swz; double mean0, worst0, mean, worst; };
+SwzChoice choose_bank_swizzle(int lt, const std::vector<uint32_t>& urec, const std::vector<uint32_t>& addr) {
+  const size_t NT = (size_t)1 << lt, nu = urec.size();
+  std::vector<uint8_t> lo, hi;          // per scored (unit, thread): index bits 0..3 and 4..7
+  size_t n_scored = 0;
+  for (size_t u = 0; u < nu; ++u) {
+    if (!urec[u]) continue;             // zero-table padding
+    ++n_scored;
+    for (size_t t = 0; t < NT; ++t) {
+      const uint32_t p = addr[((u / kUnitTrip) * NT + t) * kUnitTrip + u % kUnitTrip] >> 4;
+      lo.push_back((uint8_t)(p & 15u));
+      hi.push_back((uint8_t)((p >> 4) & 15u));
+    }
+  }
+  uint8_t grp[4][16];                   // lanes of the four ds_read_b128 groups
+  for (int g = 0, cnt[4] = {0, 0, 0, 0}; g < 64; ++g) {
+    const int k = ((g >> 5) << 1) | (((g >> 2) ^ (g >> 3) ^ (g >> 4)) & 1);
+    grp[k][cnt[k]++] = (uint8_t)g;
+  }
+  auto table = [](const uint32_t (&c)[4]) {
+    uint64_t t = 0;
+    for (uint32_t v = 0; v < 16; ++v) {
+      uint32_t code = 0;
+      for (int k = 0; k < 4; ++k) if ((v >> k) & 1u) code ^= c[k];
+      t |= (uint64_t)code << (4 * v);
+    }
+    return t;
+  };
+  auto score = [&](uint64_t swz, double* worst) {
+    size_t tot = 0;
+    int w = 1;
+    for (size_t i = 0; i < n_scored * NT; i += 64)
+      for (int k = 0; k < 4; ++k) {
+        int seen[16] = {0}, m = 0;
+        for (int l = 0; l < 16; ++l) {
+          const size_t j = i + grp[k][l];
+          const int s = lo[j] ^ (int)((swz >> (4 * hi[j])) & 15u);
+          m = std::max(m, ++seen[s]);
+        }
+        tot += m;
+        w = std::max(w, m);
+      }
+    if (worst) *worst = w;
+    return n_scored ? (double)tot / (double)(n_scored * NT / 16) : 1.0;
+  };
+  SwzChoice r{0, 1.0, 1.0, 1.0, 1.0};
+  if (!n_scored || lt < 8) return r;
+  r.mean0 = r.mean = score(0, &r.worst0);
+  r.worst = r.worst0;
+  const uint32_t starts[2][4] = {{0u, 0u, 0u, 0u}, {1u, 15u, 2u, 12u}};
+  for (const auto& st : starts) {
+    uint32_t c[4] = {st[0], st[1], st[2], st[3]};
+    double best = score(table(c), nullptr);
+    for (int sweep = 0; sweep < 4; ++sweep) {
+      bool moved = false;
+      for (int k = 0; k < 4; ++k)
+        for (uint32_t v = 0; v < 16; ++v) {
+          const uint32_t keep = c[k];
+          c[k] = v;
+          const double s = score(table(c), nullptr);
+          if (s < best) { best = s; moved = true; } else c[k] = keep;
+        }
+      if (!moved) break;
+    }
+    if (best < r.mean) { r.mean = best; r.swz = table(c); }
+  }
+  if (r.swz) score(r.swz, &r.worst);
+  return r;
+}
+
 // Build (or rebuild after re-sharding) the device Hamiltonian.
 int build_hamiltonian(vqe_t* h) {
   const int n = h->n;
@@ -381,7 +462,7 @@ int build_hamiltonian(vqe_t* h) {
   // register path: canonical index p' = M p (see IndexMap); all masks below are in p'
   const bool reg_path = h->lds_path && n >= kRegMinQubits;
   const int lt = geo_lt(n);                        // Geo<N>::LT of the register path
-  IndexMap im = identity_map(n), pm = identity_map(n);      // pm: the qubit permutation under the units' bank shear
+  IndexMap im = identity_map(n);
   // unit path (8 <= n <= 13): pass 1 in the qubit order as given - which groups are sparse, which qubits are
   // their fixed / selector bits
   const int unit_F = n - 1 - lt;
@@ -417,17 +498,8 @@ int build_hamiltonian(vqe_t* h) {
         dense_xs.push_back(x);
       }
     }
-    if (any_sparse && reg_path) {      // (below the register path the state stays in logical order)
-      pm = choose_permutation(n, lt, dense_xs, hole_freq);
-      // the canonical map of the handle: the permutation followed by the bank shear of the unit path (kSwzCode)
-      im = pm;
-      if (kUnitShear) {
-        for (int i = 0; i < 4 && i < n; ++i)
-          for (int j = 4; j < 8 && j < n; ++j)
-            if ((kSwzCode[j - 4] >> i) & 1u) im.row[i] ^= pm.row[j];
-        finish_inverse(im);
-      }
-    }
+    if (any_sparse && reg_path)      // (below the register path the state stays in logical order)
+      im = choose_permutation(n, lt, dense_xs, hole_freq);
   }
   if (reg_path && !any_sparse) {
     std::vector<uint32_t> xs;
@@ -435,7 +507,7 @@ int build_hamiltonian(vqe_t* h) {
     im = choose_index_map(n, lt, xs);
   }
   // pass 2 in the canonical index space: the units themselves
-  std::vector<uint32_t> urec;
+  std::vector<uint32_t> urec, uaddr;
   std::vector<double> utab;
   if (any_sparse) {
     const size_t NT = (size_t)1 << lt;
@@ -444,10 +516,10 @@ int build_hamiltonian(vqe_t* h) {
     std::vector<int> fixed;
     for (int g : mine) {
       if (!sparse[g]) continue;
-      const uint32_t x = pm.map_x(h->gx_all[g]);      // the cubes are axis aligned in the permuted index, before the shear
+      const uint32_t x = im.map_x(h->gx_all[g]);
       const int sel = 31 - __builtin_clz(x);
       double scale;
-      pair_table(h, g, pm, n, sel, D, &scale);
+      pair_table(h, g, im, n, sel, D, &scale);
       auto rep = [&](size_t q) { return (uint32_t)(((q >> sel) << (sel + 1)) | (q & (((size_t)1 << sel) - 1))); };
       act.clear();
       for (size_t q = 0; q < D.size(); ++q) if (std::fabs(D[q]) > kUnitZeroTol * scale) act.push_back(rep(q));
@@ -466,20 +538,9 @@ int build_hamiltonian(vqe_t* h) {
         if (!dup && n_keys < 8) seen_keys[n_keys++] = key;
       }
       std::sort(seen_keys, seen_keys + n_keys);
-      // deposit masks: the free positions between consecutive holes (holes = fixed bits + selector), byte addresses
-      std::vector<int> holes(fixed);
-      holes.push_back(sel);
-      std::sort(holes.begin(), holes.end());
-      uint32_t m[5] = {0, 0, 0, 0, 0};
-      for (size_t i = 0; i <= holes.size(); ++i) {
-        const int lo = i == 0 ? 0 : holes[i - 1] + 1, hi = i == holes.size() ? n : holes[i];
-        m[i] = (uint32_t)((((uint64_t)1 << hi) - ((uint64_t)1 << lo)) << 4);
-      }
       for (int ki = 0; ki < n_keys; ++ki) {
         const uint32_t s = seen_keys[ki];
-        const uint32_t toff = (uint32_t)(utab.size() * sizeof(double));
-        const uint32_t rec[8] = {m[0], m[1], m[2], m[3], m[4], (kUnitShear ? swz_index(s) : s) << 4, (kUnitShear ? swz_index(x) : x) << 4, toff};
-        urec.insert(urec.end(), rec, rec + 8);
+        urec.push_back(x << 4);
         for (size_t t = 0; t < NT; ++t) {
           uint32_t p0 = s, tb = 0;       // deposit the bits of t into the free positions, ascending
           for (int b = 0; b < n; ++b)
@@ -487,29 +548,32 @@ int build_hamiltonian(vqe_t* h) {
           const size_t q = ((size_t)(p0 >> (sel + 1)) << sel) | (p0 & (((size_t)1 << sel) - 1));
           const double d = D[q];
           utab.push_back(std::fabs(d) > kUnitZeroTol * scale ? d : 0.0);
+          uaddr.push_back(p0 << 4);      // LDS byte address of the selector-0 member (the state is 16 bytes per index)
         }
       }
     }
     if (utab.size() * sizeof(double) + (size_t)kUnitUnroll * NT * sizeof(double) > 0x7FFFFFFFu)
       return fail(h, VQE_EINVAL, "Hamiltonian too large for the LDS-resident path");
-    // padding to a multiple of kUnitUnroll: units with a table of zeros
-    while ((urec.size() / 8) % kUnitUnroll) {
-      const uint32_t rec[8] = {0, 0, 0, 0, 0, 0, 0, (uint32_t)(utab.size() * sizeof(double))};
-      urec.insert(urec.end(), rec, rec + 8);
+    // padding to a multiple of kUnitUnroll: units with a table of zeros (both members at address 0)
+    while (urec.size() % kUnitUnroll) {
+      urec.push_back(0u);
       utab.resize(utab.size() + NT, 0.0);
+      uaddr.resize(uaddr.size() + NT, 0u);
     }
-    // table layout the unit loop reads: per trip of kUnitTrip units [thread][unit of the trip] - a thread's values of a
-    // trip are 32 contiguous bytes (two 16-byte loads instead of four 8-byte ones, one offset computation per trip:
-    // 335.7 -> 331.2 ms on one box)
-    {
-      std::vector<double> t(utab.size());
-      const size_t n_trips = urec.size() / 8 / kUnitTrip;
+    // layout the unit loop reads: per trip of kUnitTrip units [thread][unit of the trip] - a thread's table values of a
+    // trip are 32 contiguous bytes, its addresses 16 (one 16-byte load per 2 table values / 4 addresses instead of one
+    // 8-byte load per unit, one offset computation per trip: 335.7 -> 331.2 ms on one box)
+    auto by_trip = [&](auto& v) {
+      std::remove_reference_t<decltype(v)> t(v.size());
+      const size_t n_trips = urec.size() / kUnitTrip;
       for (size_t T = 0; T < n_trips; ++T)
         for (size_t j = 0; j < (size_t)kUnitTrip; ++j)
           for (size_t th = 0; th < NT; ++th)
-            t[(T * NT + th) * kUnitTrip + j] = utab[(T * kUnitTrip + j) * NT + th];
-      utab.swap(t);
-    }
+            t[(T * NT + th) * kUnitTrip + j] = v[(T * kUnitTrip + j) * NT + th];
+      v.swap(t);
+    };
+    by_trip(utab);
+    by_trip(uaddr);
   }
   auto gxm = [&](int g) { return im.map_x(h->gx_all[g]); };
   // section of a group: 0 diagonal, 1 real with a register bit in x' (register path only),
@@ -596,6 +660,14 @@ int build_hamiltonian(vqe_t* h) {
     }
   }
   enter_section(4);
+  // bank swizzle of the state's LDS copy: register path, units present, and every other group a class group or the
+  // diagonal (the plain table paths read the canonical index; a handle with such groups keeps S = I)
+  SwzChoice sw{0, 1.0, 1.0, 1.0, 1.0};
+  if (reg_path && !urec.empty() && gx.size() == (size_t)(has_diag + n_cls)) sw = choose_bank_swizzle(lt, urec, uaddr);
+  if (sw.swz) {
+    for (uint32_t& a : uaddr) a = swz_slot(sw.swz, a >> 4) << 4;
+    for (uint32_t& x : urec) x = swz_slot(sw.swz, x >> 4) << 4;
+  }
   int rc;
   if ((rc = upload(h, h->d_gx, gx.data(), gx.size()))) return rc;
   if ((rc = upload(h, h->d_tab_r, tab_r.data(), tab_r.size()))) return rc;
@@ -606,6 +678,7 @@ int build_hamiltonian(vqe_t* h) {
   if ((rc = upload(h, h->d_term_cr, term_cr.data(), term_cr.size()))) return rc;
   if ((rc = upload(h, h->d_term_ci, term_ci.data(), term_ci.size()))) return rc;
   if ((rc = upload(h, h->d_urec, urec.data(), urec.size()))) return rc;
+  if ((rc = upload(h, h->d_uaddr, uaddr.data(), uaddr.size()))) return rc;
   if ((rc = upload(h, h->d_utab, utab.data(), utab.size()))) return rc;
   HIP_TRY(h, hipStreamSynchronize(h->stream));  // host vectors go out of scope
   h->ham.n_groups = (int)gx.size();
@@ -617,9 +690,17 @@ int build_hamiltonian(vqe_t* h) {
   h->ham.has_diag = has_diag;
   h->ham.n_real = n_real;
   h->ham.n_cls = n_cls;
-  for (int i = 0; i < 16; ++i) h->ham.mrow[i] = im.row[i];
-  h->ham.n_units = (int)(urec.size() / 8);
+  for (int i = 0; i < 16; ++i) {     // S M: the final scatter writes canonical index p' to LDS slot S(p')
+    uint32_t row = im.row[i];
+    for (int k = 0; i < 4 && k < 4; ++k)
+      if ((sw.swz >> (4 * (1 << k)) >> i) & 1u) row ^= im.row[4 + k];
+    h->ham.mrow[i] = row;
+  }
+  h->ham.swz = sw.swz;
+  h->unit_score[0] = sw.mean0; h->unit_score[1] = sw.worst0; h->unit_score[2] = sw.mean; h->unit_score[3] = sw.worst;
+  h->ham.n_units = (int)urec.size();
   h->ham.urec = h->d_urec.p;
+  h->ham.uaddr = h->d_uaddr.p;
   h->ham.utab = h->d_utab.p;
   h->ham.term_off = h->d_term_off.p;
   h->ham.term_z = h->d_term_z.p;
@@ -1712,6 +1793,13 @@ int vqe_hamiltonian_layout(vqe_t* h, int32_t out[4]) {
   if (!h || !out) return VQE_EINVAL;
   if (!h->ham_set) return fail(h, VQE_ESTATE, "no Hamiltonian set");
   out[0] = h->ham.n_groups; out[1] = h->ham.n_units; out[2] = h->ham.n_cls; out[3] = h->ham.has_diag;
+  return VQE_OK;
+}
+
+int vqe_unit_bank_score(vqe_t* h, double out[4]) {
+  if (!h || !out) return VQE_EINVAL;
+  if (!h->ham_set) return fail(h, VQE_ESTATE, "no Hamiltonian set");
+  for (int i = 0; i < 4; ++i) out[i] = h->unit_score[i];
   return VQE_OK;
 }
 

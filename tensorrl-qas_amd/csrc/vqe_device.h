@@ -115,16 +115,22 @@ struct HamDev {
   // p' = M p (GF(2)-linear, chosen by the host so that the X mask of every real group touches one
   // of the R register bits LT..n-1 of p'); masks and tables below are expressed in p'.
   int n_cls;                // leading real groups whose x' has a register bit (multiple of energy_pd(n))
-  uint32_t mrow[16];        // row i of M: bit i of p' = parity(mrow[i] & p)
+  uint32_t mrow[16];        // row i of S M: bit i of the LDS slot of p' = parity(mrow[i] & p) (the final scatter's map)
+  // LDS bank swizzle of the register path (storage only): canonical index p' lives at LDS slot S(p') = p' ^ code(p'),
+  // code = 4-bit entry (p' >> 4) & 15 of swz (entry v at bits [4v, 4v+4)); GF(2)-linear, 0 = identity.  Chosen by
+  // the host against the unit list's ds_read_b128 lane groups; thread <-> pair ownership does not change.
+  uint64_t swz;
   // unit path (LDS-resident kernels): X-mask groups whose sign-sum table is mostly EXACT zeros (fermionic excitation
   // operators connect one occupation pattern in 2^w) are stored as *units* - sub-cubes of NT pairs on which the table
   // does not vanish - and never enter the group lists above.  A unit fixes F = n-1-LT bit positions (plus the
   // selector bit that tells the two members of a pair apart); thread t owns the pair whose remaining LT index bits
-  // are the bits of t.  urec: 8 words per unit {m0..m4: byte-address masks of the bit deposit, s16: the fixed bits,
-  // x16: the X mask, toff: byte offset of its NT table doubles in utab}; n_units is a multiple of kUnitUnroll
-  // (zero-table padding).
+  // are the bits of t.  urec: one word per unit, its X mask << 4 (the byte-address distance of the pair members);
+  // uaddr: the LDS byte address of the selector-0 member of each (unit, thread), built by the host; utab: the table
+  // values.  uaddr and utab are laid out per trip of kUnitTrip units as [trip][thread][unit of the trip].
+  // n_units is a multiple of kUnitUnroll (zero-table padding).
   int n_units;
   const uint32_t* urec;
+  const uint32_t* uaddr;
   const double* utab;
   // streaming path (n >= 14): explicit terms
   int n_terms;              // terms of the groups above
@@ -134,22 +140,8 @@ struct HamDev {
   const double* term_ci;    // [n_terms]
 };
 
-// LDS bank shear of the unit path.  ds_read_b128 serves a wavefront in four groups of 16 lanes - (lane bit 5, parity of
-// lane bits 2..4) - and a group is conflict free when its 16 lanes hit 16 different 16-byte slots modulo 256 B
-// (MI355X_MICROARCH.md, LDS).  The lanes of a unit differ in the lowest FREE index bits; wherever a low index bit is a
-// hole of the unit (a fixed or the selector bit) the plain layout stacks a group 2, 4 or 8 deep on the same slots:
-// 2.95 x the conflict-free LDS cycles averaged over all four-hole patterns of 12 index bits, 2.14 x for the bench
-// Hamiltonian's 174 units (tools/conflict_model.py).  So the canonical index map gets a shear on top of its qubit
-// permutation: the four low index bits are XORed with a 4-bit code of bits 4..7 (kSwzCode, the best of all 15^4
-// assignments: 1.25 x on average).  The shear is part of the index map M - free in the final scatter of the
-// circuit, invisible to the table paths, which work in canonical space for any M; only the unit loop, whose cubes are
-// axis aligned BEFORE the shear, applies it to the deposited thread id: a 16-entry table of 4-bit codes in one 64-bit
-// constant (entry u at bits [4u, 4u+4)).
-constexpr uint32_t kSwzCode[4] = {1u, 15u, 2u, 12u};
-constexpr unsigned long long kSwzTable = 0x1fe23dccd32ef10ull;
-__host__ __device__ constexpr uint32_t swz_index(uint32_t p) {      // permuted index -> canonical (sheared) index
-  return p ^ (((p >> 4) & 1u) * kSwzCode[0]) ^ (((p >> 5) & 1u) * kSwzCode[1]) ^ (((p >> 6) & 1u) * kSwzCode[2]) ^
-         (((p >> 7) & 1u) * kSwzCode[3]);
+__host__ __device__ inline uint32_t swz_slot(uint64_t swz, uint32_t p) {
+  return p ^ (uint32_t)((swz >> (((p >> 4) & 15u) << 2)) & 15u);
 }
 constexpr int kUnitMinQubits = 8;             // below: a group has no more pairs than a workgroup has threads
 constexpr int kUnitTrip = 4;                  // units per trip of the unit loop
@@ -583,7 +575,7 @@ __device__ __forceinline__ void stage_cls(const HamDev& H, const Lds& L) {
     const int cls = (31 - __clz((int)x)) - LT;
     const uint32_t xr = x >> LT;
     uint32_t* w = (uint32_t*)(L.cm + i);
-    w[0] = (x & ((1u << LT) - 1u)) << 4;
+    w[0] = swz_slot(H.swz, x & ((1u << LT) - 1u)) << 4;     // S(p ^ x) = S(p) ^ S(x)
     w[1] = (uint32_t)cls;
     w[2] = w[3] = 0u;
     for (int j = 0; j < 8; ++j) w[4 + j] = j < NP ? ((insert0((uint32_t)j, cls) ^ xr) << (LT + 4)) : 0u;
@@ -1207,11 +1199,12 @@ __device__ __forceinline__ void pair_fma1(double& acc0, const double2& a0, const
 }
 
 // Unit path: the X-mask groups whose sign-sum tables are mostly exact zeros (HamDev::urec, built by the host).  One
-// pair per thread and unit, both members from LDS: the record (8 scalars, read with scalar loads - the records sit
-// in the constant address space) gives the byte-address masks that deposit the thread id into the free index bits,
-// the fixed bits, the X mask and the offset of the unit's NT table values.  No dispatch of any kind: 7 integer
-// instructions, 2 ds_read_b128, one 8-byte table load and 3 FP64 instructions per unit and thread, against ~60
-// instructions, 8 ds_read_b128 and 64 table bytes for a group of the class path below.
+// pair per thread and unit, both members from LDS.  The host stores, next to each unit's table values, the LDS byte
+// address of the thread's selector-0 pair member (HamDev::uaddr); the other member is that address XOR the unit's X
+// mask, a scalar of the record.  Per unit and thread: one integer instruction, 2 ds_read_b128, 12 bytes of table
+// stream and 3 FP64 instructions, against ~60 instructions, 8 ds_read_b128 and 64 table bytes for a group of the class
+// path below.  (Until the addresses came from the host the thread id was deposited into the unit's free index bits on
+// the device: 7 integer instructions per unit and thread, 329 ms per bench launch.)
 // (Measured and dropped: trips whose four units share ONE deposit - a hopping pair's four units differ in two filler
 // bits only -: 13 instead of 28 integer instructions for 28 of the bench Hamiltonian's 45 trips, but a second loop, its
 // own prologue and padding of both phases to whole turns: 326.4 ms against 327.8, not worth a second code path.)
@@ -1222,50 +1215,44 @@ __device__ __forceinline__ double2 lds_load_abs(uint32_t addr) {
   const d2v_t v = *(const __attribute__((address_space(3))) d2v_t*)(uintptr_t)addr;
   return make_double2(v.x, v.y);
 }
-#ifndef VQE_UNIT_SHEAR
-#define VQE_UNIT_SHEAR 0
-#endif
-constexpr bool kUnitShear = VQE_UNIT_SHEAR != 0;
-typedef uint32_t u32x8_t __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(4))) const u32x8_t const_u32x8;
+typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(4))) const u32x4_t const_u32x4;
 
 template <int N>
 __device__ __forceinline__ void unit_energy(const Lds& L, const HamDev& H, double& acc0, double& acc1) {
   constexpr int LT = Geo<N>::LT;
-  constexpr int SEG = (N - 1 - LT) + 2;      // holes (fixed bits + selector) + 1 runs of free positions
-  static_assert(SEG >= 2 && SEG <= 5, "unit records hold five deposit masks");
   constexpr int U = kUnitTrip;
   static_assert(kUnitUnroll == 3 * kUnitTrip, "three trips per turn of the loop (ring of three table buffers)");
-  constexpr uint32_t TSTRIDE = (uint32_t)8 << LT;   // table bytes of one unit
-  static_assert(U == 4, "the tables of a trip are interleaved [thread][unit of the trip]: two 16-byte loads per thread and trip");
-  constexpr uint32_t TRIP_BYTES = U * TSTRIDE;
+  static_assert(U == 4, "a trip is [thread][unit of the trip]: two 16-byte table loads and one 16-byte address load per thread");
+  constexpr uint32_t TRIP_BYTES = (uint32_t)(8 * U) << LT;     // table bytes of one trip
+  constexpr uint32_t TRIP_ABYTES = (uint32_t)(4 * U) << LT;    // address bytes of one trip
   const int nu = __builtin_amdgcn_readfirstlane(H.n_units);
   if (nu <= 0) return;
   uint32_t tid = threadIdx.x;
   asm volatile("" : "+v"(tid));
   const __amdgpu_buffer_rsrc_t ru = table_rsrc(H.utab);
-  const const_u32x8* rec = (const const_u32x8*)H.urec;
-  uint32_t tsh[SEG];
-#pragma unroll
-  for (int i = 0; i < SEG; ++i) tsh[i] = tid << (4 + i);
-  // A trip = U units.  Table values come from L2 two trips ahead (ring of three register buffers, the loop body is
-  // three trips so that the buffer indices are static).  The records of the next trip are requested into the SAME
-  // scalar registers once the addresses of this trip are formed, and land while its LDS reads are in flight
-  // (scalar and LDS loads share one counter: requested earlier, a wait for a record would also wait for LDS reads).
+  const __amdgpu_buffer_rsrc_t ra = table_rsrc(H.uaddr);
+  const const_u32x4* rec = (const const_u32x4*)H.urec;     // X masks << 4 of the U units of a trip
+  // A trip = U units.  Table values and addresses come from L2 two trips ahead (ring of three register buffers, the
+  // loop body is three trips so that the buffer indices are static).  The X masks of the next trip are requested into
+  // the SAME scalar registers once the partner addresses of this trip are formed, and land while its LDS reads are in
+  // flight (scalar and LDS loads share one counter: requested earlier, a wait for a record would also wait for LDS
+  // reads).
   double d[3][U];
-  u32x8_t R[U];
-#pragma unroll
-  for (int j = 0; j < U; ++j) {
-    R[j] = rec[j];
-  }
+  u32x4_t ad[3];
+  u32x4_t X = rec[0];
   const uint32_t tid32 = tid << 5;      // the thread's U table values of a trip are 32 contiguous bytes
-  auto load_trip = [&](double (&dst)[U], uint32_t first_unit) {
-    const uint32_t soff = (first_unit / U) * TRIP_BYTES;
+  const uint32_t tid16 = tid << 4;      // ... and its U addresses 16
+  auto load_trip = [&](double (&dst)[U], u32x4_t& adst, uint32_t first_unit) {
+    const uint32_t trip = first_unit / U;
+    const v4i_t av = __builtin_amdgcn_raw_buffer_load_b128(ra, (int)tid16, (int)(trip * TRIP_ABYTES), 0);
+    adst = u32x4_t{(uint32_t)av.x, (uint32_t)av.y, (uint32_t)av.z, (uint32_t)av.w};
+    const uint32_t soff = trip * TRIP_BYTES;
     const double2 lo = buf_load_d2(ru, tid32, soff), hi = buf_load_d2(ru, tid32 + 16u, soff);
     dst[0] = lo.x; dst[1] = lo.y; dst[2] = hi.x; dst[3] = hi.y;
   };
-  load_trip(d[0], 0u);
-  load_trip(d[1], (uint32_t)(U < nu ? U : 0));
+  load_trip(d[0], ad[0], 0u);
+  load_trip(d[1], ad[1], (uint32_t)(U < nu ? U : 0));
   const int last = nu - U;       // first unit of the last trip
   for (int u = 0; u < nu; u += 3 * U) {
 #pragma unroll
@@ -1277,20 +1264,8 @@ __device__ __forceinline__ void unit_energy(const Lds& L, const HamDev& H, doubl
       uint32_t a[U], ax[U];
 #pragma unroll
       for (int j = 0; j < U; ++j) {
-        // deposit of the thread id: one v_and_or_b32 per run of free positions (left to itself the compiler builds
-        // an AND / OR3 tree of 7 instructions for the 5 runs)
-        uint32_t v;
-        asm("v_and_b32 %0, %1, %2" : "=v"(v) : "s"(R[j][0]), "v"(tsh[0]));
-#pragma unroll
-        for (int i = 1; i < SEG; ++i) asm("v_and_or_b32 %0, %1, %2, %0" : "+v"(v) : "v"(tsh[i]), "s"(R[j][i]));
-        if constexpr (kUnitShear) {
-          // the bank shear of the canonical index (kSwzTable) on the deposited thread id; the record's fixed bits
-          // and X mask arrive sheared
-          const uint32_t u4 = (v >> 6) & 0x3Cu;                  // 4 x (index bits 4..7)
-          v ^= ((uint32_t)(kSwzTable >> u4) << 4) & 0xF0u;
-        }
-        a[j] = v ^ R[j][5];
-        ax[j] = a[j] ^ R[j][6];
+        a[j] = ad[k][j];
+        asm("v_xor_b32 %0, %1, %2" : "=v"(ax[j]) : "s"(X[j]), "v"(a[j]));
       }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -1298,11 +1273,9 @@ __device__ __forceinline__ void unit_energy(const Lds& L, const HamDev& H, doubl
         pb[j] = lds_load_abs(a[j]);
         pa[j] = lds_load_abs(ax[j]);
       }
-      load_trip(d[(k + 2) % 3], (uint32_t)u2);
+      load_trip(d[(k + 2) % 3], ad[(k + 2) % 3], (uint32_t)u2);
       __builtin_amdgcn_sched_barrier(0);
-      const const_u32x8* rn = rec + u1;
-#pragma unroll
-      for (int j = 0; j < U; ++j) R[j] = rn[j];
+      X = rec[u1 / U];
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int j = 0; j < U; ++j) {
@@ -1340,11 +1313,12 @@ __device__ __forceinline__ double reg_energy(const Lds& L, const HamDev& H, Hook
   static_assert(NP >= 2 && NP <= 8 && PD % 2 == 0, "register energy path: 2..8 pairs per thread");
   uint32_t tid = threadIdx.x;
   asm volatile("" : "+v"(tid));   // opaque: address terms derived from it are rebuilt per evaluation, not kept live across the kernel
+  const uint32_t stid = swz_slot(H.swz, tid);   // LDS slot of the thread's canonical index (the swizzle keeps bits >= 8)
   const double* __restrict__ tables = H.tables;
   lds_cbyte* psi_l = (lds_cbyte*)L.psi;
   double2 own[NA];
 #pragma unroll
-  for (int r = 0; r < NA; ++r) own[r] = lds_load_d2(psi_l, (tid + (uint32_t)r * kThreads) << 4);
+  for (int r = 0; r < NA; ++r) own[r] = lds_load_d2(psi_l, (stid + (uint32_t)r * kThreads) << 4);
   double acc0 = 0.0, acc1 = 0.0;
   int g0 = 0;
   if (H.has_diag) {
@@ -1380,7 +1354,7 @@ __device__ __forceinline__ double reg_energy(const Lds& L, const HamDev& H, Hook
     // addressing records of the group being loaded / the next one: two alternating sets
     uint2 mh[2];
     uint4 mo[2][2];
-    const uint32_t tid16 = tid << 4;
+    const uint32_t tid16 = stid << 4;
     uint32_t tb;
     int ccls;
 #define VQE_R_FETCH(S, GI)                                                                         \
@@ -1456,6 +1430,7 @@ __device__ __forceinline__ double reg_energy(const Lds& L, const HamDev& H, Hook
   after_pairs();
   unit_energy<N>(L, H, acc0, acc1);
   const int g1 = g0 + H.n_real;
+  // (groups of the plain table paths read the canonical index: the host keeps S = I for a handle that has any)
   energy_real_lds<N>(L, tables, gc, g1, acc0, acc1);
   energy_imag_lds<N>(L, tables, g1, H.n_groups, acc0);
   return block_sum<Geo<N>::NW>(acc0 + acc1, L.red);

@@ -146,6 +146,13 @@ class VQEEngine:
         self._chk(self._lib.vqe_hamiltonian_layout(self._h, out))
         return {"table_groups": out[0], "units": out[1], "class_groups": out[2], "has_diag": bool(out[3])}
 
+    def unit_bank_score(self):
+        """Modelled LDS bank conflicts of the unit path: mean / worst lanes per 16-byte slot of a ds_read_b128 lane group
+        with the plain state layout ("plain_*") and with the bank swizzle this handle uses (1.0 = conflict free)."""
+        out = (C.c_double * 4)()
+        self._chk(self._lib.vqe_unit_bank_score(self._h, out))
+        return {"plain_mean": out[0], "plain_worst": out[1], "mean": out[2], "worst": out[3]}
+
     # -- RCCL behind the C ABI (the collective of the term-sharded sum as a library call) -----------
     @staticmethod
     def comm_unique_id() -> bytes:

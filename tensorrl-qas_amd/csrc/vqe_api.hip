@@ -1,14 +1,15 @@
-// vqe_api.hip - host side of libvqe_hip.so: handle management, Hamiltonian layout, batch
-// upload and kernel dispatch behind the C ABI of include/vqe_hip.h.
+// vqe_api.hip - host side of libvqe_hip.so: handle management, upload of the Hamiltonian layout (planned by
+// ham_layout.h), batch upload and kernel dispatch behind the C ABI of include/vqe_hip.h.
 #include "../../include/vqe_hip.h"
 #include "vqe_device.h"
 #include "vqe_stream.h"
 #include "vqe_dm.h"
 #include "vqe_grad.h"
+#include "ham_layout.h"
+#include "dm_host.h"
 
 #include <algorithm>
 #include <cmath>
-#include <complex>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -51,11 +52,7 @@ struct vqe_handle {
   std::string err;
 
   DevBuf<double2> init;
-  // Hamiltonian (host copy, grouped by X mask)
-  std::vector<uint32_t> gx_all;
-  std::vector<std::vector<int>> group_terms;
-  std::vector<uint64_t> hx, hz;
-  std::vector<double> hcr, hci;
+  HamHost ham_host;   // Hamiltonian (host copy, grouped by X mask)
   int shard_rank = 0, shard_world = 1;
   int amp_rank = 0, amp_world = 1;
   bool ham_set = false;
@@ -152,560 +149,39 @@ int upload(vqe_t* h, DevBuf<T>& b, const T* src, size_t n) {
   return VQE_OK;
 }
 
-// Pauli-term sharding: greedy bin packing of X-mask groups over ranks by cost (table length
-// on the LDS path, partner sweep + terms on the streaming path); deterministic, so every
-// rank computes the same partition.
-std::vector<int> assign_groups(const std::vector<uint32_t>& gx, const std::vector<std::vector<int>>& terms,
-                               bool lds_path, int world) {
-  std::vector<int> order(gx.size());
-  for (size_t i = 0; i < order.size(); ++i) order[i] = (int)i;
-  auto cost = [&](int g) -> double {
-    return lds_path ? (gx[g] == 0 ? 2.0 : 1.0) : 1.0 + 0.25 * (double)terms[g].size();
-  };
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return cost(a) > cost(b); });
-  std::vector<double> load(world, 0.0);
-  std::vector<int> owner(gx.size(), 0);
-  for (int g : order) {
-    int best = 0;
-    for (int r = 1; r < world; ++r) if (load[r] < load[best]) best = r;
-    load[best] += cost(g);
-    owner[g] = best;
-  }
-  return owner;
-}
-
-// ---- canonical index map of the register path -----------------------------------------------
-// p' = M p over GF(2).  The top R rows of M are functionals chosen greedily so that as many X
-// masks as possible have a non-zero image in the register bits (every one of them in the
-// molecular Hamiltonians tried); the lower rows complete M to an invertible matrix with unit
-// vectors.  Pauli masks transform as x' = M x, z' = M^-T z.
-struct IndexMap {
-  int n = 0;
-  uint32_t row[32] = {0};      // rows of M (identity beyond the register path's n <= 13)
-  uint32_t inv_col[32] = {0};  // columns of M^-1 (as bit masks over its rows)
-  uint32_t map_x(uint32_t x) const {
-    uint32_t r = 0;
-    for (int i = 0; i < n; ++i) r |= (uint32_t)(__builtin_popcount(row[i] & x) & 1) << i;
-    return r;
-  }
-  uint32_t map_z(uint32_t z) const {
-    uint32_t r = 0;
-    for (int i = 0; i < n; ++i) r |= (uint32_t)(__builtin_popcount(inv_col[i] & z) & 1) << i;
-    return r;
-  }
-};
-
-IndexMap identity_map(int n) {
-  IndexMap m;
-  m.n = n;
-  for (int i = 0; i < n; ++i) m.row[i] = m.inv_col[i] = 1u << i;
-  return m;
-}
-
-// M^-1 by Gauss-Jordan on [M | I] (rows as bit masks) -> inv_col
-void finish_inverse(IndexMap& m) {
-  const int n = m.n;
-  uint32_t a[32], inv[32];
-  for (int i = 0; i < n; ++i) { a[i] = m.row[i]; inv[i] = 1u << i; }
-  for (int c = 0; c < n; ++c) {
-    int piv = c;
-    while (piv < n && !((a[piv] >> c) & 1u)) ++piv;
-    std::swap(a[c], a[piv]);
-    std::swap(inv[c], inv[piv]);
-    for (int r = 0; r < n; ++r)
-      if (r != c && ((a[r] >> c) & 1u)) { a[r] ^= a[c]; inv[r] ^= inv[c]; }
-  }
-  for (int i = 0; i < n; ++i) {
-    uint32_t col = 0;
-    for (int j = 0; j < n; ++j) col |= ((inv[j] >> i) & 1u) << j;
-    m.inv_col[i] = col;
-  }
-}
-
-IndexMap choose_index_map(int n, int lt, const std::vector<uint32_t>& xs) {
-  IndexMap m;
-  m.n = n;
-  const int R = n - lt;
-  std::vector<uint32_t> rem(xs), rows;     // masks not yet hit / chosen functionals (any order)
-  uint32_t ech[32] = {0};                  // echelon basis of the chosen rows, by highest bit
-  auto independent = [&](uint32_t v) {
-    for (int bit = n - 1; bit >= 0 && v; --bit)
-      if (((v >> bit) & 1u) && ech[bit]) v ^= ech[bit];
-    return v;
-  };
-  auto add_row = [&](uint32_t f) {
-    const uint32_t red = independent(f);
-    ech[31 - __builtin_clz(red)] = red;
-    rows.push_back(f);
-  };
-  for (int i = 0; i < R; ++i) {
-    uint32_t best = 0;
-    int best_hits = -1;
-    if (!rem.empty()) {
-      for (uint32_t f = 1; f < (1u << n); ++f) {
-        int hits = 0;
-        for (uint32_t x : rem) hits += __builtin_popcount(f & x) & 1;
-        if (hits > best_hits && independent(f)) { best_hits = hits; best = f; }
-      }
-    }
-    if (best_hits <= 0) {   // nothing left to hit: any independent unit functional
-      for (int bit = n - 1; bit >= 0; --bit) if (independent(1u << bit)) { best = 1u << bit; break; }
-    }
-    add_row(best);
-    std::vector<uint32_t> keep;
-    for (uint32_t x : rem) if (!(__builtin_popcount(best & x) & 1)) keep.push_back(x);
-    rem.swap(keep);
-  }
-  for (int i = 0; i < R; ++i) m.row[lt + i] = rows[i];
-  int filled = 0;
-  for (int bit = 0; bit < n && filled < lt; ++bit)
-    if (independent(1u << bit)) { add_row(1u << bit); m.row[filled++] = 1u << bit; }
-  finish_inverse(m);
-  return m;
-}
-
-// ---- unit path: X-mask groups with mostly-zero sign-sum tables -------------------------------------
-// The sign-sum table D_x(p) = sum_k c_k (-1)^{popc(p & z_k)} of a fermionic excitation operator vanishes EXACTLY on
-// every pair {p, p^x} whose occupation pattern the operator does not connect (a hopping pair XZ..ZX + YZ..ZY acts on
-// 01 <-> 10 only, a double-excitation octet on one pattern pair in eight): 76 % of the entries of the bench
-// Hamiltonian, 69 % of the shipped H2O one.  A group is cut into sub-cubes of NT pairs (fix F = n-1-LT index bits
-// besides the selector bit); only sub-cubes on which D does not vanish become *units* (HamDev::urec).
-// Entries below kUnitZeroTol x sum_k |c_k| are rounding residues of sums that cancel exactly in real arithmetic
-// (3w - w - w - w is not 0 in floating point) and count as zero.
-constexpr double kUnitZeroTol = 0x1p-44;       // 5.7e-14 relative: far above the residues (~1e-16), far below any term
-
-// a permutation of the qubits as canonical index map: position lt.. (the register bits of the class path) cover
-// the masks of the dense groups, the other qubits are placed by how often they are a fixed / selector bit of a
-// unit - the most frequent ones highest, so that the lowest index bits (consecutive lanes, LDS banks) stay free
-IndexMap choose_permutation(int n, int lt, const std::vector<uint32_t>& dense_xs, const std::vector<int>& hole_freq) {
-  IndexMap m;
-  m.n = n;
-  std::vector<int> at(n, -1);            // qubit at canonical position i
-  std::vector<bool> used(n, false);
-  std::vector<uint32_t> rem(dense_xs);
-  for (int pos = n - 1; pos >= 0; --pos) {
-    int best = -1;
-    if (pos >= lt && !rem.empty()) {
-      int best_hits = 0;
-      for (int q = 0; q < n; ++q) {
-        if (used[q]) continue;
-        int hits = 0;
-        for (uint32_t x : rem) hits += (x >> q) & 1u;
-        if (hits > best_hits) { best_hits = hits; best = q; }
-      }
-      if (best >= 0) {
-        std::vector<uint32_t> keep;
-        for (uint32_t x : rem) if (!((x >> best) & 1u)) keep.push_back(x);
-        rem.swap(keep);
-      }
-    }
-    if (best < 0)
-      for (int q = n - 1; q >= 0; --q)
-        if (!used[q] && (best < 0 || hole_freq[q] > hole_freq[best])) best = q;
-    used[best] = true;
-    at[pos] = best;
-  }
-  for (int i = 0; i < n; ++i) m.row[i] = m.inv_col[i] = 1u << at[i];
-  return m;
-}
-
-// sign-sum table of a real group over pair representatives p0 = insert0(q, sel) in the index space of `im`
-// (factor 2 of the pair symmetry included, as in the pair tables of the group lists)
-void pair_table(const vqe_t* h, int g, const IndexMap& im, int n, int sel, std::vector<double>& D, double* scale) {
-  const size_t len = (size_t)1 << (n - 1);
-  D.assign(len, 0.0);
-  *scale = 0.0;
-  for (int k : h->group_terms[g]) {
-    const uint32_t z = im.map_z((uint32_t)h->hz[k]);
-    const double c = 2.0 * h->hcr[k];
-    *scale += std::fabs(c);
-    for (size_t q = 0; q < len; ++q) {
-      const uint32_t p0 = (uint32_t)(((q >> sel) << (sel + 1)) | (q & (((size_t)1 << sel) - 1)));
-      D[q] += (__builtin_popcount(p0 & z) & 1) ? -c : c;
-    }
-  }
-}
-
-// Fixed bits of a group's units: greedily the index bits (not the selector) on which the active pairs agree most;
-// stops when no bit helps any more (every remaining one doubles the number of active patterns).  Returns the
-// number of active patterns on `fixed`; the units of the group are patterns x 2^(F - |fixed|) (filler bits).
-int choose_fixed_bits(int n, int sel, int F, const std::vector<uint32_t>& act, std::vector<int>& fixed) {
-  fixed.clear();
-  if (act.empty()) return 0;
-  int patterns = 1;
-  auto count = [&](int extra) {
-    uint32_t seen = 0;
-    for (uint32_t p0 : act) {
-      uint32_t key = 0;
-      for (size_t i = 0; i < fixed.size(); ++i) key |= ((p0 >> fixed[i]) & 1u) << i;
-      key |= ((p0 >> extra) & 1u) << fixed.size();
-      seen |= 1u << key;
-    }
-    return __builtin_popcount(seen);
-  };
-  while ((int)fixed.size() < F) {
-    int best = -1, best_cnt = 1 << 30;
-    for (int b = n - 1; b >= 0; --b) {
-      if (b == sel || std::find(fixed.begin(), fixed.end(), b) != fixed.end()) continue;
-      const int c = count(b);
-      if (c < best_cnt) { best_cnt = c; best = b; }
-    }
-    if (best < 0 || best_cnt >= 2 * patterns) break;
-    fixed.push_back(best);
-    patterns = best_cnt;
-  }
-  return patterns;
-}
-
-// LDS bank swizzle of the register path (HamDev::swz).  ds_read_b128 serves a wavefront in four groups of 16 lanes -
-// (lane bit 5, parity of lane bits 2..4) - and a group is conflict free when its 16 lanes hit 16 different 16-byte
-// slots modulo 256 B, i.e. 16 different values of index bits 0..3.  The lanes of a unit differ in its free index bits;
-// where a low index bit is a hole of the unit (a fixed or the selector bit) the plain layout stacks a group 2, 4 or 8
-// deep.  S XORs bits 0..3 with a linear code of bits 4..7: codes c[k] for bit 4+k, coordinate descent from the
-// identity and from the best fixed code of all four-hole patterns of 12 bits, scored by the sum over units, waves and
-// lane groups of the deepest stack of one slot.  `addr`: the units' member addresses (canonical index << 4) in the
-// [trip][thread][unit of the trip] layout.  Returns the swz table and the scores (mean and worst slot depth, 1 =
-// conflict free) of the identity and of the chosen map.
-struct SwzChoice { uint64_t swz; double mean0, worst0, mean, worst; };
-SwzChoice choose_bank_swizzle(int lt, const std::vector<uint32_t>& urec, const std::vector<uint32_t>& addr) {
-  const size_t NT = (size_t)1 << lt, nu = urec.size();
-  std::vector<uint8_t> lo, hi;          // per scored (unit, thread): index bits 0..3 and 4..7
-  size_t n_scored = 0;
-  for (size_t u = 0; u < nu; ++u) {
-    if (!urec[u]) continue;             // zero-table padding
-    ++n_scored;
-    for (size_t t = 0; t < NT; ++t) {
-      const uint32_t p = addr[((u / kUnitTrip) * NT + t) * kUnitTrip + u % kUnitTrip] >> 4;
-      lo.push_back((uint8_t)(p & 15u));
-      hi.push_back((uint8_t)((p >> 4) & 15u));
-    }
-  }
-  uint8_t grp[4][16];                   // lanes of the four ds_read_b128 groups
-  for (int g = 0, cnt[4] = {0, 0, 0, 0}; g < 64; ++g) {
-    const int k = ((g >> 5) << 1) | (((g >> 2) ^ (g >> 3) ^ (g >> 4)) & 1);
-    grp[k][cnt[k]++] = (uint8_t)g;
-  }
-  auto table = [](const uint32_t (&c)[4]) {
-    uint64_t t = 0;
-    for (uint32_t v = 0; v < 16; ++v) {
-      uint32_t code = 0;
-      for (int k = 0; k < 4; ++k) if ((v >> k) & 1u) code ^= c[k];
-      t |= (uint64_t)code << (4 * v);
-    }
-    return t;
-  };
-  auto score = [&](uint64_t swz, double* worst) {
-    size_t tot = 0;
-    int w = 1;
-    for (size_t i = 0; i < n_scored * NT; i += 64)
-      for (int k = 0; k < 4; ++k) {
-        int seen[16] = {0}, m = 0;
-        for (int l = 0; l < 16; ++l) {
-          const size_t j = i + grp[k][l];
-          const int s = lo[j] ^ (int)((swz >> (4 * hi[j])) & 15u);
-          m = std::max(m, ++seen[s]);
-        }
-        tot += m;
-        w = std::max(w, m);
-      }
-    if (worst) *worst = w;
-    return n_scored ? (double)tot / (double)(n_scored * NT / 16) : 1.0;
-  };
-  SwzChoice r{0, 1.0, 1.0, 1.0, 1.0};
-  if (!n_scored || lt < 8) return r;
-  r.mean0 = r.mean = score(0, &r.worst0);
-  r.worst = r.worst0;
-  const uint32_t starts[2][4] = {{0u, 0u, 0u, 0u}, {1u, 15u, 2u, 12u}};
-  for (const auto& st : starts) {
-    uint32_t c[4] = {st[0], st[1], st[2], st[3]};
-    double best = score(table(c), nullptr);
-    for (int sweep = 0; sweep < 4; ++sweep) {
-      bool moved = false;
-      for (int k = 0; k < 4; ++k)
-        for (uint32_t v = 0; v < 16; ++v) {
-          const uint32_t keep = c[k];
-          c[k] = v;
-          const double s = score(table(c), nullptr);
-          if (s < best) { best = s; moved = true; } else c[k] = keep;
-        }
-      if (!moved) break;
-    }
-    if (best < r.mean) { r.mean = best; r.swz = table(c); }
-  }
-  if (r.swz) score(r.swz, &r.worst);
-  return r;
-}
-
-// Build (or rebuild after re-sharding) the device Hamiltonian.
+// Build (or rebuild after re-sharding) the device Hamiltonian: plan the layout on the host (ham_layout.h), upload it.
 int build_hamiltonian(vqe_t* h) {
-  const int n = h->n;
   ++h->gen;
   ++h->ham_ver;
-  const std::vector<int> owner = assign_groups(h->gx_all, h->group_terms, h->lds_path, h->shard_world);
-  std::vector<int> mine;
-  for (size_t g = 0; g < owner.size(); ++g) if (owner[g] == h->shard_rank) mine.push_back((int)g);
-  std::sort(mine.begin(), mine.end());
-
-  std::vector<uint32_t> gx;
-  std::vector<int32_t> term_off{0};
-  std::vector<uint32_t> term_z;
-  std::vector<double> term_cr, term_ci;
-  const size_t dim = (size_t)1 << n;
-  std::vector<int32_t> tab_r, tab_i;
-  std::vector<double> tables;
-  // LDS-path order: diagonal group first, then real-table groups (padded with zero-table
-  // dummy groups to a multiple of energy_pd(n)), then groups that also need an imaginary table.
-  auto group_has_im = [&](int g) {
-    for (int k : h->group_terms[g]) if (h->hci[k] != 0.0) return true;
-    return false;
-  };
-  // register path: canonical index p' = M p (see IndexMap); all masks below are in p'
-  const bool reg_path = h->lds_path && n >= kRegMinQubits;
-  const int lt = geo_lt(n);                        // Geo<N>::LT of the register path
-  IndexMap im = identity_map(n);
-  // unit path (8 <= n <= 13): pass 1 in the qubit order as given - which groups are sparse, which qubits are
-  // their fixed / selector bits
-  const int unit_F = n - 1 - lt;
   static const bool units_on = [] { const char* e = std::getenv("VQE_UNITS"); return !(e && e[0] == '0'); }();   // A/B knob
-  std::vector<char> sparse(h->gx_all.size(), 0);
-  bool any_sparse = false;
-  if (h->lds_path && n >= kUnitMinQubits && units_on && unit_F >= 1) {
-    std::vector<int> hole_freq(n, 0);
-    std::vector<uint32_t> dense_xs;
-    std::vector<double> D;
-    std::vector<uint32_t> act;
-    std::vector<int> fixed;
-    for (int g : mine) {
-      const uint32_t x = h->gx_all[g];
-      if (!x || group_has_im(g)) continue;
-      const int sel = 31 - __builtin_clz(x);
-      double scale;
-      pair_table(h, g, im, n, sel, D, &scale);
-      act.clear();
-      for (size_t q = 0; q < D.size(); ++q)
-        if (std::fabs(D[q]) > kUnitZeroTol * scale)
-          act.push_back((uint32_t)(((q >> sel) << (sel + 1)) | (q & (((size_t)1 << sel) - 1))));
-      const int patterns = choose_fixed_bits(n, sel, unit_F, act, fixed);
-      const int units = patterns << (unit_F - (int)fixed.size());
-      // a unit costs 2 LDS reads, a group of the class path 2^(F+1) / 2: sparse when no more than half of its
-      // sub-cubes are active
-      if (2 * units <= (1 << unit_F)) {
-        sparse[g] = 1;
-        any_sparse = true;
-        for (int b : fixed) ++hole_freq[b];
-        ++hole_freq[sel];
-      } else {
-        dense_xs.push_back(x);
-      }
-    }
-    if (any_sparse && reg_path)      // (below the register path the state stays in logical order)
-      im = choose_permutation(n, lt, dense_xs, hole_freq);
-  }
-  if (reg_path && !any_sparse) {
-    std::vector<uint32_t> xs;
-    for (int g : mine) if (h->gx_all[g] && !group_has_im(g)) xs.push_back(h->gx_all[g]);
-    im = choose_index_map(n, lt, xs);
-  }
-  // pass 2 in the canonical index space: the units themselves
-  std::vector<uint32_t> urec, uaddr;
-  std::vector<double> utab;
-  if (any_sparse) {
-    const size_t NT = (size_t)1 << lt;
-    std::vector<double> D;
-    std::vector<uint32_t> act;
-    std::vector<int> fixed;
-    for (int g : mine) {
-      if (!sparse[g]) continue;
-      const uint32_t x = im.map_x(h->gx_all[g]);
-      const int sel = 31 - __builtin_clz(x);
-      double scale;
-      pair_table(h, g, im, n, sel, D, &scale);
-      auto rep = [&](size_t q) { return (uint32_t)(((q >> sel) << (sel + 1)) | (q & (((size_t)1 << sel) - 1))); };
-      act.clear();
-      for (size_t q = 0; q < D.size(); ++q) if (std::fabs(D[q]) > kUnitZeroTol * scale) act.push_back(rep(q));
-      choose_fixed_bits(n, sel, unit_F, act, fixed);
-      // filler bits: the highest positions that are neither fixed nor the selector
-      for (int b = n - 1; b >= 0 && (int)fixed.size() < unit_F; --b)
-        if (b != sel && std::find(fixed.begin(), fixed.end(), b) == fixed.end()) fixed.push_back(b);
-      uint32_t fmask = 0;
-      for (int b : fixed) fmask |= 1u << b;
-      uint32_t seen_keys[8];
-      int n_keys = 0;
-      for (uint32_t p0 : act) {       // distinct patterns of the fixed bits among the active pairs
-        const uint32_t key = p0 & fmask;
-        bool dup = false;
-        for (int i = 0; i < n_keys; ++i) dup |= seen_keys[i] == key;
-        if (!dup && n_keys < 8) seen_keys[n_keys++] = key;
-      }
-      std::sort(seen_keys, seen_keys + n_keys);
-      for (int ki = 0; ki < n_keys; ++ki) {
-        const uint32_t s = seen_keys[ki];
-        urec.push_back(x << 4);
-        for (size_t t = 0; t < NT; ++t) {
-          uint32_t p0 = s, tb = 0;       // deposit the bits of t into the free positions, ascending
-          for (int b = 0; b < n; ++b)
-            if (!((fmask >> b) & 1u) && b != sel) { p0 |= (uint32_t)((t >> tb) & 1u) << b; ++tb; }
-          const size_t q = ((size_t)(p0 >> (sel + 1)) << sel) | (p0 & (((size_t)1 << sel) - 1));
-          const double d = D[q];
-          utab.push_back(std::fabs(d) > kUnitZeroTol * scale ? d : 0.0);
-          uaddr.push_back(p0 << 4);      // LDS byte address of the selector-0 member (the state is 16 bytes per index)
-        }
-      }
-    }
-    if (utab.size() * sizeof(double) + (size_t)kUnitUnroll * NT * sizeof(double) > 0x7FFFFFFFu)
-      return fail(h, VQE_EINVAL, "Hamiltonian too large for the LDS-resident path");
-    // padding to a multiple of kUnitUnroll: units with a table of zeros (both members at address 0)
-    while (urec.size() % kUnitUnroll) {
-      urec.push_back(0u);
-      utab.resize(utab.size() + NT, 0.0);
-      uaddr.resize(uaddr.size() + NT, 0u);
-    }
-    // layout the unit loop reads: per trip of kUnitTrip units [thread][unit of the trip] - a thread's table values of a
-    // trip are 32 contiguous bytes, its addresses 16 (one 16-byte load per 2 table values / 4 addresses instead of one
-    // 8-byte load per unit, one offset computation per trip: 335.7 -> 331.2 ms on one box)
-    auto by_trip = [&](auto& v) {
-      std::remove_reference_t<decltype(v)> t(v.size());
-      const size_t n_trips = urec.size() / kUnitTrip;
-      for (size_t T = 0; T < n_trips; ++T)
-        for (size_t j = 0; j < (size_t)kUnitTrip; ++j)
-          for (size_t th = 0; th < NT; ++th)
-            t[(T * NT + th) * kUnitTrip + j] = v[(T * kUnitTrip + j) * NT + th];
-      v.swap(t);
-    };
-    by_trip(utab);
-    by_trip(uaddr);
-  }
-  auto gxm = [&](int g) { return im.map_x(h->gx_all[g]); };
-  // section of a group: 0 diagonal, 1 real with a register bit in x' (register path only),
-  // 2 other real groups, 3 groups that also need an imaginary table
-  auto rank_of = [&](int g) {
-    if (group_has_im(g)) return 3;
-    const uint32_t x = gxm(g);
-    if (x == 0) return 0;
-    return reg_path && (x >> lt) ? 1 : 2;
-  };
-  // ... and inside a section by the top bit of x'
-  auto top_bit = [&](int g) { const uint32_t x = gxm(g); return x ? 31 - __builtin_clz(x) : -1; };
-  if (h->lds_path)
-    std::stable_sort(mine.begin(), mine.end(), [&](int a, int b) {
-      return rank_of(a) != rank_of(b) ? rank_of(a) < rank_of(b) : top_bit(a) > top_bit(b);
-    });
-  int has_diag = 0, n_real = 0, n_cls = 0;
-  auto add_dummy = [&](uint32_t xd) {   // zero table: pads a section to a multiple of energy_pd(n)
-    gx.push_back(xd);
-    term_off.push_back((int32_t)term_z.size());
-    tab_r.push_back((int32_t)tables.size());
-    tab_i.push_back(-1);
-    tables.resize(tables.size() + dim / 2, 0.0);
-  };
-  int cur_rank = 0;
-  auto enter_section = [&](int rank) {   // rank 4 = end of the list
-    if (h->lds_path) {
-      if (cur_rank <= 1 && rank >= 2) while (n_cls % energy_pd(n)) { add_dummy(1u << lt); ++n_cls; ++n_real; }
-      if (cur_rank <= 2 && rank >= 3) while ((n_real - n_cls) % energy_pd(n)) { add_dummy(1u); ++n_real; }
-    }
-    cur_rank = rank;
-  };
-  for (int g : mine) {
-    if (sparse[g]) continue;         // lives in the unit list
-    const uint32_t x = gxm(g);
-    const bool has_im = group_has_im(g);
-    const int rank = rank_of(g);
-    enter_section(rank);
-    gx.push_back(x);
-    for (int k : h->group_terms[g]) {
-      term_z.push_back(im.map_z((uint32_t)h->hz[k]));
-      term_cr.push_back(h->hcr[k]);
-      term_ci.push_back(h->hci[k]);
-    }
-    term_off.push_back((int32_t)term_z.size());
-    if (h->lds_path) {
-      if (rank == 0) has_diag = 1; else if (!has_im) ++n_real;
-      if (rank == 1) ++n_cls;
-      const size_t len = x == 0 ? dim : dim / 2;
-      const int hb = x == 0 ? 0 : 31 - __builtin_clz(x);
-      if (tables.size() + 2 * len > 0x7FFFFFFFu) return fail(h, VQE_EINVAL, "Hamiltonian too large for the LDS-resident path");
-      tab_r.push_back((int32_t)tables.size());
-      tables.resize(tables.size() + len, 0.0);
-      if (has_im) { tab_i.push_back((int32_t)tables.size()); tables.resize(tables.size() + len, 0.0); }
-      else tab_i.push_back(-1);
-      double* tr = tables.data() + tab_r.back();
-      double* ti = has_im ? tables.data() + tab_i.back() : nullptr;
-      // index of the pair member that entry q of the table belongs to
-      std::vector<uint32_t> pidx(len);
-      for (size_t q = 0; q < len; ++q) {
-        if (x == 0) pidx[q] = (uint32_t)q;
-        else if (rank == 1) {   // [j/2][tid][j&1] with r = insert0(j, cls), p' = tid | r << lt
-          const int cls = hb - lt;
-          const uint32_t t = (uint32_t)((q >> 1) & (((size_t)1 << lt) - 1));
-          const uint32_t j = (uint32_t)(((q >> (lt + 1)) << 1) | (q & 1));
-          const uint32_t r = ((j >> cls) << (cls + 1)) | (j & ((1u << cls) - 1u));
-          pidx[q] = t | (r << lt);
-        } else {
-          pidx[q] = (uint32_t)(((q >> hb) << (hb + 1)) | (q & (((size_t)1 << hb) - 1)));
-        }
-      }
-      for (int k : h->group_terms[g]) {
-        const uint32_t z = im.map_z((uint32_t)h->hz[k]);
-        for (size_t q = 0; q < len; ++q) {
-          // pair tables carry the factor 2 of the p <-> p^x symmetry
-          const double sgn = ((__builtin_popcount(pidx[q] & z) & 1) ? -1.0 : 1.0) * (x == 0 ? 1.0 : 2.0);
-          tr[q] += sgn * h->hcr[k];
-          if (ti) ti[q] += sgn * h->hci[k];
-        }
-      }
-    } else {
-      tab_r.push_back(0);
-      tab_i.push_back(has_im ? 0 : -1);
-    }
-  }
-  enter_section(4);
-  // bank swizzle of the state's LDS copy: register path, units present, and every other group a class group or the
-  // diagonal (the plain table paths read the canonical index; a handle with such groups keeps S = I)
-  SwzChoice sw{0, 1.0, 1.0, 1.0, 1.0};
-  if (reg_path && !urec.empty() && gx.size() == (size_t)(has_diag + n_cls)) sw = choose_bank_swizzle(lt, urec, uaddr);
-  if (sw.swz) {
-    for (uint32_t& a : uaddr) a = swz_slot(sw.swz, a >> 4) << 4;
-    for (uint32_t& x : urec) x = swz_slot(sw.swz, x >> 4) << 4;
-  }
+  HamLayout L;
+  std::string err;
+  if (!plan_hamiltonian(h->ham_host, h->n, h->lds_path, h->shard_rank, h->shard_world, units_on, L, err))
+    return fail(h, VQE_EINVAL, err);
   int rc;
-  if ((rc = upload(h, h->d_gx, gx.data(), gx.size()))) return rc;
-  if ((rc = upload(h, h->d_tab_r, tab_r.data(), tab_r.size()))) return rc;
-  if ((rc = upload(h, h->d_tab_i, tab_i.data(), tab_i.size()))) return rc;
-  if ((rc = upload(h, h->d_tables, tables.data(), tables.size()))) return rc;
-  if ((rc = upload(h, h->d_term_off, term_off.data(), term_off.size()))) return rc;
-  if ((rc = upload(h, h->d_term_z, term_z.data(), term_z.size()))) return rc;
-  if ((rc = upload(h, h->d_term_cr, term_cr.data(), term_cr.size()))) return rc;
-  if ((rc = upload(h, h->d_term_ci, term_ci.data(), term_ci.size()))) return rc;
-  if ((rc = upload(h, h->d_urec, urec.data(), urec.size()))) return rc;
-  if ((rc = upload(h, h->d_uaddr, uaddr.data(), uaddr.size()))) return rc;
-  if ((rc = upload(h, h->d_utab, utab.data(), utab.size()))) return rc;
-  HIP_TRY(h, hipStreamSynchronize(h->stream));  // host vectors go out of scope
-  h->ham.n_groups = (int)gx.size();
-  h->ham.n_terms = (int)term_z.size();
-  h->ham.gx = h->d_gx.p;
-  h->ham.tab_r = h->d_tab_r.p;
-  h->ham.tab_i = h->d_tab_i.p;
-  h->ham.tables = h->d_tables.p;
-  h->ham.has_diag = has_diag;
-  h->ham.n_real = n_real;
-  h->ham.n_cls = n_cls;
-  for (int i = 0; i < 16; ++i) {     // S M: the final scatter writes canonical index p' to LDS slot S(p')
-    uint32_t row = im.row[i];
-    for (int k = 0; i < 4 && k < 4; ++k)
-      if ((sw.swz >> (4 * (1 << k)) >> i) & 1u) row ^= im.row[4 + k];
-    h->ham.mrow[i] = row;
-  }
-  h->ham.swz = sw.swz;
-  h->unit_score[0] = sw.mean0; h->unit_score[1] = sw.worst0; h->unit_score[2] = sw.mean; h->unit_score[3] = sw.worst;
-  h->ham.n_units = (int)urec.size();
-  h->ham.urec = h->d_urec.p;
-  h->ham.uaddr = h->d_uaddr.p;
-  h->ham.utab = h->d_utab.p;
-  h->ham.term_off = h->d_term_off.p;
-  h->ham.term_z = h->d_term_z.p;
-  h->ham.term_cr = h->d_term_cr.p;
-  h->ham.term_ci = h->d_term_ci.p;
+  if ((rc = upload(h, h->d_gx, L.gx.data(), L.gx.size()))) return rc;
+  if ((rc = upload(h, h->d_tab_r, L.tab_r.data(), L.tab_r.size()))) return rc;
+  if ((rc = upload(h, h->d_tab_i, L.tab_i.data(), L.tab_i.size()))) return rc;
+  if ((rc = upload(h, h->d_tables, L.tables.data(), L.tables.size()))) return rc;
+  if ((rc = upload(h, h->d_term_off, L.term_off.data(), L.term_off.size()))) return rc;
+  if ((rc = upload(h, h->d_term_z, L.term_z.data(), L.term_z.size()))) return rc;
+  if ((rc = upload(h, h->d_term_cr, L.term_cr.data(), L.term_cr.size()))) return rc;
+  if ((rc = upload(h, h->d_term_ci, L.term_ci.data(), L.term_ci.size()))) return rc;
+  if ((rc = upload(h, h->d_urec, L.urec.data(), L.urec.size()))) return rc;
+  if ((rc = upload(h, h->d_uaddr, L.uaddr.data(), L.uaddr.size()))) return rc;
+  if ((rc = upload(h, h->d_utab, L.utab.data(), L.utab.size()))) return rc;
+  HIP_TRY(h, hipStreamSynchronize(h->stream));  // the layout goes out of scope
+  HamDev& d = h->ham;
+  d.n_groups = (int)L.gx.size();
+  d.n_terms = (int)L.term_z.size();
+  d.n_units = (int)L.urec.size();
+  d.gx = h->d_gx.p; d.tab_r = h->d_tab_r.p; d.tab_i = h->d_tab_i.p; d.tables = h->d_tables.p;
+  d.urec = h->d_urec.p; d.uaddr = h->d_uaddr.p; d.utab = h->d_utab.p;
+  d.term_off = h->d_term_off.p; d.term_z = h->d_term_z.p; d.term_cr = h->d_term_cr.p; d.term_ci = h->d_term_ci.p;
+  d.has_diag = L.has_diag; d.n_real = L.n_real; d.n_cls = L.n_cls;
+  std::copy(L.mrow, L.mrow + 16, d.mrow);
+  d.swz = L.swz;
+  h->unit_score[0] = L.mean0; h->unit_score[1] = L.worst0; h->unit_score[2] = L.mean; h->unit_score[3] = L.worst;
   return VQE_OK;
 }
 
@@ -1086,145 +562,18 @@ int stream_run(vqe_t* h, int which, BatchArgs& A) {
   return VQE_OK;
 }
 
-// ---- exact channel mode (vqe_dm.h) -----------------------------------------------------------------
-typedef std::complex<double> cplx;
-struct Sup { cplx m[16][16]; };      // superoperator on the window: entry index e = i + 4 j, i = ket bits (a, b), j = bra bits
-
-void sup_identity(Sup& S) {
-  for (int r = 0; r < 16; ++r) for (int c = 0; c < 16; ++c) S.m[r][c] = r == c ? 1.0 : 0.0;
-}
-// rho -> U rho U^+ :  S[(i, j), (i', j')] = U[i][i'] conj(U[j][j'])
-void sup_conj(const cplx U[4][4], Sup& S) {
-  for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) for (int ip = 0; ip < 4; ++ip) for (int jp = 0; jp < 4; ++jp)
-    S.m[i + 4 * j][ip + 4 * jp] = U[i][ip] * std::conj(U[j][jp]);
-}
-void sup_apply(Sup& acc, const Sup& G) {      // acc <- G acc
-  Sup t;
-  for (int r = 0; r < 16; ++r) for (int c = 0; c < 16; ++c) {
-    cplx v = 0.0;
-    for (int k = 0; k < 16; ++k) v += G.m[r][k] * acc.m[k][c];
-    t.m[r][c] = v;
-  }
-  acc = t;
-}
-// one-qubit operator on window position pos (0: qubit a = bit 0 of the 2-bit index, 1: qubit b)
-void embed_1q(const cplx R[2][2], int pos, cplx U[4][4]) {
-  for (int i = 0; i < 4; ++i) for (int ip = 0; ip < 4; ++ip) {
-    const int other = pos ^ 1;
-    U[i][ip] = (((i >> other) & 1) == ((ip >> other) & 1)) ? R[(i >> pos) & 1][(ip >> pos) & 1] : cplx(0.0);
-  }
-}
-void pauli_1q(int p, cplx R[2][2]) {          // 0 I, 1 X, 2 Y, 3 Z
-  R[0][0] = R[0][1] = R[1][0] = R[1][1] = 0.0;
-  if (p == 0) { R[0][0] = R[1][1] = 1.0; }
-  else if (p == 1) { R[0][1] = R[1][0] = 1.0; }
-  else if (p == 2) { R[0][1] = cplx(0.0, -1.0); R[1][0] = cplx(0.0, 1.0); }
-  else { R[0][0] = 1.0; R[1][1] = -1.0; }
-}
-// (1 - p) id + p / (4^k - 1) sum over the non-identity Paulis on the qubits of `mask` (bit 0: a, bit 1: b)
-void sup_depol(int mask, double p, Sup& S) {
-  const int k = (mask & 1) + ((mask >> 1) & 1);
-  const double w = p / (k == 2 ? 15.0 : 3.0);
-  for (int r = 0; r < 16; ++r) for (int c = 0; c < 16; ++c) S.m[r][c] = r == c ? 1.0 - p : 0.0;
-  for (int pa = 0; pa < 4; ++pa) for (int pb = 0; pb < 4; ++pb) {
-    if ((pa && !(mask & 1)) || (pb && !(mask & 2)) || (!pa && !pb)) continue;
-    cplx Ra[2][2], Rb[2][2], Ua[4][4], Ub[4][4], U[4][4];
-    pauli_1q(pa, Ra); pauli_1q(pb, Rb);
-    embed_1q(Ra, 0, Ua); embed_1q(Rb, 1, Ub);
-    for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) {
-      cplx v = 0.0;
-      for (int m = 0; m < 4; ++m) v += Ua[i][m] * Ub[m][j];
-      U[i][j] = v;
-    }
-    Sup P;
-    sup_conj(U, P);
-    for (int r = 0; r < 16; ++r) for (int c = 0; c < 16; ++c) S.m[r][c] += w * P.m[r][c];
-  }
-}
-
-struct DmBlockHost { int a, b; Sup S; };
-
-// Gate list -> superoperator blocks.  A block collects the gates / channels that stay inside its two-qubit window; blocks
-// on DISJOINT windows commute (they act on different index bits of rho), so several blocks are open at a time and a
-// gate joins the open block that holds all of its qubits wherever that block was opened; a gate that touches an open
-// window without fitting into it closes that block first (blocks are emitted in the order they are closed, which keeps
-// every qubit's own sequence of operations intact).  Gate semantics as in vqe_device.h (qulacs: R = exp(+i theta/2 P),
-// CNOT(control, target)).  Bench circuits (63 gates + 63 channels on 12 qubits): 57 blocks with consecutive fusion
-// only, ~40 with this one.
-void dm_make_blocks(int n, const GateRec* g, int G, const double* theta, double p1, double p2, std::vector<DmBlockHost>& out) {
-  out.clear();
-  std::vector<DmBlockHost> open;            // pairwise disjoint windows
-  auto owner = [&](int q) { for (size_t k = 0; k < open.size(); ++k) if (open[k].a == q || open[k].b == q) return (int)k; return -1; };
-  auto close = [&](int k) { out.push_back(open[k]); open.erase(open.begin() + k); };
-  for (int i = 0; i < G; ++i) {
-    const GateRec r = g[i];
-    const bool two = r.kind == G_CNOT || r.kind == G_DEPOL2;
-    const int qa = r.q0, qb = two ? r.q1 : -1;
-    int k = owner(qa);
-    const int k2 = two ? owner(qb) : k;
-    if (k < 0 || k2 != k) {
-      // no open block holds all qubits of the gate: close the ones it touches (the higher index first), open a new one
-      const int c1 = k, c2 = two ? k2 : -1;
-      if (c1 >= 0 && c2 >= 0 && c1 != c2) { close(std::max(c1, c2)); close(std::min(c1, c2)); }
-      else if (c1 >= 0) close(c1);
-      else if (c2 >= 0) close(c2);
-      DmBlockHost nb{};
-      nb.a = qa;
-      nb.b = qb;
-      if (nb.b < 0) {
-        // a one-qubit gate opens the window: its partner is the other qubit of the next two-qubit gate that touches it,
-        // if that qubit is free; else any free qubit; if every other qubit sits in an open window, the oldest block goes
-        int want = -1;
-        for (int j = i + 1; j < G && want < 0; ++j) {
-          const bool t2 = g[j].kind == G_CNOT || g[j].kind == G_DEPOL2;
-          if (t2 && g[j].q0 == qa) want = g[j].q1;
-          else if (t2 && g[j].q1 == qa) want = g[j].q0;
-        }
-        if (want >= 0 && owner(want) < 0) nb.b = want;
-        for (int q = 0; q < n && nb.b < 0; ++q) if (q != qa && owner(q) < 0) nb.b = q;
-        if (nb.b < 0) { nb.b = open[0].a; close(0); }
-      }
-      sup_identity(nb.S);
-      open.push_back(nb);
-      k = (int)open.size() - 1;
-    }
-    DmBlockHost& cur = open[k];
-    const int wa = cur.a;
-    Sup Gs;
-    if (r.kind == G_CNOT) {
-      const int pc = r.q0 == wa ? 0 : 1, pt = pc ^ 1;
-      cplx U[4][4];
-      for (int x = 0; x < 4; ++x) for (int y = 0; y < 4; ++y) U[x][y] = (x == (y ^ (((y >> pc) & 1) << pt))) ? 1.0 : 0.0;
-      sup_conj(U, Gs);
-    } else if (r.kind >= G_RX && r.kind <= G_RZ) {
-      const double c = std::cos(0.5 * theta[r.pidx]), sn = std::sin(0.5 * theta[r.pidx]);
-      cplx R[2][2], U[4][4];
-      if (r.kind == G_RX) { R[0][0] = R[1][1] = c; R[0][1] = R[1][0] = cplx(0.0, sn); }
-      else if (r.kind == G_RY) { R[0][0] = R[1][1] = c; R[0][1] = sn; R[1][0] = -sn; }
-      else { R[0][0] = cplx(c, sn); R[1][1] = cplx(c, -sn); R[0][1] = R[1][0] = 0.0; }
-      embed_1q(R, r.q0 == wa ? 0 : 1, U);
-      sup_conj(U, Gs);
-    } else if (r.kind == G_DEPOL1) {
-      sup_depol(r.q0 == wa ? 1 : 2, p1, Gs);
-    } else {
-      sup_depol(3, p2, Gs);
-    }
-    sup_apply(cur.S, Gs);
-  }
-  while (!open.empty()) close(0);
-}
+// ---- exact channel mode (vqe_dm.h; superoperator blocks: dm_host.h) ---------------------------------
 
 // this handle's Hamiltonian terms (all of its share under term sharding) for k_dm_energy
 int dm_prepare_ham(vqe_t* h) {
   if (h->dm_ham_gen == h->gen) return VQE_OK;
-  const std::vector<int> owner = assign_groups(h->gx_all, h->group_terms, h->lds_path, h->shard_world);
+  const HamHost& H = h->ham_host;
   std::vector<uint32_t> gx, tz;
   std::vector<int32_t> toff{0};
   std::vector<double> cr, ci;
-  for (size_t g = 0; g < owner.size(); ++g) {
-    if (owner[g] != h->shard_rank) continue;
-    gx.push_back(h->gx_all[g]);
-    for (int k : h->group_terms[g]) { tz.push_back((uint32_t)h->hz[k]); cr.push_back(h->hcr[k]); ci.push_back(h->hci[k]); }
+  for (int g : shard_groups(H, h->lds_path, h->shard_rank, h->shard_world)) {
+    gx.push_back(H.gx_all[g]);
+    for (int k : H.group_terms[g]) { tz.push_back((uint32_t)H.hz[k]); cr.push_back(H.hcr[k]); ci.push_back(H.hci[k]); }
     toff.push_back((int32_t)tz.size());
   }
   int rc;
@@ -1398,49 +747,19 @@ int run(vqe_t* h, int which, double rhobeg, double rhoend, int maxfun) {
 }
 
 // ---- adjoint gradient (vqe_grad.h) -----------------------------------------------------------
-// The unit-free table set of k_lds_energy_grad: every X-mask group of this handle's shard (the same partition as
-// build_hamiltonian) in the logical index, T[q] = D_x(p0) = sum_k c_k i^{#Y} (-1)^{popc(p0 & z_k)} over the pair
-// representatives p0 = insert0(q, hb(x)) (complex entries only for groups with an odd number of Y factors), the
-// diagonal group over all indices.  Rebuilt when the Hamiltonian or its shard changed.
+// The unit-free table set of k_lds_energy_grad (plan_grad_tables, ham_layout.h), rebuilt when the Hamiltonian or its
+// shard changed.
 int build_grad_tables(vqe_t* h) {
   if (h->grad_ham_ver == h->ham_ver) return VQE_OK;
-  const int n = h->n;
-  const size_t dim = (size_t)1 << n;
-  const std::vector<int> owner = assign_groups(h->gx_all, h->group_terms, h->lds_path, h->shard_world);
-  std::vector<uint32_t> gx;
-  std::vector<int64_t> off;
-  std::vector<int32_t> cplx;
-  std::vector<double> tab;
-  for (size_t g = 0; g < owner.size(); ++g) {
-    if (owner[g] != h->shard_rank) continue;
-    const uint32_t x = h->gx_all[g];
-    bool im = false;
-    for (int k : h->group_terms[g]) im |= h->hci[k] != 0.0;
-    const size_t len = x == 0 ? dim : dim / 2;
-    const int hb = x == 0 ? 0 : 31 - __builtin_clz(x);
-    gx.push_back(x);
-    off.push_back((int64_t)tab.size());
-    cplx.push_back(im ? 1 : 0);
-    const size_t base = tab.size();
-    tab.resize(base + (im ? 2 * len : len), 0.0);
-    double* t = tab.data() + base;
-    for (int k : h->group_terms[g]) {
-      const uint32_t z = (uint32_t)h->hz[k];
-      for (size_t q = 0; q < len; ++q) {
-        const uint32_t p0 = x == 0 ? (uint32_t)q : (uint32_t)(((q >> hb) << (hb + 1)) | (q & (((size_t)1 << hb) - 1)));
-        const double sgn = (__builtin_popcount(p0 & z) & 1) ? -1.0 : 1.0;
-        if (im) { t[2 * q] += sgn * h->hcr[k]; t[2 * q + 1] += sgn * h->hci[k]; }
-        else t[q] += sgn * h->hcr[k];
-      }
-    }
-  }
+  GradTables T;
+  plan_grad_tables(h->ham_host, h->n, h->lds_path, h->shard_rank, h->shard_world, T);
   int rc;
-  if ((rc = upload(h, h->g_gx, gx.data(), gx.size()))) return rc;
-  if ((rc = upload(h, h->g_off, off.data(), off.size()))) return rc;
-  if ((rc = upload(h, h->g_cplx, cplx.data(), cplx.size()))) return rc;
-  if ((rc = upload(h, h->g_tab, tab.data(), tab.size()))) return rc;
+  if ((rc = upload(h, h->g_gx, T.gx.data(), T.gx.size()))) return rc;
+  if ((rc = upload(h, h->g_off, T.off.data(), T.off.size()))) return rc;
+  if ((rc = upload(h, h->g_cplx, T.cplx.data(), T.cplx.size()))) return rc;
+  if ((rc = upload(h, h->g_tab, T.tab.data(), T.tab.size()))) return rc;
   HIP_TRY(h, hipStreamSynchronize(h->stream));  // host vectors go out of scope
-  h->gham = GradHam{(int)gx.size(), h->g_gx.p, h->g_off.p, h->g_cplx.p, h->g_tab.p};
+  h->gham = GradHam{(int)T.gx.size(), h->g_gx.p, h->g_off.p, h->g_cplx.p, h->g_tab.p};
   h->grad_ham_ver = h->ham_ver;
   return VQE_OK;
 }
@@ -1631,29 +950,8 @@ int vqe_set_hamiltonian_pauli(vqe_t* h, int n_terms, const uint64_t* xmask, cons
   if (n_terms < 0 || (n_terms > 0 && (!xmask || !zmask || !coeff)))
     return fail(h, VQE_EINVAL, "bad Hamiltonian arguments");
   HIP_TRY(h, hipSetDevice(h->dev));
-  const uint64_t lim = h->n >= 64 ? ~0ull : (((uint64_t)1 << h->n) - 1);
-  h->hx.assign(xmask, xmask + n_terms);
-  h->hz.assign(zmask, zmask + n_terms);
-  h->hcr.assign(n_terms, 0.0);
-  h->hci.assign(n_terms, 0.0);
-  std::map<uint32_t, int> index;
-  h->gx_all.clear();
-  h->group_terms.clear();
-  for (int k = 0; k < n_terms; ++k) {
-    if ((xmask[k] | zmask[k]) & ~lim) return fail(h, VQE_EINVAL, "Pauli mask uses a qubit >= n_qubits");
-    const int ny = __builtin_popcountll(xmask[k] & zmask[k]) & 3;  // i^{#Y}
-    const double w = coeff[k];
-    h->hcr[k] = ny == 0 ? w : (ny == 2 ? -w : 0.0);
-    h->hci[k] = ny == 1 ? w : (ny == 3 ? -w : 0.0);
-    const uint32_t x = (uint32_t)xmask[k];
-    auto it = index.find(x);
-    if (it == index.end()) {
-      it = index.emplace(x, (int)h->gx_all.size()).first;
-      h->gx_all.push_back(x);
-      h->group_terms.emplace_back();
-    }
-    h->group_terms[it->second].push_back(k);
-  }
+  if (!ham_from_paulis(h->n, n_terms, xmask, zmask, coeff, h->ham_host))
+    return fail(h, VQE_EINVAL, "Pauli mask uses a qubit >= n_qubits");
   h->ham_set = true;
   return build_hamiltonian(h);
 }
@@ -1702,8 +1000,8 @@ int vqe_set_hamiltonian_dense(vqe_t* h, const double* op_re_im, double tol) {
 int vqe_hamiltonian_terms(vqe_t* h, int32_t* n_terms, int32_t* n_xgroups) {
   if (!h || !n_terms || !n_xgroups) return VQE_EINVAL;
   if (!h->ham_set) return fail(h, VQE_ESTATE, "no Hamiltonian set");
-  *n_terms = (int32_t)h->hx.size();
-  *n_xgroups = (int32_t)h->gx_all.size();
+  *n_terms = (int32_t)h->ham_host.hx.size();
+  *n_xgroups = (int32_t)h->ham_host.gx_all.size();
   return VQE_OK;
 }
 

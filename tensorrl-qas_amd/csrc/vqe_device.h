@@ -38,56 +38,9 @@ __device__ long long g_cby_t0_unused;
 #endif
 #endif
 #include "cobyla_m0.h"
+#include "vqe_geo.h"
 
 namespace vqe {
-
-constexpr int kThreads = 256;   // default workgroup size (n <= 11 and the streaming path)
-
-// Workgroup geometry of the LDS-resident kernels.
-//  * n <= 11: 256 threads, registers capped for 4 waves per SIMD (4 workgroups per CU fit the
-//    LDS): measured at n = 11 +31 % over 2 waves per SIMD although the cap costs spills - the
-//    vector-memory, LDS and VALU pipes of the energy step overlap better across more waves;
-//  * n = 12: 256 threads x 16 amplitudes, 2 workgroups per CU (LDS bound), 256 VGPRs.  The
-//    512-thread variant (8 amplitudes per thread, 4 waves per SIMD in 128 VGPRs) was measured
-//    15 % slower: 124 spilled registers and one more re-layout per ~3 rotations;
-//  * n = 13: 512 threads x 16 amplitudes, one workgroup per CU.
-#ifndef VQE_WIDE_MIN
-#define VQE_WIDE_MIN 13
-#endif
-constexpr int kWideMinQubits = VQE_WIDE_MIN;   // 512-thread workgroups from this size on
-
-#ifndef VQE_ONE_WAVE_MAX
-#define VQE_ONE_WAVE_MAX 9
-#endif
-// Up to this size an environment is ONE wavefront (64 threads, 4 amplitudes per thread at 8 qubits).  With four waves
-// per environment three of them sit at a barrier while wave 0 runs the optimiser update, and at this size that update
-// is most of an evaluation: one-wave workgroups keep 16 environments per CU busy instead of 4 (8 qubits, 20 gates:
-// 46.9 -> 92.4 M evaluations/s; 150 gates: 12.9 -> 13.2 M; 129 variables: 6.3 -> 5.8 M at 4096 environments, 6.4 M
-// at 16384 - the price of having no second wave for the workgroup-wide update).
-constexpr int kOneWaveMaxQubits = VQE_ONE_WAVE_MAX;
-
-#ifndef VQE_ONE_WAVE_REG
-#define VQE_ONE_WAVE_REG 0      // 1: 10 qubits on the register path with one wave (16 amplitudes per thread) - parity green, 0..9 % slower than four waves x 4 amplitudes
-#endif
-__host__ __device__ constexpr bool geo_one_wave(int n) { return n <= kOneWaveMaxQubits || (VQE_ONE_WAVE_REG && n == 10); }
-__host__ __device__ constexpr int geo_lt(int n) { return n >= kWideMinQubits ? 9 : (geo_one_wave(n) ? 6 : 8); }
-
-#ifndef VQE_WPS_SMALL
-#define VQE_WPS_SMALL 2     // n <= 9 (one wave per environment): all 256 registers - at 128 these kernels spilled 470..690 B per lane; eight environments per CU without spills beat sixteen with them by 18..32 %
-#endif
-#ifndef VQE_WPS10
-#define VQE_WPS10 4
-#endif
-#ifndef VQE_WPS11
-#define VQE_WPS11 3     // n = 11: 170 registers per wave instead of 128 (464 B of spills), three workgroups per CU (the LDS rarely admits a fourth): +2..3 %
-#endif
-template <int N>
-struct Geo {
-  static constexpr int NT = 1 << geo_lt(N);        // threads per workgroup
-  static constexpr int LT = geo_lt(N);             // log2(NT)
-  static constexpr int NW = NT / 64;               // waves per workgroup
-  static constexpr int WPS = N == 11 ? VQE_WPS11 : (N == 10 ? (VQE_ONE_WAVE_REG ? 2 : VQE_WPS10) : (N <= 9 ? VQE_WPS_SMALL : 2));      // waves per SIMD asked of the register allocator
-};
 
 typedef int v4i_t __attribute__((ext_vector_type(4)));
 typedef int v2i_t __attribute__((ext_vector_type(2)));
@@ -95,13 +48,13 @@ typedef double d2v_t __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) const unsigned char lds_cbyte;
 typedef __attribute__((address_space(3))) double lds_double;
 
-enum : int { G_CNOT = 0, G_RX = 1, G_RY = 2, G_RZ = 3, G_DEPOL1 = 4, G_DEPOL2 = 5 };
 enum : int { OP_RX = 1, OP_RY = 2, OP_RZ = 3, OP_PZ = 4, OP_NOP = 6 };   // (5 = OP_RELAYOUT, vqe_reg.h)
 
-struct GateRec { int32_t kind, q0, q1, pidx; };           // as uploaded by the host
 struct Op { uint32_t xm, zm; int32_t pidx; int32_t kind; };  // kind | (inv << 8)
 
-// Hamiltonian in device memory.
+// Hamiltonian in device memory: the device copies of the arrays of HamLayout (ham_layout.h), which states what each
+// of them means - section order and padding of the group list, the canonical index p' = M p of the register path,
+// the bank swizzle S, the unit path.  Planned on the host by plan_hamiltonian.
 struct HamDev {
   int n_groups;             // X-mask groups evaluated by this handle (after sharding)
   const uint32_t* gx;       // [n_groups] X mask
@@ -111,27 +64,14 @@ struct HamDev {
   const double* tables;
   int has_diag;             // 1: group 0 is the diagonal (x == 0) group
   int n_real;               // real-table pair groups incl. zero padding (multiple of energy_pd(n))
-  // register path (10 <= n <= 13): the state is handed to the energy step in the CANONICAL index
-  // p' = M p (GF(2)-linear, chosen by the host so that the X mask of every real group touches one
-  // of the R register bits LT..n-1 of p'); masks and tables below are expressed in p'.
-  int n_cls;                // leading real groups whose x' has a register bit (multiple of energy_pd(n))
+  int n_cls;                // register path: leading real groups whose x' has a register bit (multiple of energy_pd(n))
   uint32_t mrow[16];        // row i of S M: bit i of the LDS slot of p' = parity(mrow[i] & p) (the final scatter's map)
-  // LDS bank swizzle of the register path (storage only): canonical index p' lives at LDS slot S(p') = p' ^ code(p'),
-  // code = 4-bit entry (p' >> 4) & 15 of swz (entry v at bits [4v, 4v+4)); GF(2)-linear, 0 = identity.  Chosen by
-  // the host against the unit list's ds_read_b128 lane groups; thread <-> pair ownership does not change.
-  uint64_t swz;
-  // unit path (LDS-resident kernels): X-mask groups whose sign-sum table is mostly EXACT zeros (fermionic excitation
-  // operators connect one occupation pattern in 2^w) are stored as *units* - sub-cubes of NT pairs on which the table
-  // does not vanish - and never enter the group lists above.  A unit fixes F = n-1-LT bit positions (plus the
-  // selector bit that tells the two members of a pair apart); thread t owns the pair whose remaining LT index bits
-  // are the bits of t.  urec: one word per unit, its X mask << 4 (the byte-address distance of the pair members);
-  // uaddr: the LDS byte address of the selector-0 member of each (unit, thread), built by the host; utab: the table
-  // values.  uaddr and utab are laid out per trip of kUnitTrip units as [trip][thread][unit of the trip].
-  // n_units is a multiple of kUnitUnroll (zero-table padding).
+  uint64_t swz;             // bank swizzle: p' lives at LDS slot swz_slot(swz, p'); 0 = identity
+  // unit path: n_units a multiple of kUnitUnroll; uaddr and utab as [trip][thread][unit of the trip]
   int n_units;
-  const uint32_t* urec;
-  const uint32_t* uaddr;
-  const double* utab;
+  const uint32_t* urec;     // [n_units] S(x') << 4: the byte-address distance of the pair members
+  const uint32_t* uaddr;    // LDS byte address of the selector-0 member of each (unit, thread)
+  const double* utab;       // table values
   // streaming path (n >= 14): explicit terms
   int n_terms;              // terms of the groups above
   const int32_t* term_off;  // [n_groups + 1]
@@ -139,13 +79,6 @@ struct HamDev {
   const double* term_cr;    // [n_terms] real part of c_k (incl. i^{#Y})
   const double* term_ci;    // [n_terms]
 };
-
-__host__ __device__ inline uint32_t swz_slot(uint64_t swz, uint32_t p) {
-  return p ^ (uint32_t)((swz >> (((p >> 4) & 15u) << 2)) & 15u);
-}
-constexpr int kUnitMinQubits = 8;             // below: a group has no more pairs than a workgroup has threads
-constexpr int kUnitTrip = 4;                  // units per trip of the unit loop
-constexpr int kUnitUnroll = 3 * kUnitTrip;    // HamDev::n_units is padded to a multiple of this (three trips per turn of the loop)
 
 struct NoiseCfg { double p1, p2; uint64_t seed; uint64_t eval_base; double shot_sigma; };
 
@@ -926,9 +859,7 @@ __device__ __forceinline__ void load_init(const Lds& L, const double2* init) {
 // multiple of PD] [groups with an imaginary table].  Table values stream from L2 through a
 // PD-deep register ring (group g+PD is requested when group g is consumed); the PD-unrolled
 // body is branch free so LDS reads of one group overlap the FMAs of the previous one.
-// (depth of the table ring by size: the shallower ring frees 32 registers where the kernel sits at its register cap -
-// n = 11 ... 13: +1..2 % - and costs 2..3 % where it does not)
-__host__ __device__ constexpr int energy_pd(int n) { return n >= 11 ? 2 : 4; }
+// (PD = energy_pd(n), vqe_geo.h)
 
 // All pairs of one group, both members read from LDS in batches of kEnergyBatch pairs (all
 // reads of a batch are in flight together, then the arithmetic).  DEXPR yields D for pair k

@@ -16,10 +16,10 @@
 // (~4 two-level rotations + all diagonal ones) instead of once per rotation.  After the last
 // op every thread scatters its amplitudes to LDS in LOGICAL order for the energy phase.
 #pragma once
+#include "vqe_geo.h"
 
 namespace vqe {
 
-constexpr int kRegMinQubits = 10;
 enum : int { OP_RELAYOUT = 5 };
 
 struct LayoutRec {  // 32 bytes

@@ -40,14 +40,18 @@ enum {
 
 /* gate kinds of a circuit description (order = reference construct_ansatz order,
  * environments/VQAs/VQE_qulacs_TN_notin_RL.py:13-45; noise kinds:
- * VQE_qulacs_TN_notin_RL_noise.py:26-28,40-50) */
+ * VQE_qulacs_TN_notin_RL_noise.py:26-28,40-50; two-qubit Pauli rotations of the SU(4) gate set:
+ * environments/VQAs/VQE_qulacs_su4.py:68-90, ParametricPauliRotation([q0, q1], [P, P], theta)) */
 enum {
   VQE_GATE_CNOT = 0,   /* q0 = control, q1 = target                       */
   VQE_GATE_RX = 1,     /* q0 = qubit, param_idx = index into theta        */
   VQE_GATE_RY = 2,
   VQE_GATE_RZ = 3,
   VQE_GATE_DEPOL1 = 4, /* DepolarizingNoise(q0, p1)                       */
-  VQE_GATE_DEPOL2 = 5  /* TwoQubitDepolarizingNoise(q0, q1, p2)           */
+  VQE_GATE_DEPOL2 = 5, /* TwoQubitDepolarizingNoise(q0, q1, p2)           */
+  VQE_GATE_RXX = 6,    /* exp(+i*theta/2 * X_q0 X_q1), q0 != q1, param_idx */
+  VQE_GATE_RYY = 7,    /* exp(+i*theta/2 * Y_q0 Y_q1)   (symmetric in q0, q1; refused by the */
+  VQE_GATE_RZZ = 8     /* exp(+i*theta/2 * Z_q0 Z_q1)    exact channel mode)                 */
 };
 
 /* ---- lifetime ------------------------------------------------------------------------

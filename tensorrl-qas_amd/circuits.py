@@ -5,7 +5,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .engine import (Circuit, GATE_CNOT, GATE_DEPOL1, GATE_DEPOL2, GATE_RX)
+from .engine import (Circuit, GATE_CNOT, GATE_DEPOL1, GATE_DEPOL2, GATE_RX, GATE_RXX)
 
 
 def circuit_from_state(state, n_qubits, noise=False, with_layers=False, max_layer=None):
@@ -41,15 +41,44 @@ def circuit_from_state(state, n_qubits, noise=False, with_layers=False, max_laye
     return out + (np.asarray(lay, dtype=np.int64),) if with_layers else out
 
 
+def circuit_from_state_su4(state, n_qubits):
+    """The SU(4) ansatz builder (reference environments/VQAs/VQE_qulacs_su4.py:13-63) as an array
+    transformation.  ``state``: (L, 6n+6, n) tensor/array - rows [0,n) xx, [n,2n) yy, [2n,3n) zz positions,
+    [3n,3n+3) one-qubit rotation positions, then the angle blocks in the same order.  Per layer: RXX, then
+    RYY, then RZZ, each in row-major order of [target][control] == 1 with angle theta[target][control] on
+    qubits (q0, q1) = (control, target); then R{X,Y,Z} in row-major order of [axis][qubit] == 1.
+    Parameter j is the j-th gate met.  Returns (Circuit, angles float64[P])."""
+    s = state.detach().cpu().numpy() if hasattr(state, "detach") else np.asarray(state)
+    n = n_qubits
+    if s.ndim != 3 or s.shape[1] != 6 * n + 6 or s.shape[2] != n:
+        raise ValueError(f"SU(4) state tensor must be (L, {6 * n + 6}, {n}), got {s.shape}")
+    kind, q0, q1, ang = [], [], [], []
+    for layer in s:
+        for p in range(3):
+            theta = layer[3 * n + 3 + p * n:3 * n + 3 + (p + 1) * n]
+            for t, c in zip(*np.nonzero(layer[p * n:(p + 1) * n] == 1)):
+                if t == c:
+                    raise ValueError("a two-qubit rotation needs two distinct qubits")
+                kind.append(GATE_RXX + p), q0.append(int(c)), q1.append(int(t)), ang.append(float(theta[t, c]))
+        theta = layer[6 * n + 3:6 * n + 6]
+        for a, q in zip(*np.nonzero(layer[3 * n:3 * n + 3] == 1)):
+            kind.append(GATE_RX + int(a)), q0.append(int(q)), q1.append(-1), ang.append(float(theta[a, q]))
+    return Circuit(kind, q0, q1, np.arange(len(ang)), len(ang)), np.asarray(ang, dtype=np.float64)
+
+
 def circuit_from_qasm_gates(gates):
     """qiskit-convention gate list -> engine Circuit + angles.  qiskit r?(t) = exp(-i t/2 P) is
     the engine's (qulacs') R?(-t); the reference relies on the same flip when it copies the
     init circuit into the state tensor (environment_qulacs.py:305,308,311)."""
     kind, q0, q1, pidx, ang = [], [], [], [], []
     code = {"rx": 1, "ry": 2, "rz": 3}
+    code2 = {"rxx": 6, "ryy": 7, "rzz": 8}      # qiskit r??(t) = exp(-i t/2 PP): the same flip
     for g in gates:
         if g.name == "cx":
             kind.append(GATE_CNOT), q0.append(g.qubits[0]), q1.append(g.qubits[1]), pidx.append(-1)
+        elif g.name in code2:
+            kind.append(code2[g.name]), q0.append(g.qubits[0]), q1.append(g.qubits[1]), pidx.append(len(ang))
+            ang.append(-g.angle)
         else:
             kind.append(code[g.name]), q0.append(g.qubits[0]), q1.append(-1), pidx.append(len(ang))
             ang.append(-g.angle)
@@ -70,3 +99,4 @@ def random_circuit(n_qubits, n_gates, rng, p_cnot=0.5):
             kind.append(GATE_RX + int(rng.integers(3))), q0.append(int(rng.integers(n_qubits)))
             q1.append(-1), pidx.append(len(ang)), ang.append(float(rng.uniform(-np.pi, np.pi)))
     return Circuit(kind, q0, q1, pidx, len(ang)), np.asarray(ang, dtype=np.float64)
+

@@ -189,13 +189,13 @@ int check_gates(vqe_t* h, int64_t n_gates, const int32_t* kind, const int32_t* q
                 const int32_t* q1, const int32_t* pidx, int n_params) {
   for (int64_t i = 0; i < n_gates; ++i) {
     const int k = kind[i];
-    if (k < 0 || k > VQE_GATE_DEPOL2) return fail(h, VQE_EINVAL, "unknown gate kind");
+    if (k < 0 || k > VQE_GATE_RZZ) return fail(h, VQE_EINVAL, "unknown gate kind");
     if (q0[i] < 0 || q0[i] >= h->n) return fail(h, VQE_EINVAL, "gate qubit out of range");
-    if (k == VQE_GATE_CNOT || k == VQE_GATE_DEPOL2) {
+    if (k == VQE_GATE_CNOT || k == VQE_GATE_DEPOL2 || gate_is_rot2(k)) {
       if (q1[i] < 0 || q1[i] >= h->n || q1[i] == q0[i])
         return fail(h, VQE_EINVAL, "two-qubit gate needs two distinct qubits in range");
     }
-    if (k >= VQE_GATE_RX && k <= VQE_GATE_RZ) {
+    if (gate_is_rot(k)) {
       if (pidx[i] < 0 || pidx[i] >= n_params)
         return fail(h, VQE_EINVAL, "rotation parameter index out of range");
     }
@@ -311,7 +311,7 @@ int load_batch(vqe_t* h, int batch, const std::vector<GateRec>& gates,
     for (int64_t i = gbeg[b]; i < gbeg[b] + gcnt[b]; ++i) {
       const int k = gates[i].kind;
       ops += (k == G_CNOT) ? 0 : (k == G_DEPOL2 ? 2 : 1);
-      pair += (k == G_RX || k == G_RY) ? 1 : 0;
+      pair += (k == G_RX || k == G_RY || k == G_RXX || k == G_RYY) ? 1 : 0;
     }
     max_ops = std::max(max_ops, ops);
     max_pair = std::max(max_pair, pair);
@@ -504,7 +504,9 @@ int stream_run(vqe_t* h, int which, BatchArgs& A) {
       int skip_end = skip + 1;
       if (skip >= 0) {
         const GateRec r = h->h_gates[g0 + skip];
-        if (r.kind >= G_RX && r.kind <= G_RZ) hole[b] = r.pidx;
+        if (gate_is_rot(r.kind)) hole[b] = r.pidx;
+        // the attached channel: CNOT + DEPOL2 and R{X,Y,Z} + DEPOL1 only, as in k_lds_minimize - the SU(4) ansatz builder
+        // attaches none, a DEPOL2 behind an RXX / RYY / RZZ stays in the pre-action circuit
         if (skip + 1 < G) {
           const GateRec fo = h->h_gates[g0 + skip + 1];
           if ((fo.kind == G_DEPOL1 && r.kind >= G_RX && r.kind <= G_RZ && fo.q0 == r.q0) ||
@@ -517,7 +519,7 @@ int stream_run(vqe_t* h, int which, BatchArgs& A) {
       for (int i = 0; i < G; ++i) {
         if (i >= skip && i < skip_end) continue;
         GateRec r = h->h_gates[g0 + i];
-        if (r.kind >= G_RX && r.kind <= G_RZ && hole[b] >= 0 && r.pidx > hole[b]) r.pidx -= 1;
+        if (gate_is_rot(r.kind) && hole[b] >= 0 && r.pidx > hole[b]) r.pidx -= 1;
         g2.push_back(r);
       }
       gcnt2[b] = (int32_t)((int64_t)g2.size() - gbeg2[b]);
@@ -639,6 +641,11 @@ int dm_energy_one(vqe_t* h, const GateRec* g, int G, const double* theta, double
 // A.env_step the pre-action circuit, float32 round trip and the energy of the full circuit, as the fused kernel does).
 int dm_run(vqe_t* h, int which, const BatchArgs& A) {
   if (h->n < 2 || h->n > 13) return fail(h, VQE_EINVAL, "the exact channel mode (density matrix) serves 2 <= n_qubits <= 13");
+  // the superoperator blocks (dm_host.h) are built from CNOT, RX, RY, RZ and the two channels only: refused before anything is launched
+  for (int b = 0; b < h->batch; ++b)
+    for (int64_t i = h->h_gate_begin[b]; i < h->h_gate_begin[b] + h->h_gate_count[b]; ++i)
+      if (gate_is_rot2(h->h_gates[i].kind))
+        return fail(h, VQE_EINVAL, "the exact channel mode does not take RXX / RYY / RZZ gates (use Pauli-trajectory noise, vqe_set_noise_mode 0)");
   if (h->amp_world > 1) return fail(h, VQE_ESTATE, "the exact channel mode has no amplitude sharding");
   int rc = dm_prepare_ham(h);
   if (rc) return rc;
@@ -661,6 +668,7 @@ int dm_run(vqe_t* h, int which, const BatchArgs& A) {
     int skip_end = skip + 1, hole = -1;
     if (skip >= 0) {
       const GateRec r = g[skip];
+      // (one-qubit rotations only: dm_run has refused every circuit that holds an RXX / RYY / RZZ above)
       if (r.kind >= G_RX && r.kind <= G_RZ) hole = r.pidx;
       if (skip + 1 < G) {
         const GateRec fo = g[skip + 1];

@@ -48,7 +48,17 @@ typedef double d2v_t __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) const unsigned char lds_cbyte;
 typedef __attribute__((address_space(3))) double lds_double;
 
-enum : int { OP_RX = 1, OP_RY = 2, OP_RZ = 3, OP_PZ = 4, OP_NOP = 6 };   // (5 = OP_RELAYOUT, vqe_reg.h)
+enum : int { OP_RX = 1, OP_RY = 2, OP_RZ = 3, OP_PZ = 4, OP_NOP = 6, OP_RYY = 7 };   // (5 = OP_RELAYOUT, vqe_reg.h)
+// A two-qubit Pauli rotation is ONE op in the physical frame: RXX an OP_RX whose pair mask is the XOR of the two
+// qubits' columns of A^-1, RZZ an OP_RZ whose sign mask is the XOR of their rows of A, RYY the exchange of RXX with the
+// sign -(-1)^parity(p & zm) on its off-diagonal term (OP_RYY; the same for both members of a pair: parity(xm & zm) = 0).
+VQE_HD constexpr int rot2_op(int gate_kind) {
+  return gate_kind == G_RXX ? OP_RX : (gate_kind == G_RYY ? OP_RYY : OP_RZ);
+}
+// ops that exchange pairs of amplitudes (the ones a layout / tile / sweep has to hold the partner mask of)
+VQE_HD constexpr bool op_is_pair(int op_kind) {
+  return op_kind == OP_RX || op_kind == OP_RY || op_kind == OP_RYY;
+}
 
 struct Op { uint32_t xm, zm; int32_t pidx; int32_t kind; };  // kind | (inv << 8)
 
@@ -104,7 +114,7 @@ struct BatchArgs {
   HamDev ham;
   NoiseCfg noise;
   int max_ops;                 // LDS capacity (ops) of this launch
-  int max_pair;                // ... of which pair ops (RX / RY gates: the only ops that can open a new register layout)
+  int max_pair;                // ... of which pair ops (RX / RY / RXX / RYY gates: the only ops that can open a new register layout)
   int max_params;              // LDS capacity (cos/sin pairs)
   double rhobeg, rhoend;
   int maxfun;
@@ -568,6 +578,12 @@ __device__ __forceinline__ void compile_ops(const BatchArgs& A, int b, uint64_t 
             L.ops[nops] = Op{xm[r.q0], zm[r.q0], r.pidx, r.kind | (int)(((c >> r.q0) & 1u) << 8)};
           ++nops;
           break;
+        case G_RXX: case G_RYY: case G_RZZ:
+          if (nops < A.max_ops)
+            L.ops[nops] = Op{xm[r.q0] ^ xm[r.q1], zm[r.q0] ^ zm[r.q1], r.pidx,
+                             rot2_op(r.kind) | (int)((((c >> r.q0) ^ (c >> r.q1)) & 1u) << 8)};
+          ++nops;
+          break;
         // (noise gates: slots above, or ignored - the errors are applied by patch_noise)
         default: break;
       }
@@ -628,8 +644,9 @@ __device__ __forceinline__ void patch_noise_wave(const BatchArgs& A, int b, uint
       const uint32_t flip_a = (pa == 1 || pa == 2) ? 1u << q0 : 0u;
       const uint32_t flip_b = (pb == 1 || pb == 2) ? 1u << q1 : 0u;
       const uint32_t cnot_m = kind == G_CNOT ? 1u << q1 : 0u;
-      const int nrec = (kind >= G_RX && kind <= G_DEPOL1) ? 1 : (kind == G_DEPOL2 ? 2 : 0);
-      const uint32_t w1 = flip_a | ((uint32_t)q0 << 16) | ((uint32_t)q1 << 24);
+      const int nrec = ((kind >= G_RX && kind <= G_DEPOL1) || gate_is_rot2(kind)) ? 1 : (kind == G_DEPOL2 ? 2 : 0);
+      // (bit 31: a two-qubit rotation - its sign bit is c[q0] ^ c[q1])
+      const uint32_t w1 = flip_a | ((uint32_t)q0 << 16) | ((uint32_t)q1 << 24) | (gate_is_rot2(kind) ? 1u << 31 : 0u);
       const uint32_t w2 = cnot_m | (flip_b << 16);
       const uint64_t has1 = __ballot(nrec >= 1), has2 = __ballot(nrec == 2);
       const int k0 = kbase + __popcll(has1 & lt_mask) + __popcll(has2 & lt_mask);
@@ -649,11 +666,11 @@ __device__ __forceinline__ void patch_noise_wave(const BatchArgs& A, int b, uint
         const uint32_t a = (uint32_t)__builtin_amdgcn_readlane((int)w1, j);
         const uint32_t bw = (uint32_t)__builtin_amdgcn_readlane((int)w2, j);
         c ^= a & 0xffffu;                                   // X error on q0
-        const uint32_t b0 = (c >> ((a >> 16) & 31u)) & 1u;  // sign bit of record 0 / CNOT control
+        const uint32_t b0 = ((c >> ((a >> 16) & 31u)) ^ ((c >> ((a >> 24) & 31u)) & (a >> 31))) & 1u;  // sign bit of record 0 / CNOT control
         c ^= (0u - b0) & (bw & 0xffffu);                    // CNOT: target follows the control
         inv0 |= (uint64_t)b0 << j;
         c ^= bw >> 16;                                      // X error on q1
-        inv1 |= (uint64_t)((c >> (a >> 24)) & 1u) << j;     // sign bit of record 1
+        inv1 |= (uint64_t)((c >> ((a >> 24) & 31u)) & 1u) << j;     // sign bit of record 1
       }
       auto apply = [&](int pk, int sign, int pauli) {   // pauli < 0: a rotation, kind stays
         if (pk < kmax) {
@@ -663,7 +680,7 @@ __device__ __forceinline__ void patch_noise_wave(const BatchArgs& A, int b, uint
           o->kind = (kd & ~0x100) | (sign << 8);
         }
       };
-      if (nrec >= 1) apply(k0, (int)((inv0 >> lane) & 1ull), kind <= G_RZ ? -1 : pa);
+      if (nrec >= 1) apply(k0, (int)((inv0 >> lane) & 1ull), gate_is_rot(kind) ? -1 : pa);
       if (nrec == 2) apply(k0 + 1, (int)((inv1 >> lane) & 1ull), pb);
     }
     {
@@ -769,7 +786,7 @@ __device__ __forceinline__ void run_ops(const Lds& L, const double* theta, int P
     if constexpr (SLOTS) o += (int)((uint32_t)op.kind >> 24);   // inactive noise slots behind this record (jump counts of patch_noise_wave)
     if (kind == OP_NOP) continue;   // inactive noise slot: nothing to do, no barrier needed
     const int inv = (op.kind >> 8) & 1;
-    if (kind == OP_RX || kind == OP_RY) {
+    if (op_is_pair(kind)) {
       const double2 cs = L.cs[op.pidx];
       const int hb = 31 - __clz((int)op.xm);
       if (kind == OP_RX) {
@@ -783,7 +800,7 @@ __device__ __forceinline__ void run_ops(const Lds& L, const double* theta, int P
             L.psi[p1] = make_double2(cs.x * a1.x - cs.y * a0.y, cs.x * a1.y + cs.y * a0.x);
           }
         }
-      } else {
+      } else if (kind == OP_RY) {
 #pragma unroll
         for (int k = 0; k < NP; ++k) {
           const uint32_t q = tid + k * kThreads;
@@ -793,6 +810,18 @@ __device__ __forceinline__ void run_ops(const Lds& L, const double* theta, int P
             const double2 a0 = L.psi[p0], a1 = L.psi[p1];
             L.psi[p0] = make_double2(cs.x * a0.x + s0 * a1.x, cs.x * a0.y + s0 * a1.y);
             L.psi[p1] = make_double2(cs.x * a1.x - s0 * a0.x, cs.x * a1.y - s0 * a0.y);
+          }
+        }
+      } else {   // OP_RYY: the exchange of RX with the off-diagonal sign -(-1)^parity(p & zm), one sign per pair
+#pragma unroll
+        for (int k = 0; k < NP; ++k) {
+          const uint32_t q = tid + k * kThreads;
+          if (DIM / 2 >= kThreads || q < DIM / 2) {
+            const uint32_t p0 = insert0(q, hb), p1 = p0 ^ op.xm;
+            const double s0 = (parity32(p0 & op.zm) ^ inv) ? cs.y : -cs.y;
+            const double2 a0 = L.psi[p0], a1 = L.psi[p1];
+            L.psi[p0] = make_double2(cs.x * a0.x - s0 * a1.y, cs.x * a0.y + s0 * a1.x);
+            L.psi[p1] = make_double2(cs.x * a1.x - s0 * a0.y, cs.x * a1.y + s0 * a0.x);
           }
         }
       }
@@ -1747,9 +1776,11 @@ __global__ void __launch_bounds__(Geo<N>::NT, Geo<N>::WPS) k_lds_minimize(BatchA
   int skip_end = skip + 1;   // (no new gate: the empty range [-1, 0))
   if (skip >= 0) {
     const GateRec r = A.gates[A.gate_begin[b] + skip];
-    if (r.kind >= G_RX && r.kind <= G_RZ) p_hole = r.pidx;
+    if (gate_is_rot(r.kind)) p_hole = r.pidx;
     // the noise channel construct_ansatz puts behind every gate belongs to that gate: the
     // pre-action circuit contains neither (VQE_qulacs_TN_notin_RL_noise.py:26-28,40-50)
+    // (RXX / RYY / RZZ on purpose not: the reference's SU(4) ansatz builder attaches no channel to its gates
+    // (VQE_qulacs_su4.py:13-63), so a DEPOL2 behind a new two-qubit rotation is a gate of its own and stays in)
     if (skip + 1 < A.gate_count[b]) {
       const GateRec f = A.gates[A.gate_begin[b] + skip + 1];
       if ((f.kind == G_DEPOL1 && r.kind >= G_RX && r.kind <= G_RZ && f.q0 == r.q0) ||

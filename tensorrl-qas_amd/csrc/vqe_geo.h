@@ -62,7 +62,10 @@ struct Geo {
 
 constexpr int kRegMinQubits = 10;   // register path (vqe_reg.h) from this size on
 
-enum : int { G_CNOT = 0, G_RX = 1, G_RY = 2, G_RZ = 3, G_DEPOL1 = 4, G_DEPOL2 = 5 };
+enum : int { G_CNOT = 0, G_RX = 1, G_RY = 2, G_RZ = 3, G_DEPOL1 = 4, G_DEPOL2 = 5, G_RXX = 6, G_RYY = 7, G_RZZ = 8 };
+// two-qubit Pauli rotations exp(+i theta/2 P_q0 P_q1) (fields q0, q1, pidx) / any gate that carries a parameter
+VQE_HD constexpr bool gate_is_rot2(int k) { return k >= G_RXX && k <= G_RZZ; }
+VQE_HD constexpr bool gate_is_rot(int k) { return (k >= G_RX && k <= G_RZ) || gate_is_rot2(k); }
 struct GateRec { int32_t kind, q0, q1, pidx; };           // as uploaded by the host
 
 // Depth of the energy step's table ring, and so the multiple to which the host pads the real-table sections of the

@@ -6,7 +6,7 @@
 //  2. lambda = H psi in the logical frame: psi is gathered into logical order, every thread accumulates the lambda
 //     entries of its own amplitudes over all X-mask groups of this handle's shard in registers (no write conflicts),
 //     E = Re <psi|lambda>; then psi and lambda are scattered back to the physical frame;
-//  3. backward: for op k = K-1 .. 0 the contribution Re <lambda_k| K psi_k> (K = iP, the op at (c, s) = (0, 1)) is
+//  3. backward: for op k = K-1 .. 0 the contribution Re <lambda_k| K psi_k> (K = iP, the op at (c, s) = (0, 1); P a one- or two-qubit Pauli string) is
 //     reduced per wavefront into gacc[k][wave], then U_k^-1 is applied to psi and lambda;
 //  4. grad[j] = sum over the ops with parameter j (0 for a parameter no gate uses), plain stores.
 // The Hamiltonian comes in its own unit-free table set (GradHam, built by the host on the first gradient request for
@@ -172,7 +172,7 @@ __global__ void __launch_bounds__(Geo<N>::NT) k_lds_energy_grad(BatchArgs A, Gra
       const double2 cs = L.cs[op.pidx];
       const double c = cs.x, s = cs.y;
       double gp = 0.0;
-      if (kind == OP_RX || kind == OP_RY) {
+      if (op_is_pair(kind)) {
         const int hb = 31 - __clz((int)op.xm);
 #pragma unroll
         for (int k = 0; k < NP; ++k) {
@@ -189,6 +189,15 @@ __global__ void __launch_bounds__(Geo<N>::NT) k_lds_energy_grad(BatchArgs A, Gra
               L.psi[p1] = make_double2(c * a1.x + s * a0.y, c * a1.y - s * a0.x);
               lam[p0] = make_double2(c * l0.x + s * l1.y, c * l0.y - s * l1.x);
               lam[p1] = make_double2(c * l1.x + s * l0.y, c * l1.y - s * l0.x);
+            } else if (kind == OP_RYY) {
+              const double sg = (parity32(p0 & op.zm) ^ inv) ? 1.0 : -1.0;
+              // K = i sg X with one sign per pair: (K psi)[p0] = i sg a1, (K psi)[p1] = i sg a0
+              gp += sg * (l0.x * -a1.y + l0.y * a1.x + l1.x * -a0.y + l1.y * a0.x);
+              const double s0 = sg * s;
+              L.psi[p0] = make_double2(c * a0.x + s0 * a1.y, c * a0.y - s0 * a1.x);
+              L.psi[p1] = make_double2(c * a1.x + s0 * a0.y, c * a1.y - s0 * a0.x);
+              lam[p0] = make_double2(c * l0.x + s0 * l1.y, c * l0.y - s0 * l1.x);
+              lam[p1] = make_double2(c * l1.x + s0 * l0.y, c * l1.y - s0 * l0.x);
             } else {
               const double sg = (parity32(p0 & op.zm) ^ inv) ? -1.0 : 1.0;
               // K: (K psi)[p0] = sg a1, (K psi)[p1] = -sg a0

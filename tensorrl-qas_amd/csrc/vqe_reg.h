@@ -98,7 +98,7 @@ __device__ __forceinline__ void schedule_ops(const Lds& L) {
     B.clear();
     for (int k = from; k < nraw && B.k < R; ++k) {
       const int kd = L.ops[k].kind & 0xff;
-      if (kd == OP_RX || kd == OP_RY) B.add(L.ops[k].xm);
+      if (op_is_pair(kd)) B.add(L.ops[k].xm);
     }
     for (int b = N - 1; b >= 0 && B.k < R; --b) B.add(1u << b);   // fill with unit directions
     emit_layout<N>(B, &L.lay[nl]);
@@ -109,7 +109,7 @@ __device__ __forceinline__ void schedule_ops(const Lds& L) {
     const Op op = L.ops[o];
     const int kd = op.kind & 0xff;
     uint32_t j = 0;
-    if (kd == OP_RX || kd == OP_RY) {
+    if (op_is_pair(kd)) {
       if (B.reduce(op.xm) != 0) {
         open_layout(o);
         L.sched[ns++] = Op{(uint32_t)(nl - 1), 0u, -1, OP_RELAYOUT};
@@ -192,6 +192,20 @@ __device__ __forceinline__ void ry_pairs(double2 (&amp)[NA], double c, double s,
     const double s0 = flip_if(s, w, r);
     // amp[r] = c a0 + s0 a1, amp[r2] = c a1 - s0 a0 (componentwise)
     rot2x2(amp[r2].x, amp[r].x, amp[r2].y, amp[r].y, c, s0, s0);
+  }
+}
+
+// RYY: the exchange of rx_pairs with the sign of s taken per pair, -(-1)^(bit r of w) (the pair's two members agree:
+// the op's Z mask is orthogonal to its partner mask).  nw = ~w.
+template <int NA, int J>
+__device__ __forceinline__ void ryy_pairs(double2 (&amp)[NA], double c, double s, uint32_t nw) {
+  constexpr int HB = 31 - __builtin_clz(J);
+#pragma unroll
+  for (int r = 0; r < NA; ++r) {
+    if ((r >> HB) & 1) continue;
+    const int r2 = r ^ J;
+    const double s0 = flip_if(s, nw, r);
+    rot2x2(amp[r].x, amp[r2].y, amp[r2].x, amp[r].y, c, s0, s0);
   }
 }
 
@@ -329,6 +343,8 @@ __device__ __forceinline__ void run_ops_reg(const Lds& L, const double2* __restr
     } else if (kind == OP_PZ) {   // (OP_NOP: an inactive noise slot)
 #pragma unroll
       for (int r = 0; r < NA; ++r) amp[r] = make_double2(flip_if(amp[r].x, w, r), flip_if(amp[r].y, w, r));
+    } else if (kind == OP_RYY) {
+      VQE_PAIR_SWITCH(jm, ryy_pairs, amp, cs.x, cs.y, ~w)
     }
   }
 #ifdef VQE_STAMPS

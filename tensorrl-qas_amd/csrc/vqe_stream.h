@@ -97,6 +97,11 @@ __global__ void k_s_compile(BatchArgs A, Op* ops, uint32_t* masks, int32_t* meta
       if (nops < A.max_ops)
         out[nops] = Op{xm[r.q0], zm[r.q0], r.pidx, r.kind | (int)(((c >> r.q0) & 1u) << 8)};
       ++nops;
+    } else if (gate_is_rot2(r.kind)) {
+      if (nops < A.max_ops)
+        out[nops] = Op{xm[r.q0] ^ xm[r.q1], zm[r.q0] ^ zm[r.q1], r.pidx,
+                       rot2_op(r.kind) | (int)((((c >> r.q0) ^ (c >> r.q1)) & 1u) << 8)};
+      ++nops;
     } else if (r.kind == G_DEPOL1) {
       const double u = noise_uniform(A.noise.seed, (uint64_t)b, eval_id, (uint64_t)i);
       if (u < A.noise.p1) pauli(r.q0, 1 + (int)(u / A.noise.p1 * 3.0));
@@ -137,13 +142,14 @@ __global__ void __launch_bounds__(kThreads) k_s_init(BatchArgs A, double2* state
 // whose mask depends on the other slots (rare) takes the generic path with a computed flip code.
 // p0 runs over the coset representatives with the pivot bits of the reduced basis cleared.  Every
 // update is written per element (new[e] = c a[e] + s(e) a[partner]): parity(xm & zm) = 1 makes
-// s(partner) = -s(e), so the two members of a pair need no case distinction.
+// s(partner) = -s(e), so the two members of a pair need no case distinction (RYY: parity(xm & zm) = 0, the members share
+// the sign of an exchange that is otherwise RX's).
 template <int K>
 __device__ __forceinline__ void s_apply_k(double2 (&v)[1 << K], const uint32_t (&idx)[1 << K], const Op op,
                                           const double2* csb, const int slot, const int flip) {
   constexpr int E = 1 << K;
   const int kind = op.kind & 0xff, inv = (op.kind >> 8) & 1;
-  if (kind == OP_RX || kind == OP_RY) {
+  if (op_is_pair(kind)) {
     const double2 c = csb[op.pidx];
     double2 w[E];
     bool done = false;
@@ -155,9 +161,12 @@ __device__ __forceinline__ void s_apply_k(double2 (&v)[1 << K], const uint32_t (
         for (int e = 0; e < E; ++e) {
           const double2 a = v[e], bq = v[e ^ (1 << i)];
           if (kind == OP_RX) w[e] = make_double2(c.x * a.x - c.y * bq.y, c.x * a.y + c.y * bq.x);
-          else {
+          else if (kind == OP_RY) {
             const double sg = (parity32(idx[e] & op.zm) ^ inv) ? -c.y : c.y;
             w[e] = make_double2(c.x * a.x + sg * bq.x, c.x * a.y + sg * bq.y);
+          } else {
+            const double sg = (parity32(idx[e] & op.zm) ^ inv) ? c.y : -c.y;
+            w[e] = make_double2(c.x * a.x - sg * bq.y, c.x * a.y + sg * bq.x);
           }
         }
       }
@@ -168,9 +177,12 @@ __device__ __forceinline__ void s_apply_k(double2 (&v)[1 << K], const uint32_t (
       for (int e = 0; e < E; ++e) {
         const double2 a = tmp[e], bq = tmp[e ^ flip];
         if (kind == OP_RX) w[e] = make_double2(c.x * a.x - c.y * bq.y, c.x * a.y + c.y * bq.x);
-        else {
+        else if (kind == OP_RY) {
           const double sg = (parity32(idx[e] & op.zm) ^ inv) ? -c.y : c.y;
           w[e] = make_double2(c.x * a.x + sg * bq.x, c.x * a.y + sg * bq.y);
+        } else {
+          const double sg = (parity32(idx[e] & op.zm) ^ inv) ? c.y : -c.y;
+          w[e] = make_double2(c.x * a.x - sg * bq.y, c.x * a.y + sg * bq.x);
         }
       }
     }
@@ -232,7 +244,7 @@ __global__ void __launch_bounds__(kThreads) k_s_opk(BatchArgs A, double2* states
     if (j < cnt) {
       op[j] = ops[(size_t)b * A.max_ops + o + j];
       const int k = op[j].kind & 0xff;
-      if (k == OP_RX || k == OP_RY) {
+      if (op_is_pair(k)) {
         const uint32_t r = reduce(op[j].xm);
         if (r) { push(r); g[j] = op[j].xm; own[j] = true; flip[j] = 1 << j; }
       }
@@ -256,7 +268,7 @@ __global__ void __launch_bounds__(kThreads) k_s_opk(BatchArgs A, double2* states
   for (int j = 0; j < K; ++j)
     if (j < cnt && !own[j]) {
       const int k = op[j].kind & 0xff;
-      if (k == OP_RX || k == OP_RY)
+      if (op_is_pair(k))
         for (int f = 1; f < E; ++f) {
           uint32_t x = 0;
 #pragma unroll

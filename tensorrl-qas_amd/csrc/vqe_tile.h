@@ -82,7 +82,7 @@ constexpr int kTileK = kTileBits - 8;   // ops applied per LDS round trip: 256 t
 // One chunk of kTileK ops as k_t_ops wants it (made once by the planner, read with scalar loads): slot j of the
 // thread's coset basis is the partner mask of op j when that is independent of the earlier slots, else a filler
 // unit vector (the bookkeeping of k_s_opk, in tile coordinates).
-// A chunk holds up to kTileK pair ops (RX / RY: each needs a slot) and the diagonal ops (RZ, Pauli-Z) between
+// A chunk holds up to kTileK pair ops (RX / RY / RYY: each needs a slot) and the diagonal ops (RZ, Pauli-Z) between
 // them, which act on whatever elements a thread holds: kChunkOps ops at most.
 constexpr int kChunkOps = 6;
 struct ChunkRec {             // 24 dwords, indexed by the chunk's first op
@@ -181,7 +181,7 @@ __global__ void k_t_plan_ops(BatchArgs A, const Op* ops, const int32_t* meta, Ti
     while (o + cnt < end && cnt < kChunkOps) {
       const int kd = op[o + cnt].kind & 0xff;
       slot_of[cnt] = -1;
-      if (kd == OP_RX || kd == OP_RY) {
+      if (op_is_pair(kd)) {
         const uint32_t r = reduce(oc[o + cnt].cx);
         if (r) {
           if (nslots == K) break;              // a fourth independent mask: the next chunk
@@ -212,7 +212,7 @@ __global__ void k_t_plan_ops(BatchArgs A, const Op* ops, const int32_t* meta, Ti
       if (j < cnt) {
         const int kd = op[o + j].kind & 0xff;
         int flip = 0;
-        if (kd == OP_RX || kd == OP_RY) {
+        if (op_is_pair(kd)) {
           if (slot_of[j] >= 0) flip = 1 << slot_of[j];
           else
             for (int f = 1; f < E; ++f) {
@@ -254,7 +254,7 @@ __global__ void k_t_plan_ops(BatchArgs A, const Op* ops, const int32_t* meta, Ti
       B.emit(P + np, begin, end);
       for (int o = begin; o < end; ++o) {
         const int kd = op[o].kind & 0xff;
-        oc[o].cx = (kd == OP_RX || kd == OP_RY) ? B.coords(op[o].xm) : 0u;
+        oc[o].cx = op_is_pair(kd) ? B.coords(op[o].xm) : 0u;
         oc[o].cz = B.zcoords(op[o].zm);
       }
       for (int o = begin; o < end;) o += plan_chunk(o, end);
@@ -263,7 +263,7 @@ __global__ void k_t_plan_ops(BatchArgs A, const Op* ops, const int32_t* meta, Ti
   };
   for (int o = 0; o < nops; ++o) {
     const int kd = op[o].kind & 0xff;
-    if (kd != OP_RX && kd != OP_RY) continue;          // diagonal ops fit every tile
+    if (!op_is_pair(kd)) continue;          // diagonal ops fit every tile
     const uint32_t r = B.reduce(op[o].xm);
     if (!r) continue;
     if (B.dim < kTileBits) { B.add(r); continue; }
@@ -616,7 +616,7 @@ __global__ void k_t_cs_ops(BatchArgs A, const Op* ops, const int32_t* meta, cons
   const Op op = ops[(size_t)b * A.max_ops + o];
   const int kd = op.kind & 0xff;
   csop[(size_t)b * A.max_ops + o] =
-      (kd == OP_RX || kd == OP_RY || kd == OP_RZ) ? cs[(size_t)b * A.max_params + op.pidx] : make_double2(1.0, 0.0);
+      (op_is_pair(kd) || kd == OP_RZ) ? cs[(size_t)b * A.max_params + op.pidx] : make_double2(1.0, 0.0);
 }
 
 #ifndef VQE_OPS_TILES_PER_BLOCK
@@ -628,16 +628,19 @@ __device__ __forceinline__ double t_flip(double s, uint32_t flipword) {
   return __hiloint2double(__double2hiint(s) ^ (int)(flipword & 0x80000000u), __double2loint(s));
 }
 // w[e] = c v[e] + s(e) v[e ^ F]: the per-element updates of s_apply_k (vqe_stream.h), same expressions
-template <int E, int F, bool RX>
+template <int E, int F, int KIND>
 __device__ __forceinline__ void t_rot_pairs(double2 (&v)[E], double c, double s, uint32_t fw, uint32_t ebits) {
   double2 w[E];
 #pragma unroll
   for (int e = 0; e < E; ++e) {
     const double2 a = v[e], bq = v[e ^ F];
-    if (RX) w[e] = make_double2(c * a.x - s * bq.y, c * a.y + s * bq.x);
-    else {
+    if (KIND == OP_RX) w[e] = make_double2(c * a.x - s * bq.y, c * a.y + s * bq.x);
+    else if (KIND == OP_RY) {
       const double sg = t_flip(s, fw ^ (ebits << (31 - e)));
       w[e] = make_double2(c * a.x + sg * bq.x, c * a.y + sg * bq.y);
+    } else {      // OP_RYY: the exchange of RX, its sign -(-1)^parity per element
+      const double sg = t_flip(s, ~(fw ^ (ebits << (31 - e))));
+      w[e] = make_double2(c * a.x - sg * bq.y, c * a.y + sg * bq.x);
     }
   }
 #pragma unroll
@@ -744,23 +747,23 @@ __global__ void __launch_bounds__(kThreads, FUSED ? 4 : 1) k_t_ops(BatchArgs A, 
                              ((uint32_t)__builtin_popcount(pt & cr.op[j].zm) ^ ((kfe >> 8) & 1u))) << 31;
         if (kind == OP_RX) {
           switch (flip) {
-            case 1: t_rot_pairs<E, 1, true>(v, c.x, c.y, fw, ebits); break;
-            case 2: t_rot_pairs<E, 2, true>(v, c.x, c.y, fw, ebits); break;
-            case 3: t_rot_pairs<E, 3, true>(v, c.x, c.y, fw, ebits); break;
-            case 4: t_rot_pairs<E, 4, true>(v, c.x, c.y, fw, ebits); break;
-            case 5: t_rot_pairs<E, 5, true>(v, c.x, c.y, fw, ebits); break;
-            case 6: t_rot_pairs<E, 6, true>(v, c.x, c.y, fw, ebits); break;
-            default: t_rot_pairs<E, 7, true>(v, c.x, c.y, fw, ebits); break;
+            case 1: t_rot_pairs<E, 1, OP_RX>(v, c.x, c.y, fw, ebits); break;
+            case 2: t_rot_pairs<E, 2, OP_RX>(v, c.x, c.y, fw, ebits); break;
+            case 3: t_rot_pairs<E, 3, OP_RX>(v, c.x, c.y, fw, ebits); break;
+            case 4: t_rot_pairs<E, 4, OP_RX>(v, c.x, c.y, fw, ebits); break;
+            case 5: t_rot_pairs<E, 5, OP_RX>(v, c.x, c.y, fw, ebits); break;
+            case 6: t_rot_pairs<E, 6, OP_RX>(v, c.x, c.y, fw, ebits); break;
+            default: t_rot_pairs<E, 7, OP_RX>(v, c.x, c.y, fw, ebits); break;
           }
         } else if (kind == OP_RY) {
           switch (flip) {
-            case 1: t_rot_pairs<E, 1, false>(v, c.x, c.y, fw, ebits); break;
-            case 2: t_rot_pairs<E, 2, false>(v, c.x, c.y, fw, ebits); break;
-            case 3: t_rot_pairs<E, 3, false>(v, c.x, c.y, fw, ebits); break;
-            case 4: t_rot_pairs<E, 4, false>(v, c.x, c.y, fw, ebits); break;
-            case 5: t_rot_pairs<E, 5, false>(v, c.x, c.y, fw, ebits); break;
-            case 6: t_rot_pairs<E, 6, false>(v, c.x, c.y, fw, ebits); break;
-            default: t_rot_pairs<E, 7, false>(v, c.x, c.y, fw, ebits); break;
+            case 1: t_rot_pairs<E, 1, OP_RY>(v, c.x, c.y, fw, ebits); break;
+            case 2: t_rot_pairs<E, 2, OP_RY>(v, c.x, c.y, fw, ebits); break;
+            case 3: t_rot_pairs<E, 3, OP_RY>(v, c.x, c.y, fw, ebits); break;
+            case 4: t_rot_pairs<E, 4, OP_RY>(v, c.x, c.y, fw, ebits); break;
+            case 5: t_rot_pairs<E, 5, OP_RY>(v, c.x, c.y, fw, ebits); break;
+            case 6: t_rot_pairs<E, 6, OP_RY>(v, c.x, c.y, fw, ebits); break;
+            default: t_rot_pairs<E, 7, OP_RY>(v, c.x, c.y, fw, ebits); break;
           }
         } else if (kind == OP_RZ) {
 #pragma unroll
@@ -774,6 +777,16 @@ __global__ void __launch_bounds__(kThreads, FUSED ? 4 : 1) k_t_ops(BatchArgs A, 
           for (int e = 0; e < E; ++e) {
             const uint32_t f = fw ^ (ebits << (31 - e));
             v[e] = make_double2(t_flip(v[e].x, f), t_flip(v[e].y, f));
+          }
+        } else if (kind == OP_RYY) {
+          switch (flip) {
+            case 1: t_rot_pairs<E, 1, OP_RYY>(v, c.x, c.y, fw, ebits); break;
+            case 2: t_rot_pairs<E, 2, OP_RYY>(v, c.x, c.y, fw, ebits); break;
+            case 3: t_rot_pairs<E, 3, OP_RYY>(v, c.x, c.y, fw, ebits); break;
+            case 4: t_rot_pairs<E, 4, OP_RYY>(v, c.x, c.y, fw, ebits); break;
+            case 5: t_rot_pairs<E, 5, OP_RYY>(v, c.x, c.y, fw, ebits); break;
+            case 6: t_rot_pairs<E, 6, OP_RYY>(v, c.x, c.y, fw, ebits); break;
+            default: t_rot_pairs<E, 7, OP_RYY>(v, c.x, c.y, fw, ebits); break;
           }
         }
       }

@@ -10,6 +10,8 @@ from . import _lib
 from ._lib import VQEError, c_f64p, c_i32p, c_i64p, c_u64p
 
 GATE_CNOT, GATE_RX, GATE_RY, GATE_RZ, GATE_DEPOL1, GATE_DEPOL2 = range(6)
+# two-qubit Pauli rotations exp(+i theta/2 P_q0 P_q1) of the SU(4) gate set (reference VQE_qulacs_su4.py:68-90)
+GATE_RXX, GATE_RYY, GATE_RZZ = 6, 7, 8
 
 
 def _f64(a):
@@ -30,7 +32,8 @@ def _p(a, t):
 
 class Circuit:
     """Gate list in construct_ansatz order (reference VQE_qulacs_TN_notin_RL.py:13-45):
-    parallel int32 arrays ``kind, q0, q1, pidx`` and the number of parameters."""
+    parallel int32 arrays ``kind, q0, q1, pidx`` and the number of parameters.  RXX / RYY / RZZ
+    (VQE_qulacs_su4.py:13-45) take two distinct qubits and a parameter index."""
 
     # ``angles``: optional parameter values carried by the handle (the reference's qulacs
     # circuit holds its parameters; the VQAs shim uses this)

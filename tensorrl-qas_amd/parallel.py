@@ -212,6 +212,8 @@ def plan_amplitude_sharding(n: int, world: int, kind, q0, q1, xmask):
         raise ValueError("more ranks than amplitudes pairs")
     kind, q0, q1 = (np.asarray(a).astype(np.int64) for a in (kind, q0, q1))
     G = kind.size
+    if np.any(kind > 5):      # RXX / RYY / RZZ (engine.GATE_RXX..GATE_RZZ): a rank-bit qubit of such a gate has no local form here
+        raise NotImplementedError("amplitude sharding does not take RXX / RYY / RZZ gates")
     qubits = [[int(q0[i])] + ([int(q1[i])] if kind[i] in (0, 5) else []) for i in range(G)]
     supports = [[q for q in range(n) if (int(x) >> q) & 1] for x in xmask]
     if any(len(s) > nl for s in supports) or any(len(s) > nl for s in qubits):

@@ -1,7 +1,8 @@
 """OpenQASM 2 reader for the reference's tensor-network init circuits
 (dmrg-to-qc/init_state_circ/*.qasm, the text twin of the QPY files the reference loads
 with qiskit at environments/environment_qulacs_TN_notin_agent.py:79-84).  Only what those
-files contain: qreg, rx / ry / rz / cx, angle expressions in floats and pi."""
+files contain: qreg, rx / ry / rz / cx, the rxx / ryy / rzz of the SU(4) basis
+(dmrg-to-qc/dmrg_to_qc.py:292-296), angle expressions in floats and pi."""
 from __future__ import annotations
 
 import ast
@@ -9,6 +10,7 @@ import math
 import operator
 import re
 
+_TWO_QUBIT_ROT = ("rxx", "ryy", "rzz")
 _BIN = {ast.Add: operator.add, ast.Sub: operator.sub, ast.Mult: operator.mul, ast.Div: operator.truediv}
 
 
@@ -60,14 +62,16 @@ def parse(text: str):
         if not m:
             raise ValueError(f"cannot parse statement {s!r}")
         name = m.group(1)
-        if name not in ("rx", "ry", "rz", "cx"):
+        if name not in ("rx", "ry", "rz", "cx") + _TWO_QUBIT_ROT:
             raise ValueError(f"unsupported gate {name!r}")
         qs = [int(v) for v in re.findall(r"\[(\d+)\]", m.group(3))]
         if n is None or any(q >= n for q in qs):
             raise ValueError("qubit index out of range")
         ang = None if m.group(2) is None else parse_angle(m.group(2))
-        if (name == "cx") != (ang is None) or len(qs) != (2 if name == "cx" else 1):
+        if (name == "cx") != (ang is None) or len(qs) != (2 if name == "cx" or name in _TWO_QUBIT_ROT else 1):
             raise ValueError(f"malformed {name}")
+        if name in _TWO_QUBIT_ROT and qs[0] == qs[1]:
+            raise ValueError(f"malformed {name}: the two qubits coincide")
         gates.append(QasmGate(name, qs, ang))
     if n is None:
         raise ValueError("no qreg")

@@ -7,6 +7,7 @@
 #include "vqe_grad.h"
 #include "ham_layout.h"
 #include "dm_host.h"
+#include "env_step_host.h"
 
 #include <algorithm>
 #include <cmath>
@@ -203,8 +204,17 @@ int check_gates(vqe_t* h, int64_t n_gates, const int32_t* kind, const int32_t* q
   return VQE_OK;
 }
 
+// What one run() does with the resident batch (EnvStep: Minimize on the pre-action circuits, float32 round trip, energy
+// of the full circuits; Reduce: the streaming path's Pauli-term reduction alone, on the states of the previous run).
+enum class Run { Energy, Minimize, State, EnvStep, Reduce };
+
 template <int N>
-int launch_lds(vqe_t* h, int which, const BatchArgs& A) {
+int launch_lds(vqe_t* h, Run mode, BatchArgs A) {
+  if (mode == Run::EnvStep) {      // the minimize kernel, told to follow CircuitEnv.step
+    A.env_step = 1;
+    A.new_gate = h->has_new_gate ? h->d_new_gate.p : nullptr;
+  }
+  const bool minimize = mode == Run::Minimize || mode == Run::EnvStep;
   size_t lds = lds_bytes(N, A.max_ops, A.max_params, A.ham.n_groups, A.max_pair);
   // measurement knob: VQE_LDS_PAD=bytes of unused LDS per workgroup lowers the workgroups per CU
   static const long lds_pad = [] { const char* e = std::getenv("VQE_LDS_PAD"); return e ? std::atol(e) : 0L; }();
@@ -219,13 +229,15 @@ int launch_lds(vqe_t* h, int which, const BatchArgs& A) {
   // walk their rows of the matrices side by side (WaveRowsCtx).  The plain variant keeps neither (registers).
   constexpr bool kHasWide = N >= 6;
   static const bool wide_on = [] { const char* e = std::getenv("VQE_WIDE_UPDATE"); return !(e && e[0] == '0'); }();   // A/B knob
-  const bool wide = kHasWide && wide_on && which == 1 && A.max_params > 64;
+  const bool wide = kHasWide && wide_on && minimize && A.max_params > 64;
   const bool noisy = A.noise.p1 > 0.0 || A.noise.p2 > 0.0;
   constexpr bool kW = false;     // up to 64 parameters per circuit: the instantiation without the workgroup-wide update
-  const void* fn = which == 0 ? (const void*)k_lds_energy<N>
-                   : which == 1 ? (wide ? (noisy ? (const void*)k_lds_minimize<N, kHasWide, true> : (const void*)k_lds_minimize<N, kHasWide, false>)
-                                        : (noisy ? (const void*)k_lds_minimize<N, kW, true> : (const void*)k_lds_minimize<N, kW, false>))
-                                : (const void*)k_lds_state<N>;
+  void (*const kernel)(BatchArgs) =
+      mode == Run::Energy ? k_lds_energy<N>
+      : !minimize ? k_lds_state<N>
+      : wide ? (noisy ? k_lds_minimize<N, kHasWide, true> : k_lds_minimize<N, kHasWide, false>)
+             : (noisy ? k_lds_minimize<N, kW, true> : k_lds_minimize<N, kW, false>);
+  const void* fn = (const void*)kernel;
   HIP_TRY(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   {   // the unit loop addresses the state region absolutely (lds_load_abs): the dynamic LDS must start at 0
     hipFuncAttributes fa;
@@ -234,21 +246,16 @@ int launch_lds(vqe_t* h, int which, const BatchArgs& A) {
   }
   h->last_wg_per_cu = std::max(1, std::min(8, (int)(h->lds_per_cu / lds)));
   HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
-  const dim3 grid(which == 2 ? 1 : A.batch), block(Geo<N>::NT);
-  if (which == 0) hipLaunchKernelGGL(k_lds_energy<N>, grid, block, lds, h->stream, A);
-  else if (which == 1 && wide && noisy) hipLaunchKernelGGL((k_lds_minimize<N, kHasWide, true>), grid, block, lds, h->stream, A);
-  else if (which == 1 && wide) hipLaunchKernelGGL((k_lds_minimize<N, kHasWide, false>), grid, block, lds, h->stream, A);
-  else if (which == 1 && noisy) hipLaunchKernelGGL((k_lds_minimize<N, kW, true>), grid, block, lds, h->stream, A);
-  else if (which == 1) hipLaunchKernelGGL((k_lds_minimize<N, kW, false>), grid, block, lds, h->stream, A);
-  else hipLaunchKernelGGL(k_lds_state<N>, grid, block, lds, h->stream, A);
+  const dim3 grid(mode == Run::State ? 1 : A.batch), block(Geo<N>::NT);
+  hipLaunchKernelGGL(kernel, grid, block, lds, h->stream, A);
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
   return VQE_OK;
 }
 
-int dispatch_lds(vqe_t* h, int which, const BatchArgs& A) {
+int dispatch_lds(vqe_t* h, Run mode, const BatchArgs& A) {
   switch (h->n) {
-#define C(N) case N: return launch_lds<N>(h, which, A);
+#define C(N) case N: return launch_lds<N>(h, mode, A);
 #ifdef VQE_ONLY_N      // kernel experiments (tools/build_only_n.sh): one size, seconds to build
     C(VQE_ONLY_N)
 #else
@@ -459,15 +466,15 @@ int stream_cobyla(vqe_t* h, BatchArgs& A, const std::vector<int64_t>& pbeg, cons
 
 // Streaming path (n >= 14): kernels per op; the COBYLA loop runs all streams in lock-step (one batched
 // evaluation per iteration), its state on the device (stream_cobyla).
-int stream_run(vqe_t* h, int which, BatchArgs& A) {
+int stream_run(vqe_t* h, Run mode, BatchArgs& A) {
   HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
   int rc = 0;
-  if (which == 0) {
+  if (mode == Run::Energy) {
     rc = stream_evaluate(h->sw, A, A.ham.n_terms, h->stream, h->noise.eval_base, true, h->err, true, h->gen);
-  } else if (which == 4) {   // Pauli-term reduction only, on the states of the previous run
+  } else if (mode == Run::Reduce) {   // Pauli-term reduction only, on the states of the previous run
     if (h->sw.states_cap < ((size_t)h->batch << h->n)) return fail(h, VQE_ESTATE, "no states: run the energy first");
     rc = stream_evaluate(h->sw, A, A.ham.n_terms, h->stream, h->noise.eval_base, true, h->err, false, h->gen);
-  } else if (which == 2) {
+  } else if (mode == Run::State) {
     rc = stream_evaluate(h->sw, A, A.ham.n_terms, h->stream, h->noise.eval_base, false, h->err, true, h->gen);
     if (!rc) {
       const size_t dim = (size_t)1 << h->n;
@@ -475,7 +482,7 @@ int stream_run(vqe_t* h, int which, BatchArgs& A) {
                          h->sw.states, h->sw.masks, h->sw.meta);
       HIP_TRY(h, hipGetLastError());
     }
-  } else if (which == 1) {
+  } else if (mode == Run::Minimize) {
     const int B = h->batch;
     std::vector<double> x(h->h_theta), f(B, 0.0);
     std::vector<int32_t> nfev(B);
@@ -487,44 +494,22 @@ int stream_run(vqe_t* h, int which, BatchArgs& A) {
     HIP_TRY(h, hipMemcpyAsync(h->d_nfev.p, nfev.data(), (size_t)B * 4, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
   } else {
-    // which == 3: one CircuitEnv.step() per stream on the streaming path
-    // (environment_qulacs_TN_notin_agent.py:283-291): host-driven COBYLA on the PRE-action circuits (the new
-    // gate and the noise channel attached to it left out, its angle not a variable), float32 round trip,
-    // then the full circuits.
+    // Run::EnvStep: one CircuitEnv.step() per stream on the streaming path
+    // (environment_qulacs_TN_notin_agent.py:283-291): host-driven COBYLA on the PRE-action circuits (pre_action,
+    // vqe_geo.h; built by env_step_host.h), float32 round trip, then the full circuits.
     const int B = h->batch;
     std::vector<GateRec> g2;
     std::vector<int64_t> gbeg2(B), pbeg2(B);
-    std::vector<int32_t> gcnt2(B), pcnt2(B), hole(B, -1);
+    std::vector<int32_t> gcnt2(B), pcnt2(B), hole(B);
     std::vector<double> x0;
     g2.reserve(h->h_gates.size());
     for (int b = 0; b < B; ++b) {
-      const int64_t g0 = h->h_gate_begin[b];
-      const int G = h->h_gate_count[b];
-      const int skip = h->has_new_gate ? h->h_new_gate[b] : -1;
-      int skip_end = skip + 1;
-      if (skip >= 0) {
-        const GateRec r = h->h_gates[g0 + skip];
-        if (gate_is_rot(r.kind)) hole[b] = r.pidx;
-        // the attached channel: CNOT + DEPOL2 and R{X,Y,Z} + DEPOL1 only, as in k_lds_minimize - the SU(4) ansatz builder
-        // attaches none, a DEPOL2 behind an RXX / RYY / RZZ stays in the pre-action circuit
-        if (skip + 1 < G) {
-          const GateRec fo = h->h_gates[g0 + skip + 1];
-          if ((fo.kind == G_DEPOL1 && r.kind >= G_RX && r.kind <= G_RZ && fo.q0 == r.q0) ||
-              (fo.kind == G_DEPOL2 && r.kind == G_CNOT && fo.q0 == r.q0 && fo.q1 == r.q1))
-            skip_end = skip + 2;
-        }
-      }
       gbeg2[b] = (int64_t)g2.size();
       pbeg2[b] = (int64_t)x0.size();
-      for (int i = 0; i < G; ++i) {
-        if (i >= skip && i < skip_end) continue;
-        GateRec r = h->h_gates[g0 + i];
-        if (gate_is_rot(r.kind) && hole[b] >= 0 && r.pidx > hole[b]) r.pidx -= 1;
-        g2.push_back(r);
-      }
+      hole[b] = pre_action_circuit(h->h_gates.data() + h->h_gate_begin[b], h->h_gate_count[b],
+                                   h->has_new_gate ? h->h_new_gate[b] : -1, h->h_theta.data() + h->h_par_begin[b],
+                                   h->h_par_count[b], g2, x0).hole;
       gcnt2[b] = (int32_t)((int64_t)g2.size() - gbeg2[b]);
-      for (int j = 0; j < h->h_par_count[b]; ++j)
-        if (j != hole[b]) x0.push_back(h->h_theta[h->h_par_begin[b] + j]);
       pcnt2[b] = (int32_t)((int64_t)x0.size() - pbeg2[b]);
     }
     int rc2;
@@ -543,12 +528,8 @@ int stream_run(vqe_t* h, int which, BatchArgs& A) {
     if (rc) return rc;
     std::vector<double> xraw(h->h_theta), xr32(h->h_theta);
     for (int b = 0; b < B; ++b) {
-      int k = 0;
-      for (int j = 0; j < h->h_par_count[b]; ++j) {
-        const double v = j == hole[b] ? h->h_theta[h->h_par_begin[b] + j] : x0[pbeg2[b] + k++];
-        xraw[h->h_par_begin[b] + j] = v;
-        xr32[h->h_par_begin[b] + j] = (double)(float)v;
-      }
+      const int64_t p0 = h->h_par_begin[b];
+      merge_optimum(h->h_theta.data() + p0, h->h_par_count[b], hole[b], x0.data() + pbeg2[b], true, xr32.data() + p0, xraw.data() + p0);
     }
     if (h->total_params) {
       HIP_TRY(h, hipMemcpyAsync(h->d_x.p, xr32.data(), xr32.size() * 8, hipMemcpyHostToDevice, h->stream));
@@ -637,9 +618,9 @@ int dm_energy_one(vqe_t* h, const GateRec* g, int G, const double* theta, double
   return VQE_OK;
 }
 
-// The resident batch in exact channel mode: which = 0 energies, 1 COBYLA (host-driven on exact energies; with
-// A.env_step the pre-action circuit, float32 round trip and the energy of the full circuit, as the fused kernel does).
-int dm_run(vqe_t* h, int which, const BatchArgs& A) {
+// The resident batch in exact channel mode: Run::Energy, or COBYLA (host-driven on exact energies; Run::EnvStep: on the
+// pre-action circuit, then float32 round trip and the energy of the full circuit, as the fused kernel does).
+int dm_run(vqe_t* h, Run mode, const BatchArgs& A) {
   if (h->n < 2 || h->n > 13) return fail(h, VQE_EINVAL, "the exact channel mode (density matrix) serves 2 <= n_qubits <= 13");
   // the superoperator blocks (dm_host.h) are built from CNOT, RX, RY, RZ and the two channels only: refused before anything is launched
   for (int b = 0; b < h->batch; ++b)
@@ -653,39 +634,21 @@ int dm_run(vqe_t* h, int which, const BatchArgs& A) {
   h->dm_gpu_ms = 0.f;
   h->last_run_dm = true;
   const int B = h->batch;
+  const bool env_step = mode == Run::EnvStep;
   std::vector<double> f(B, 0.0), x(h->h_theta), xraw(h->h_theta);
   std::vector<int32_t> nfev(B, 1);
   for (int b = 0; b < B; ++b) {
     const GateRec* g = h->h_gates.data() + h->h_gate_begin[b];
     const int G = h->h_gate_count[b], P = h->h_par_count[b];
     double* xb = x.data() + h->h_par_begin[b];
-    if (which == 0) {
+    if (mode == Run::Energy) {
       if ((rc = dm_energy_one(h, g, G, xb, &f[b]))) return rc;
       continue;
     }
-    // the circuit COBYLA sees: without the new gate (and the channel attached to it) when this is an env-step
-    const int skip = (A.env_step && h->has_new_gate) ? h->h_new_gate[b] : -1;
-    int skip_end = skip + 1, hole = -1;
-    if (skip >= 0) {
-      const GateRec r = g[skip];
-      // (one-qubit rotations only: dm_run has refused every circuit that holds an RXX / RYY / RZZ above)
-      if (r.kind >= G_RX && r.kind <= G_RZ) hole = r.pidx;
-      if (skip + 1 < G) {
-        const GateRec fo = g[skip + 1];
-        if ((fo.kind == G_DEPOL1 && r.kind >= G_RX && r.kind <= G_RZ && fo.q0 == r.q0) ||
-            (fo.kind == G_DEPOL2 && r.kind == G_CNOT && fo.q0 == r.q0 && fo.q1 == r.q1))
-          skip_end = skip + 2;
-      }
-    }
+    // the circuit COBYLA sees: the pre-action circuit (pre_action, vqe_geo.h) when this is an env-step
     std::vector<GateRec> g2;
-    for (int i = 0; i < G; ++i) {
-      if (i >= skip && i < skip_end) continue;
-      GateRec r = g[i];
-      if (r.kind >= G_RX && r.kind <= G_RZ && hole >= 0 && r.pidx > hole) r.pidx -= 1;
-      g2.push_back(r);
-    }
     std::vector<double> xo;
-    for (int j = 0; j < P; ++j) if (j != hole) xo.push_back(xb[j]);
+    const int hole = pre_action_circuit(g, G, (env_step && h->has_new_gate) ? h->h_new_gate[b] : -1, xb, P, g2, xo).hole;
     double fo = 0.0;
     if (xo.empty()) {      // scipy returns after one evaluation
       if ((rc = dm_energy_one(h, g2.data(), (int)g2.size(), xo.data(), &fo))) return rc;
@@ -701,16 +664,11 @@ int dm_run(vqe_t* h, int which, const BatchArgs& A) {
       vqe_cobyla_result(cob, xo.data(), &fo, &nfev[b], nullptr);
       vqe_cobyla_destroy(cob);
     }
-    double* xr = xraw.data() + h->h_par_begin[b];
-    for (int j = 0, k = 0; j < P; ++j) {
-      const double v = j == hole ? xb[j] : xo[k++];
-      xr[j] = v;
-      xb[j] = A.env_step ? (double)(float)v : v;
-    }
+    merge_optimum(h->h_theta.data() + h->h_par_begin[b], P, hole, xo.data(), env_step, xb, xraw.data() + h->h_par_begin[b]);
     f[b] = fo;
-    if (A.env_step && (rc = dm_energy_one(h, g, G, xb, &f[b]))) return rc;
+    if (env_step && (rc = dm_energy_one(h, g, G, xb, &f[b]))) return rc;
   }
-  if (which != 0 && h->total_params) {
+  if (mode != Run::Energy && h->total_params) {
     HIP_TRY(h, hipMemcpyAsync(h->d_x.p, x.data(), x.size() * 8, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(h->d_xraw.p, xraw.data(), xraw.size() * 8, hipMemcpyHostToDevice, h->stream));
   }
@@ -721,23 +679,17 @@ int dm_run(vqe_t* h, int which, const BatchArgs& A) {
   return VQE_OK;
 }
 
-int run(vqe_t* h, int which, double rhobeg, double rhoend, int maxfun) {
+int run(vqe_t* h, Run mode, double rhobeg, double rhoend, int maxfun) {
   HIP_TRY(h, hipSetDevice(h->dev));
   BatchArgs A = make_args(h);
   A.rhobeg = rhobeg; A.rhoend = rhoend; A.maxfun = maxfun;
-  int rc;
-  if (which == 3) {
-    which = 1;
-    A.env_step = 1;
-    A.new_gate = h->has_new_gate ? h->d_new_gate.p : nullptr;
-    if (!h->lds_path) which = 3;      // streaming path: host-driven loop in stream_run
-  }
-  if ((which == 1 || which == 3) && (h->shard_world > 1 || h->amp_world > 1))
+  const bool optimise = mode == Run::Minimize || mode == Run::EnvStep;
+  if (optimise && (h->shard_world > 1 || h->amp_world > 1))
     return fail(h, VQE_ESTATE, "term-sharded handles hold partial energies: drive COBYLA with "
                                "vqe_cobyla_ask/tell and sum the partial energies of all ranks");
-  if (which == 4 && h->lds_path)
+  if (mode == Run::Reduce && h->lds_path)
     return fail(h, VQE_ESTATE, "the reduction-only launch exists on the streaming path (n >= 14) only");
-  if (h->trace_on && which == 1 && h->lds_path) {
+  if (h->trace_on && optimise && h->lds_path) {
     const size_t stride = (size_t)1 + (size_t)h->max_params, words = (size_t)h->batch * (size_t)maxfun * stride;
     HIP_TRY(h, h->d_trace.reserve(words));
     HIP_TRY(h, hipMemsetAsync(h->d_trace.p, 0, words * sizeof(double), h->stream));
@@ -745,12 +697,11 @@ int run(vqe_t* h, int which, double rhobeg, double rhoend, int maxfun) {
     h->trace_maxfun = maxfun; h->trace_stride = (int)stride; h->trace_batch = h->batch;
   }
   h->last_run_dm = false;
-  if (h->noise_mode == 1 && (which == 0 || which == 1 || which == 3)) return dm_run(h, which == 0 ? 0 : 1, A);
-  if (h->lds_path) rc = dispatch_lds(h, which, A);
-  else rc = stream_run(h, which, A);
+  if (h->noise_mode == 1 && (mode == Run::Energy || optimise)) return dm_run(h, mode, A);
+  const int rc = h->lds_path ? dispatch_lds(h, mode, A) : stream_run(h, mode, A);
   if (rc) return rc;
   // every evaluation of a stochastic run consumes fresh trajectory numbers
-  if (which != 4) h->noise.eval_base += ((which == 1 || which == 3) ? (uint64_t)maxfun + 1 : 1);
+  if (mode != Run::Reduce) h->noise.eval_base += (optimise ? (uint64_t)maxfun + 1 : 1);
   return VQE_OK;
 }
 
@@ -947,7 +898,7 @@ int vqe_get_state_dev(vqe_t* h, const double* theta, void* dev_amps) {
   if (rc) return rc;
   const size_t dim = (size_t)1 << h->n;
   HIP_TRY(h, h->d_state.reserve(dim));
-  if ((rc = run(h, 2, 0, 0, 0))) return rc;
+  if ((rc = run(h, Run::State, 0, 0, 0))) return rc;
   HIP_TRY(h, hipMemcpyAsync(dev_amps, h->d_state.p, dim * 16, hipMemcpyDeviceToDevice, h->stream));
   return VQE_OK;
 }
@@ -1209,7 +1160,7 @@ int vqe_energy_batch(vqe_t* h, int batch, const double* theta, double* energy) {
   int rc = load_single(h, batch, theta);
   if (rc) return rc;
   if ((rc = ready(h))) return rc;
-  if ((rc = run(h, 0, 0, 0, 0))) return rc;
+  if ((rc = run(h, Run::Energy, 0, 0, 0))) return rc;
   HIP_TRY(h, hipMemcpyAsync(energy, h->d_f.p, (size_t)batch * 8, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   return VQE_OK;
@@ -1225,7 +1176,7 @@ int vqe_get_state(vqe_t* h, const double* theta, double* amps) {
   if (rc) return rc;
   const size_t dim = (size_t)1 << h->n;
   HIP_TRY(h, h->d_state.reserve(dim));
-  if ((rc = run(h, 2, 0, 0, 0))) return rc;
+  if ((rc = run(h, Run::State, 0, 0, 0))) return rc;
   HIP_TRY(h, hipMemcpyAsync(amps, h->d_state.p, dim * 16, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   return VQE_OK;
@@ -1240,7 +1191,7 @@ int vqe_minimize_cobyla(vqe_t* h, const double* x0, double rhobeg, double rhoend
   int rc = load_single(h, 1, x0);
   if (rc) return rc;
   if ((rc = ready(h))) return rc;
-  if ((rc = run(h, 1, rhobeg, rhoend, maxfun))) return rc;
+  if ((rc = run(h, Run::Minimize, rhobeg, rhoend, maxfun))) return rc;
   return vqe_batch_fetch(h, x, f, nfev);
 }
 
@@ -1269,7 +1220,7 @@ int vqe_batch_load(vqe_t* h, int batch, const int64_t* gate_off, const int32_t* 
 int vqe_batch_run_energy(vqe_t* h) {
   int rc = ready(h);
   if (rc) return rc;
-  return run(h, 0, 0, 0, 0);
+  return run(h, Run::Energy, 0, 0, 0);
 }
 
 int vqe_energy_grad_batch(vqe_t* h, int batch, const double* theta, double* energy, double* grad) {
@@ -1308,14 +1259,14 @@ int vqe_batch_fetch_grad(vqe_t* h, double* grad) {
 int vqe_batch_run_reduction(vqe_t* h) {
   int rc = ready(h);
   if (rc) return rc;
-  return run(h, 4, 0, 0, 0);
+  return run(h, Run::Reduce, 0, 0, 0);
 }
 
 int vqe_batch_run_minimize(vqe_t* h, double rhobeg, double rhoend, int maxfun) {
   int rc = ready(h);
   if (rc) return rc;
   if (maxfun < 1 || !(rhobeg > 0) || !(rhoend > 0)) return fail(h, VQE_EINVAL, "bad COBYLA arguments");
-  return run(h, 1, rhobeg, rhoend, maxfun);
+  return run(h, Run::Minimize, rhobeg, rhoend, maxfun);
 }
 
 int vqe_batch_set_new_gate(vqe_t* h, const int32_t* new_gate) {
@@ -1337,7 +1288,7 @@ int vqe_batch_run_env_step(vqe_t* h, double rhobeg, double rhoend, int maxfun) {
   int rc = ready(h);
   if (rc) return rc;
   if (maxfun < 1 || !(rhobeg > 0) || !(rhoend > 0)) return fail(h, VQE_EINVAL, "bad COBYLA arguments");
-  return run(h, 3, rhobeg, rhoend, maxfun);
+  return run(h, Run::EnvStep, rhobeg, rhoend, maxfun);
 }
 
 int vqe_batch_fetch(vqe_t* h, double* x, double* f, int32_t* nfev) {

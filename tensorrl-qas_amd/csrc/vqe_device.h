@@ -1771,16 +1771,15 @@ __global__ void __launch_bounds__(Geo<N>::NT, Geo<N>::WPS) k_lds_minimize(BatchA
   const double* theta = A.theta + A.par_begin[b];
   double* xout = A.xout + A.par_begin[b];
   constexpr bool noisy = NOISY;
+  // The rule is pre_action (vqe_geo.h), which the host drivers call; this is a hand-kept copy of it, statement for
+  // statement, and a change must land in both.  A call would evaluate the gate-list loads in front of the test for a
+  // new gate, which perturbs the register allocation of the whole kernel.
   const int skip = A.new_gate ? A.new_gate[b] : -1;
   int p_hole = -1;
   int skip_end = skip + 1;   // (no new gate: the empty range [-1, 0))
   if (skip >= 0) {
     const GateRec r = A.gates[A.gate_begin[b] + skip];
     if (gate_is_rot(r.kind)) p_hole = r.pidx;
-    // the noise channel construct_ansatz puts behind every gate belongs to that gate: the
-    // pre-action circuit contains neither (VQE_qulacs_TN_notin_RL_noise.py:26-28,40-50)
-    // (RXX / RYY / RZZ on purpose not: the reference's SU(4) ansatz builder attaches no channel to its gates
-    // (VQE_qulacs_su4.py:13-63), so a DEPOL2 behind a new two-qubit rotation is a gate of its own and stays in)
     if (skip + 1 < A.gate_count[b]) {
       const GateRec f = A.gates[A.gate_begin[b] + skip + 1];
       if ((f.kind == G_DEPOL1 && r.kind >= G_RX && r.kind <= G_RZ && f.q0 == r.q0) ||

@@ -68,6 +68,28 @@ VQE_HD constexpr bool gate_is_rot2(int k) { return k >= G_RXX && k <= G_RZZ; }
 VQE_HD constexpr bool gate_is_rot(int k) { return (k >= G_RX && k <= G_RZ) || gate_is_rot2(k); }
 struct GateRec { int32_t kind, q0, q1, pidx; };           // as uploaded by the host
 
+// The circuit COBYLA sees in an environment step (CircuitEnv.step of the reference,
+// environments/environment_qulacs_TN_notin_agent.py:283-291,452-482): circuit g[0..G) WITHOUT the gate the action just
+// added, g[new_gate].  Gates [skip, skip_end) are left out; hole = parameter index of the new gate if it is a rotation
+// (its angle is not a variable), else -1.  The noise channel construct_ansatz puts behind every gate belongs to that
+// gate, so the pre-action circuit contains neither (VQE_qulacs_TN_notin_RL_noise.py:26-28,40-50): a DEPOL1 behind a
+// one-qubit rotation on the same qubit, a DEPOL2 behind a CNOT on the same (q0, q1).  RXX / RYY / RZZ on purpose not:
+// the reference's SU(4) ansatz builder attaches no channel to its gates (VQE_qulacs_su4.py:13-63), so a DEPOL2 behind
+// a new two-qubit rotation is a gate of its own and stays in.  No new gate: the empty range [-1, 0).
+struct PreAction { int skip, skip_end, hole; };
+VQE_HD inline PreAction pre_action(const GateRec* g, int G, int new_gate) {
+  if (new_gate < 0) return PreAction{-1, 0, -1};
+  const GateRec r = g[new_gate];
+  PreAction pa{new_gate, new_gate + 1, gate_is_rot(r.kind) ? r.pidx : -1};
+  if (new_gate + 1 < G) {
+    const GateRec fo = g[new_gate + 1];
+    if ((fo.kind == G_DEPOL1 && r.kind >= G_RX && r.kind <= G_RZ && fo.q0 == r.q0) ||
+        (fo.kind == G_DEPOL2 && r.kind == G_CNOT && fo.q0 == r.q0 && fo.q1 == r.q1))
+      pa.skip_end = new_gate + 2;
+  }
+  return pa;
+}
+
 // Depth of the energy step's table ring, and so the multiple to which the host pads the real-table sections of the
 // group list (by size: the shallower ring frees 32 registers where the kernel sits at its register cap -
 // n = 11 ... 13: +1..2 % - and costs 2..3 % where it does not)

@@ -547,6 +547,62 @@ def test_streaming_env_step_semantics(tq):
         assert nfev[b] == nh and np.array_equal(xr[sel], xh), (b, nfev[b], nh, np.abs(xr[sel] - xh).max())
 
 
+def test_streaming_env_step_leaves_out_the_attached_channel(tq):
+    """n = 14, the new gate is the last but one and carries the channel the noisy ansatz builder attached to it
+    (CNOT + DEPOL2, RX + DEPOL1): the host-built pre-action circuit of the streaming path leaves out both.  The noise
+    probabilities are 0, so the channels act as identities and only test the gate range: the new rotation keeps its
+    angle, x is xraw in float32, f is the oracle's energy of the full circuit, and the optimum of the pre-action cost
+    is no worse than its start."""
+    n, maxfun = 14, 20
+    rng = np.random.default_rng(1416)
+    psi0 = random_state(n, rng)
+    ham = random_hamiltonian(n, 20, rng)
+    eng = _engine(tq, n, psi0, ham)
+    eng.set_noise(0.0, 0.0, 5)
+    raw = []
+    for tail in ((0, 5), (1, 4)):      # CNOT + DEPOL2, RX + DEPOL1
+        qs = [int(q) for q in rng.permutation(n)[:4]]      # four gates in front: rotations on distinct qubits, one CNOT
+        kind, q0, q1, pidx = [2, 0, 3, 1], [qs[0], qs[1], qs[2], qs[3]], [-1, qs[0], -1, -1], [0, -1, 1, 2]
+        th = [float(v) for v in rng.uniform(-np.pi, np.pi, 3)]
+        c = int(rng.integers(n))
+        t = int((c + 1 + rng.integers(n - 1)) % n)
+        kind += list(tail)
+        q0 += [c, c]
+        q1 += [t, t] if tail[0] == 0 else [-1, -1]
+        pidx += [len(th) if tail[0] else -1, -1]
+        if tail[0]:
+            th.append(0.25)
+        g = tuple(np.array(v, np.int32) for v in (kind, q0, q1, pidx)) + (np.array(th, np.float32).astype(np.float64),)
+        assert g[0].size == 6 and g[4].size >= 3
+        raw.append(g)
+    new = [g[0].size - 2 for g in raw]
+    eng.batch_load([tq.Circuit(*g[:4], g[4].size) for g in raw], [g[4] for g in raw])
+    eng.batch_set_new_gate(new)
+    eng.batch_run_env_step(1.0, 1e-4, maxfun)
+    x, f, nfev = eng.batch_fetch()
+    xopt = eng.batch_fetch_xopt()
+    off = 0
+    for b, ((kind, q0, q1, pidx, th), at) in enumerate(zip(raw, new)):
+        P = th.size
+        xb, xr = x[off:off + P], xopt[off:off + P]
+        off += P
+        hole = int(pidx[at])
+        if hole >= 0:
+            assert xb[hole] == th[hole] and xr[hole] == th[hole]
+        assert np.array_equal(xb, xr.astype(np.float32).astype(np.float64))
+        e_full = vo.energy_pauli(vo.run_circuit(psi0, kind, q0, q1, pidx, xb), *ham)
+        print(f"b={b}: nfev {nfev[b]}, |f - oracle| = {abs(e_full - f[b]):.2e}")
+        assert abs(e_full - f[b]) < E_TOL
+        keep = np.ones(kind.size, bool)
+        keep[at] = keep[at + 1] = False      # the gate and ITS noise channel
+        sel = [j for j in range(P) if j != hole]
+        pre = np.where(pidx > hole, pidx - 1, pidx) if hole >= 0 else pidx
+        cost = lambda t: vo.energy_pauli(vo.run_circuit(psi0, kind[keep], q0[keep], q1[keep], pre[keep], t), *ham)
+        assert cost(xr[sel]) <= cost(th[sel]) + 1e-12
+        assert 1 <= nfev[b] <= maxfun
+    eng.close()
+
+
 def test_heisenberg_20q_circuit_env_episode(tmp_path):
     """BASELINE config 4 through the environment API: 20-qubit Heisenberg chain written by the package's own
     generator + npz writer (reference formula dmrg-to-qc/heisenberg_model.py:22-72; Lanczos ground energy

@@ -81,6 +81,14 @@ int vqe_vecenv_moments(vqe_vecenv_t* v, int32_t env, int32_t* moments /* n */, i
 int vqe_vecenv_actions(vqe_vecenv_t* v, int32_t env, int32_t* current /* 4 */, int32_t* previous /* 4 */);
 /* scipy's result.x of the last step (env.opt_ang_save): count via *n, values into out (may be NULL to query) */
 int vqe_vecenv_opt_ang(vqe_vecenv_t* v, int32_t env, double* out, int32_t* n);
+/* Which device optimiser every following step launches: VQE_ENV_OPT_COBYLA (the default; vqe_batch_run_env_step with
+ * scipy's COBYLA defaults and the config's maxfun; `opts` is ignored) or VQE_ENV_OPT_LBFGS
+ * (vqe_batch_run_env_step_lbfgs with `opts`, which must not be NULL: VQE_EINVAL; start from vqe_lbfgs_default_opts and
+ * set maxfun to the config's maxfun to keep nfev comparable with COBYLA's budget).
+ * The reference has no counterpart: its optimiser is the config's optim_alg, one environment at a time.  Refused
+ * (VQE_ESTATE) between step_begin and step_end, and for VQE_ENV_OPT_LBFGS on a noisy batch. */
+enum { VQE_ENV_OPT_COBYLA = 0, VQE_ENV_OPT_LBFGS = 1 };
+int vqe_vecenv_set_optimizer(vqe_vecenv_t* v, int kind, const vqe_lbfgs_opts_t* opts);
 /* kernel time of the last launch (HIP events) */
 int vqe_vecenv_last_kernel_ms(vqe_vecenv_t* v, float* ms);
 

@@ -222,6 +222,42 @@ int vqe_batch_fetch_grad(vqe_t* h, double* grad /* sum of n_params, layout of vq
 /* the optimiser's result before the float32 rounding of vqe_batch_run_env_step
  * (scipy's result.x, stored by the reference as env.opt_ang_save, :288); same layout as x */
 int vqe_batch_fetch_xopt(vqe_t* h, double* x /* sum of n_params */);
+/* ---- device L-BFGS on the adjoint gradient ---------------------------------------------------
+ * A batched quasi-Newton optimiser with the shape of the COBYLA launch: one workgroup per circuit, and the whole loop -
+ * energy + gradient (the adjoint sweep of vqe_energy_grad_batch), two-loop recursion over `history` pairs, Armijo
+ * backtracking - inside ONE launch, no host round trip per iteration.  The cost of an iteration does not grow with the
+ * number of parameters.
+ * replaces: scipy.optimize.minimize(cost, x0, method='L-BFGS-B', jac=...) of
+ * environment_qulacs_TN_notin_agent.py:452-482, B times - with this CAVEAT: it is NOT scipy's L-BFGS-B.  There are no
+ * bounds, the line search is Armijo backtracking (t = 1, 1/2, 1/4, ...; accept f(x + t d) <= f + c1 t g.d) and not
+ * More-Thuente, and the trajectories differ from scipy's.  CircuitEnv's optim_alg = "L-BFGS-B" keeps running scipy on
+ * the host.  The algorithm, decision for decision, is in csrc/vqe_lbfgs.h and DESIGN 4.8.
+ * status: 0 max|g_j| <= gtol; 1 f - f_new <= ftol max(|f|, |f_new|, 1); 2 no step accepted in max_ls trials (x, f
+ * unchanged); 3 maxfun evaluations used; 4 maxiter accepted steps made.  x is always the best point (Armijo makes f
+ * monotone).  Parameters that no gate uses never move.
+ * 1 <= n <= 13 (n >= 14: VQE_EINVAL).  Refused with VQE_ESTATE, before anything is launched, while Pauli noise, the
+ * exact channel mode, shot noise, an amplitude shard or a term shard (the line search needs the full energy) is set;
+ * VQE_EINVAL for history outside 1..16, maxiter < 0, maxfun < 1, max_ls < 1, a negative tolerance or c1 outside (0, 1).
+ * opts == NULL: the defaults. */
+typedef struct { int32_t history; int32_t maxiter; int32_t maxfun; int32_t max_ls;
+                 double gtol, ftol, c1; } vqe_lbfgs_opts_t;
+/* replaces: the `options` dict of that scipy call (:478) */
+int vqe_lbfgs_default_opts(vqe_lbfgs_opts_t* o);            /* 8, 100, 1000, 20, 1e-6, 1e-12, 1e-4 */
+/* replaces: one such scipy.optimize.minimize call on the circuit of vqe_set_circuit (see the caveat above);
+ * nit = accepted steps; nfev, nit, status may be NULL */
+int vqe_minimize_lbfgs(vqe_t* h, const double* x0, const vqe_lbfgs_opts_t* opts, double* x, double* f,
+                       int32_t* nfev, int32_t* nit, int32_t* status);
+/* replaces: B such calls, on the resident batch from x0 = theta0 (see the caveat above).  vqe_batch_fetch,
+ * vqe_batch_fetch_xopt, vqe_batch_energy_devptr, vqe_batch_copy_energy, vqe_last_kernel_ms and - after
+ * vqe_batch_set_trace(1) - vqe_batch_fetch_trace serve these launches as they serve COBYLA's. */
+int vqe_batch_run_minimize_lbfgs(vqe_t* h, const vqe_lbfgs_opts_t* opts);
+/* replaces: B CircuitEnv.step() calls with a gradient optim_alg (environment_qulacs_TN_notin_agent.py:283-291,452-482;
+ * see the caveat above): vqe_batch_run_env_step with the L-BFGS in COBYLA's place - it optimises the circuit WITHOUT
+ * gate new_gate[b] (vqe_batch_set_new_gate), rounds the optimum to float32 and returns the energy of the FULL circuit
+ * at those angles in f; the new rotation keeps its theta0 value. */
+int vqe_batch_run_env_step_lbfgs(vqe_t* h, const vqe_lbfgs_opts_t* opts);
+/* replaces: result.nit / result.status of those scipy calls (status numbered as above); either pointer may be NULL */
+int vqe_batch_fetch_lbfgs_info(vqe_t* h, int32_t* nit /* batch */, int32_t* status /* batch */);
 /* device pointer to the batch's f / energy array (float64[batch]) for on-device
  * reductions by the caller (e.g. torch.distributed all_reduce over RCCL) */
 int vqe_batch_energy_devptr(vqe_t* h, void** dev_ptr);

@@ -24,6 +24,12 @@ c_u64p = C.POINTER(C.c_uint64)
 c_f64p = C.POINTER(C.c_double)
 vp = C.c_void_p
 
+class LbfgsOpts(C.Structure):
+    """vqe_lbfgs_opts_t of include/vqe_hip.h"""
+    _fields_ = [("history", C.c_int32), ("maxiter", C.c_int32), ("maxfun", C.c_int32), ("max_ls", C.c_int32),
+                ("gtol", C.c_double), ("ftol", C.c_double), ("c1", C.c_double)]
+
+
 # name -> (restype, argtypes); mirrors include/vqe_hip.h one to one
 SIGNATURES = {
     "vqe_create": (C.c_int, [C.c_int, C.c_int, C.POINTER(vp)]),
@@ -70,6 +76,11 @@ SIGNATURES = {
     "vqe_batch_fetch_xopt": (C.c_int, [vp, c_f64p]),
     "vqe_batch_run_energy_grad": (C.c_int, [vp]),
     "vqe_batch_fetch_grad": (C.c_int, [vp, c_f64p]),
+    "vqe_lbfgs_default_opts": (C.c_int, [C.POINTER(LbfgsOpts)]),
+    "vqe_minimize_lbfgs": (C.c_int, [vp, c_f64p, C.POINTER(LbfgsOpts), c_f64p, c_f64p, c_i32p, c_i32p, c_i32p]),
+    "vqe_batch_run_minimize_lbfgs": (C.c_int, [vp, C.POINTER(LbfgsOpts)]),
+    "vqe_batch_run_env_step_lbfgs": (C.c_int, [vp, C.POINTER(LbfgsOpts)]),
+    "vqe_batch_fetch_lbfgs_info": (C.c_int, [vp, c_i32p, c_i32p]),
     "vqe_batch_energy_devptr": (C.c_int, [vp, C.POINTER(vp)]),
     "vqe_batch_copy_energy": (C.c_int, [vp, vp]),
     "vqe_batch_set_trace": (C.c_int, [vp, C.c_int]),
@@ -111,6 +122,7 @@ SIGNATURES.update({
     "vqe_vecenv_actions": (C.c_int, [vp, C.c_int32, c_i32p, c_i32p]),
     "vqe_vecenv_opt_ang": (C.c_int, [vp, C.c_int32, c_f64p, c_i32p]),
     "vqe_vecenv_last_kernel_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
+    "vqe_vecenv_set_optimizer": (C.c_int, [vp, C.c_int, C.POINTER(LbfgsOpts)]),
 })
 
 # include/mps2qc_hip.h (libmps2qc_hip.so: the offline MPS -> PQC fit)

@@ -63,6 +63,8 @@ struct vqe_vecenv {
   std::vector<Env> env;
   std::string err;
   bool pending = false;
+  int optimizer = VQE_ENV_OPT_COBYLA;      // vqe_vecenv_set_optimizer
+  vqe_lbfgs_opts_t lbfgs{};
   // flat batch description (reused)
   std::vector<int64_t> gate_off, par_off;
   std::vector<int32_t> kind, q0, q1, pidx, new_gate, nfev;
@@ -319,7 +321,9 @@ int vqe_vecenv_step_begin(vqe_vecenv_t* v, const int32_t* actions) {
   int rc = vqe_batch_load(v->eng, B, v->gate_off.data(), v->kind.data(), v->q0.data(), v->q1.data(), v->pidx.data(),
                           v->par_off.data(), v->theta.data());
   if (!rc) rc = vqe_batch_set_new_gate(v->eng, v->new_gate.data());
-  if (!rc) rc = vqe_batch_run_env_step(v->eng, 1.0, 1e-4, v->cfg.maxfun);   // scipy 1.15 COBYLA defaults (:478)
+  if (!rc) rc = v->optimizer == VQE_ENV_OPT_LBFGS
+                    ? vqe_batch_run_env_step_lbfgs(v->eng, &v->lbfgs)
+                    : vqe_batch_run_env_step(v->eng, 1.0, 1e-4, v->cfg.maxfun);   // scipy 1.15 COBYLA defaults (:478)
   if (rc) return fail(v, rc, std::string("engine: ") + vqe_last_error(v->eng));
   v->pending = true;
   return VQE_OK;
@@ -437,6 +441,19 @@ int vqe_vecenv_opt_ang(vqe_vecenv_t* v, int32_t b, double* out, int32_t* n) {
   const auto& o = v->env[b].opt_ang;
   *n = (int32_t)o.size();
   if (out) std::copy(o.begin(), o.end(), out);
+  return VQE_OK;
+}
+
+int vqe_vecenv_set_optimizer(vqe_vecenv_t* v, int kind, const vqe_lbfgs_opts_t* opts) {
+  if (!v) return VQE_EINVAL;
+  if (kind != VQE_ENV_OPT_COBYLA && kind != VQE_ENV_OPT_LBFGS) return fail(v, VQE_EINVAL, "unknown optimiser kind");
+  if (v->pending) return fail(v, VQE_ESTATE, "set_optimizer between step_begin and step_end");
+  if (kind == VQE_ENV_OPT_LBFGS) {
+    if (v->cfg.noisy) return fail(v, VQE_ESTATE, "the device L-BFGS takes no noisy batch");
+    if (!opts) return fail(v, VQE_EINVAL, "VQE_ENV_OPT_LBFGS needs its options");
+    v->lbfgs = *opts;
+  }
+  v->optimizer = kind;
   return VQE_OK;
 }
 

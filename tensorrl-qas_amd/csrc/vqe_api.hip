@@ -5,6 +5,7 @@
 #include "vqe_stream.h"
 #include "vqe_dm.h"
 #include "vqe_grad.h"
+#include "vqe_lbfgs.h"
 #include "ham_layout.h"
 #include "dm_host.h"
 #include "env_step_host.h"
@@ -124,6 +125,10 @@ struct vqe_handle {
   DevBuf<double> g_tab, d_grad;
   DevBuf<double2> g_lam;
   GradHam gham{};
+  // device L-BFGS (vqe_lbfgs.h): per-workgroup slices of the optimiser's vectors, per-circuit iteration count and status
+  DevBuf<double> lb_work;
+  DevBuf<int32_t> lb_nit, lb_status;
+  int lb_batch = 0;      // circuits of the last L-BFGS run on the resident batch (0: none)
 };
 
 #ifdef VQE_STAMPS
@@ -360,6 +365,7 @@ int load_batch(vqe_t* h, int batch, const std::vector<GateRec>& gates,
   h->h_gate_begin = gbeg;
   h->h_theta.assign(theta0, theta0 + total_params);
   h->has_new_gate = false;
+  h->lb_batch = 0;
   ++h->gen;
   return VQE_OK;
 }
@@ -697,6 +703,7 @@ int run(vqe_t* h, Run mode, double rhobeg, double rhoend, int maxfun) {
     h->trace_maxfun = maxfun; h->trace_stride = (int)stride; h->trace_batch = h->batch;
   }
   h->last_run_dm = false;
+  h->lb_batch = 0;             // fout / nfev are about to be another run's: the L-BFGS info of an earlier one is stale
   if (h->noise_mode == 1 && (mode == Run::Energy || optimise)) return dm_run(h, mode, A);
   const int rc = h->lds_path ? dispatch_lds(h, mode, A) : stream_run(h, mode, A);
   if (rc) return rc;
@@ -784,6 +791,94 @@ int run_grad(vqe_t* h) {
 #undef C
   }
   return fail(h, VQE_EINVAL, "energy gradients are computed for n_qubits <= 13 (LDS-resident path) only");
+}
+
+// ---- device L-BFGS (vqe_lbfgs.h) -------------------------------------------------------------
+// Everything a run of k_lds_minimize_lbfgs can be refused for, checked before anything is loaded or launched; *o
+// receives the options (NULL: the defaults).
+int lbfgs_check(vqe_t* h, const vqe_lbfgs_opts_t* opts, vqe_lbfgs_opts_t* o) {
+  (void)vqe_lbfgs_default_opts(o);
+  if (opts) *o = *opts;
+  int rc;
+  if (h->amp_world > 1) return fail(h, VQE_ESTATE, "the device L-BFGS takes no amplitude shard");      // (only n >= 14 can hold one)
+  if ((rc = grad_refusal(h))) return rc;
+  if (h->shard_world > 1)
+    return fail(h, VQE_ESTATE, "term-sharded handles hold partial energies: the line search of the device L-BFGS needs the full energy");
+  if (o->history < 1 || o->history > kLbfgsMaxHistory) return fail(h, VQE_EINVAL, "L-BFGS history must be in [1, 16]");
+  if (o->maxiter < 0 || o->maxfun < 1 || o->max_ls < 1) return fail(h, VQE_EINVAL, "L-BFGS needs maxiter >= 0, maxfun >= 1, max_ls >= 1");
+  if (!(o->gtol >= 0.0) || !(o->ftol >= 0.0)) return fail(h, VQE_EINVAL, "L-BFGS tolerances must be >= 0");
+  if (!(o->c1 > 0.0 && o->c1 < 1.0)) return fail(h, VQE_EINVAL, "L-BFGS c1 must be in (0, 1)");
+  return VQE_OK;
+}
+
+template <int N>
+int launch_lbfgs(vqe_t* h, const BatchArgs& A, LbfgsArgs O) {
+  constexpr int NW = Geo<N>::NW;
+  bool lam_global = N >= 13;
+  size_t lds = lbfgs_lds_bytes(N, lam_global, A.max_ops, A.max_params, NW);
+  if (!lam_global && lds > (size_t)h->lds_per_cu) {      // psi + lambda + ops do not fit: lambda moves to global memory
+    lam_global = true;
+    lds = lbfgs_lds_bytes(N, true, A.max_ops, A.max_params, NW);
+  }
+  if (lds > (size_t)h->lds_per_cu) return fail(h, VQE_EINVAL, "circuit too large for the device L-BFGS kernel (gates + parameters)");
+  const int wg_per_cu = std::max(1, (int)(h->lds_per_cu / lds));
+  const void* fn = lam_global ? (const void*)k_lds_minimize_lbfgs<N, true> : (const void*)k_lds_minimize_lbfgs<N, false>;
+  HIP_TRY(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  h->last_wg_per_cu = std::min(8, wg_per_cu);
+  int grid = A.batch;
+  if (lam_global) {
+    grid = std::min(A.batch, h->cu_count * wg_per_cu);
+    HIP_TRY(h, h->g_lam.reserve((size_t)grid << N));
+  }
+  HIP_TRY(h, h->lb_work.reserve((size_t)grid * lbfgs_work_doubles(A.max_params, O.m)));
+  O.work = h->lb_work.p;
+  HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
+  if (lam_global)
+    hipLaunchKernelGGL((k_lds_minimize_lbfgs<N, true>), dim3(grid), dim3(Geo<N>::NT), lds, h->stream, A, h->gham, O, h->g_lam.p);
+  else
+    hipLaunchKernelGGL((k_lds_minimize_lbfgs<N, false>), dim3(grid), dim3(Geo<N>::NT), lds, h->stream, A, h->gham, O, (double2*)nullptr);
+  HIP_TRY(h, hipGetLastError());
+  HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
+  return VQE_OK;
+}
+
+// o: options that passed lbfgs_check
+int run_lbfgs(vqe_t* h, bool env_step, const vqe_lbfgs_opts_t& o) {
+  int rc;
+  HIP_TRY(h, hipSetDevice(h->dev));
+  if ((rc = build_grad_tables(h))) return rc;
+  BatchArgs A = make_args(h);
+  A.maxfun = o.maxfun;
+  if (env_step) {
+    A.env_step = 1;
+    A.new_gate = h->has_new_gate ? h->d_new_gate.p : nullptr;
+  }
+  if (h->trace_on) {
+    const size_t stride = (size_t)1 + (size_t)h->max_params, words = (size_t)h->batch * (size_t)o.maxfun * stride;
+    HIP_TRY(h, h->d_trace.reserve(words));
+    HIP_TRY(h, hipMemsetAsync(h->d_trace.p, 0, words * sizeof(double), h->stream));
+    A.trace = h->d_trace.p;
+    h->trace_maxfun = o.maxfun; h->trace_stride = (int)stride; h->trace_batch = h->batch;
+  }
+  HIP_TRY(h, h->lb_nit.reserve(h->batch));
+  HIP_TRY(h, h->lb_status.reserve(h->batch));
+  LbfgsArgs O{o.history, o.maxiter, o.maxfun, o.max_ls, o.gtol, o.ftol, o.c1, nullptr, h->lb_nit.p, h->lb_status.p};
+  h->last_run_dm = false;
+  h->lb_batch = 0;
+  rc = VQE_EINVAL;
+  switch (h->n) {
+#define C(N) case N: rc = launch_lbfgs<N>(h, A, O); break;
+#ifdef VQE_ONLY_N
+    C(VQE_ONLY_N)
+#else
+    C(1) C(2) C(3) C(4) C(5) C(6) C(7) C(8) C(9) C(10) C(11) C(12) C(13)
+#endif
+#undef C
+    default: return fail(h, VQE_EINVAL, "the device L-BFGS serves n_qubits <= 13 (LDS-resident path) only");
+  }
+  if (rc) return rc;
+  h->lb_batch = h->batch;
+  return VQE_OK;
 }
 
 }  // namespace
@@ -1289,6 +1384,55 @@ int vqe_batch_run_env_step(vqe_t* h, double rhobeg, double rhoend, int maxfun) {
   if (rc) return rc;
   if (maxfun < 1 || !(rhobeg > 0) || !(rhoend > 0)) return fail(h, VQE_EINVAL, "bad COBYLA arguments");
   return run(h, Run::EnvStep, rhobeg, rhoend, maxfun);
+}
+
+int vqe_lbfgs_default_opts(vqe_lbfgs_opts_t* o) {
+  if (!o) return VQE_EINVAL;
+  *o = vqe_lbfgs_opts_t{8, 100, 1000, 20, 1e-6, 1e-12, 1e-4};
+  return VQE_OK;
+}
+
+int vqe_minimize_lbfgs(vqe_t* h, const double* x0, const vqe_lbfgs_opts_t* opts, double* x, double* f, int32_t* nfev,
+                       int32_t* nit, int32_t* status) {
+  if (!h) return VQE_EINVAL;
+  vqe_lbfgs_opts_t o;
+  int rc;
+  if ((rc = lbfgs_check(h, opts, &o))) return rc;
+  if (!f || (h->circ_params > 0 && (!x0 || !x))) return fail(h, VQE_EINVAL, "x0 / x / f is NULL");
+  HIP_TRY(h, hipSetDevice(h->dev));
+  if ((rc = load_single(h, 1, x0))) return rc;
+  if ((rc = ready(h))) return rc;
+  if ((rc = run_lbfgs(h, false, o))) return rc;
+  if ((rc = vqe_batch_fetch(h, x, f, nfev))) return rc;
+  return (nit || status) ? vqe_batch_fetch_lbfgs_info(h, nit, status) : VQE_OK;
+}
+
+int vqe_batch_run_minimize_lbfgs(vqe_t* h, const vqe_lbfgs_opts_t* opts) {
+  if (!h) return VQE_EINVAL;
+  vqe_lbfgs_opts_t o;
+  int rc;
+  if ((rc = lbfgs_check(h, opts, &o))) return rc;
+  if ((rc = ready(h))) return rc;
+  return run_lbfgs(h, false, o);
+}
+
+int vqe_batch_run_env_step_lbfgs(vqe_t* h, const vqe_lbfgs_opts_t* opts) {
+  if (!h) return VQE_EINVAL;
+  vqe_lbfgs_opts_t o;
+  int rc;
+  if ((rc = lbfgs_check(h, opts, &o))) return rc;
+  if ((rc = ready(h))) return rc;
+  return run_lbfgs(h, true, o);
+}
+
+int vqe_batch_fetch_lbfgs_info(vqe_t* h, int32_t* nit, int32_t* status) {
+  if (!h) return VQE_EINVAL;
+  if (h->batch <= 0 || h->lb_batch != h->batch) return fail(h, VQE_ESTATE, "no device L-BFGS run on the resident batch");
+  HIP_TRY(h, hipSetDevice(h->dev));
+  if (nit) HIP_TRY(h, hipMemcpyAsync(nit, h->lb_nit.p, (size_t)h->batch * 4, hipMemcpyDeviceToHost, h->stream));
+  if (status) HIP_TRY(h, hipMemcpyAsync(status, h->lb_status.p, (size_t)h->batch * 4, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return VQE_OK;
 }
 
 int vqe_batch_fetch(vqe_t* h, double* x, double* f, int32_t* nfev) {

@@ -251,6 +251,34 @@ class VQEEngine:
                                                 _p(x, c_f64p), C.byref(f), C.byref(nfev)))
         return x, f.value, nfev.value
 
+    # -- device L-BFGS on the adjoint gradient (NOT scipy's L-BFGS-B: no bounds, Armijo backtracking) ----
+    LBFGS_STATUS = {0: "gtol", 1: "ftol", 2: "line search failed", 3: "maxfun", 4: "maxiter"}
+
+    def lbfgs_opts(self, **opts):
+        """vqe_lbfgs_opts_t with the library's defaults (history 8, maxiter 100, maxfun 1000, max_ls 20, gtol 1e-6,
+        ftol 1e-12, c1 1e-4) and the given fields replaced."""
+        o = _lib.LbfgsOpts()
+        self._chk(self._lib.vqe_lbfgs_default_opts(C.byref(o)))
+        names = {f[0] for f in _lib.LbfgsOpts._fields_}
+        for k, v in opts.items():
+            if k not in names:
+                raise TypeError(f"unknown L-BFGS option {k!r} (known: {sorted(names)})")
+            setattr(o, k, float(v) if k in ("gtol", "ftol", "c1") else int(v))
+        return o
+
+    def minimize_lbfgs(self, x0, **opts):
+        """Minimise E from x0 with the device L-BFGS (one launch).  Returns (x, f, nfev, nit, status)."""
+        x0 = _f64(x0)
+        if x0.size != self._P:
+            raise ValueError("x0 has the wrong length")
+        o = self.lbfgs_opts(**opts)
+        x = np.empty_like(x0)
+        f = C.c_double()
+        nfev, nit, st = C.c_int32(), C.c_int32(), C.c_int32()
+        self._chk(self._lib.vqe_minimize_lbfgs(self._h, _p(x0, c_f64p), C.byref(o), _p(x, c_f64p), C.byref(f),
+                                               C.byref(nfev), C.byref(nit), C.byref(st)))
+        return x, f.value, nfev.value, nit.value, st.value
+
     # -- batches of circuits --------------------------------------------------------------
     def batch_load(self, circuits, thetas):
         """``circuits``: list of Circuit; ``thetas``: list of arrays (x0 / theta per circuit)."""
@@ -296,6 +324,23 @@ class VQEEngine:
 
     def batch_run_env_step(self, rhobeg=1.0, rhoend=1e-4, maxfun=1000):
         self._chk(self._lib.vqe_batch_run_env_step(self._h, rhobeg, rhoend, int(maxfun)))
+
+    def batch_run_minimize_lbfgs(self, **opts):
+        """The device L-BFGS on every circuit of the resident batch, one launch (results: batch_fetch, batch_fetch_lbfgs_info)."""
+        o = self.lbfgs_opts(**opts)
+        self._chk(self._lib.vqe_batch_run_minimize_lbfgs(self._h, C.byref(o)))
+
+    def batch_run_env_step_lbfgs(self, **opts):
+        """batch_run_env_step with the device L-BFGS in COBYLA's place (honours batch_set_new_gate)."""
+        o = self.lbfgs_opts(**opts)
+        self._chk(self._lib.vqe_batch_run_env_step_lbfgs(self._h, C.byref(o)))
+
+    def batch_fetch_lbfgs_info(self):
+        """(nit, status) per circuit of the last device L-BFGS run."""
+        nit = np.empty(self._batch, np.int32)
+        st = np.empty(self._batch, np.int32)
+        self._chk(self._lib.vqe_batch_fetch_lbfgs_info(self._h, _p(nit, c_i32p), _p(st, c_i32p)))
+        return nit, st
 
     def batch_fetch(self, want_x=True):
         x = np.empty(self._total_params, np.float64) if want_x else None

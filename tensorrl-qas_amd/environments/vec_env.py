@@ -75,13 +75,31 @@ class _EnvView:
 
 
 class VecCircuitEnv:
-    def __init__(self, env_cls, conf, device, num_envs: int, seed: int = 0, native: bool | None = None):
+    """``device_optimizer``: the optimiser of every step's fused launch, a property of the batch and not of the
+    reference's config file - "cobyla" (default: batch_run_env_step, the config's optim_alg = COBYLA) or "lbfgs"
+    (batch_run_env_step_lbfgs: the device L-BFGS on adjoint gradients, noiseless configurations only; NOT scipy's
+    L-BFGS-B).  ``lbfgs_opts``: options of VQEEngine.lbfgs_opts; ``maxfun`` defaults to the config's global_iters so
+    that nfev stays comparable with COBYLA's budget."""
+
+    def __init__(self, env_cls, conf, device, num_envs: int, seed: int = 0, native: bool | None = None,
+                 device_optimizer: str = "cobyla", lbfgs_opts: dict | None = None):
         if not issubclass(env_cls, CircuitEnvBase):
             raise TypeError("env_cls must be one of the CircuitEnv classes of this package")
+        if device_optimizer not in ("cobyla", "lbfgs"):
+            raise ValueError('device_optimizer must be "cobyla" or "lbfgs"')
+        if lbfgs_opts is not None and device_optimizer != "lbfgs":
+            raise ValueError('lbfgs_opts needs device_optimizer = "lbfgs"')
         first = env_cls(conf, device, seed=seed)
         if first.optimizer_kind not in (None, "device_cobyla"):
             raise NotImplementedError(f"VecCircuitEnv runs the device COBYLA of batch_run_env_step only; optim_alg = "
                                       f"{first.optim_alg!r} is served by CircuitEnv")
+        self.device_optimizer = device_optimizer
+        self._lbfgs_opts = None
+        if device_optimizer == "lbfgs":
+            if first.NOISY or first.phys_noise or first.n_shots:
+                raise NotImplementedError("device_optimizer = 'lbfgs' needs an exact, deterministic energy: noisy and "
+                                          "finite-shot configurations are served by the device COBYLA")
+            self._lbfgs_opts = {"maxfun": int(first.global_iters), **(lbfgs_opts or {})}
         self.engine = first.engine
         self._proto = first
         self.num_envs = num_envs
@@ -134,6 +152,9 @@ class VecCircuitEnv:
         rc = lib.vqe_vecenv_create(C.byref(cfg), self.engine._h, C.byref(self._h))
         if rc:
             raise _lib.VQEError(f"vqe_vecenv_create failed ({rc})")
+        if self._lbfgs_opts is not None:
+            o = self.engine.lbfgs_opts(**self._lbfgs_opts)
+            self._chk(lib.vqe_vecenv_set_optimizer(self._h, 1, C.byref(o)))
         self._base_obs = base_obs.to(self.device)
         self._obs = self._base_obs.repeat(B, 1)
         self._cache = {}
@@ -250,7 +271,10 @@ class VecCircuitEnv:
         eng = self.engine
         eng.batch_load([p[1] for p in pre], [p[2] for p in pre])
         eng.batch_set_new_gate([p[3] for p in pre])
-        eng.batch_run_env_step(1.0, 1e-4, int(self.envs[0].global_iters))
+        if self._lbfgs_opts is not None:
+            eng.batch_run_env_step_lbfgs(**self._lbfgs_opts)
+        else:
+            eng.batch_run_env_step(1.0, 1e-4, int(self.envs[0].global_iters))
         self._pending = (pre, actions)
 
     def step_wait(self, train_flag=True):

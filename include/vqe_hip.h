@@ -114,6 +114,9 @@ int vqe_set_term_shard(vqe_t* h, int rank, int world);
  * partial energies are summed by the caller exactly as for term sharding.  Work and memory
  * traffic of the reduction are 1/world per rank. */
 int vqe_set_amplitude_shard(vqe_t* h, int rank, int world);
+/* n >= 14: allow vqe_energy_grad_batch / vqe_batch_run_energy_grad on the streaming path (a second
+ * state-sized buffer per resident stream).  0 (default): VQE_EINVAL as before.  n <= 13: accepted, no effect. */
+int vqe_set_stream_grad(vqe_t* h, int enable);
 /* The one collective of the term-sharded sum as a library call (RCCL over xGMI; librccl is opened lazily).  Rank 0
  * makes the 128-byte id (vqe_comm_unique_id) and hands it to the other ranks by any means; every rank calls
  * vqe_comm_init on its handle; vqe_comm_allreduce_energy sums the batch's energy array (float64[batch], what
@@ -167,7 +170,10 @@ int vqe_energy_batch(vqe_t* h, int batch, const double* theta /* batch x n_param
  * parameters).  grad[b * P + j] sums over every gate with parameter index j (0 for a parameter no gate uses).
  * replaces: the finite-difference gradient scipy.optimize.minimize builds for a gradient method when the reference
  * passes no `jac` (environment_qulacs_TN_notin_agent.py:452-482 with optim_alg = BFGS, L-BFGS-B, ...): P + 1
- * sequential get_exp_val calls per gradient.  1 <= n <= 13 (LDS-resident path; n >= 14: VQE_EINVAL).  Refused with
+ * sequential get_exp_val calls per gradient.  1 <= n <= 13: the LDS-resident kernel.  n >= 14: VQE_EINVAL unless
+ * vqe_set_stream_grad(h, 1) was called; then the streaming path computes it (forward sweeps, lambda = H psi in a second
+ * state-sized buffer, backward sweeps over both).  Such a call undoes the circuit on the resident states: a
+ * vqe_batch_run_reduction right after it is refused with VQE_ESTATE.  Refused with
  * VQE_ESTATE while Pauli noise (p1 or p2 > 0), the exact channel noise mode, shot noise or an amplitude shard is set
  * on the handle.  On a term-sharded handle energy and gradient are the shard's partial sums. */
 int vqe_energy_grad_batch(vqe_t* h, int batch, const double* theta /* batch x P */,

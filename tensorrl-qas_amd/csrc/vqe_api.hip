@@ -129,6 +129,9 @@ struct vqe_handle {
   DevBuf<double> lb_work;
   DevBuf<int32_t> lb_nit, lb_status;
   int lb_batch = 0;      // circuits of the last L-BFGS run on the resident batch (0: none)
+  // adjoint gradient of the streaming path (vqe_stream_grad.h): opt-in (vqe_set_stream_grad); its backward sweep undoes
+  // the circuit in place, so the states it leaves are not those a reduction-only launch may take
+  bool stream_grad = false, stream_states_undone = false;
 };
 
 #ifdef VQE_STAMPS
@@ -473,8 +476,11 @@ int stream_cobyla(vqe_t* h, BatchArgs& A, const std::vector<int64_t>& pbeg, cons
 // Streaming path (n >= 14): kernels per op; the COBYLA loop runs all streams in lock-step (one batched
 // evaluation per iteration), its state on the device (stream_cobyla).
 int stream_run(vqe_t* h, Run mode, BatchArgs& A) {
+  if (mode == Run::Reduce && h->stream_states_undone)
+    return fail(h, VQE_ESTATE, "the states of the last run were undone by its gradient sweep: run the energy first");
   HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
   int rc = 0;
+  if (mode != Run::Reduce) h->stream_states_undone = false;
   if (mode == Run::Energy) {
     rc = stream_evaluate(h->sw, A, A.ham.n_terms, h->stream, h->noise.eval_base, true, h->err, true, h->gen);
   } else if (mode == Run::Reduce) {   // Pauli-term reduction only, on the states of the previous run
@@ -730,11 +736,12 @@ int build_grad_tables(vqe_t* h) {
   return VQE_OK;
 }
 
-// What the adjoint kernel cannot serve: a gradient of a stochastic trajectory is of no use to an optimiser, and the
-// streaming path (n >= 14) has no adjoint kernel.  Checked before anything is loaded, so a refused call leaves the
-// handle as it was.
+// What the adjoint kernels cannot serve: a gradient of a stochastic trajectory is of no use to an optimiser, and the
+// streaming path (n >= 14) computes gradients only after vqe_set_stream_grad (a second state-sized buffer per stream).
+// Checked before anything is loaded, so a refused call leaves the handle as it was.
 int grad_refusal(vqe_t* h) {
-  if (!h->lds_path) return fail(h, VQE_EINVAL, "energy gradients are computed for n_qubits <= 13 (LDS-resident path) only");
+  if (!h->lds_path && !h->stream_grad)
+    return fail(h, VQE_EINVAL, "energy gradients are computed for n_qubits <= 13 (LDS-resident path) only");
   if (h->noise.p1 > 0.0 || h->noise.p2 > 0.0)
     return fail(h, VQE_ESTATE, "energy gradients of Pauli-noise trajectories are refused (set p1 = p2 = 0)");
   if (h->noise_mode == 1) return fail(h, VQE_ESTATE, "energy gradients are not available in the exact channel noise mode");
@@ -773,14 +780,25 @@ int launch_grad(vqe_t* h, const BatchArgs& A) {
   return VQE_OK;
 }
 
+// Streaming path (n >= 14, vqe_set_stream_grad): forward sweeps, lambda = H psi, backward sweeps (vqe_stream_grad.h)
+int stream_grad(vqe_t* h, const BatchArgs& A) {
+  HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
+  h->stream_states_undone = true;
+  const int rc = stream_energy_grad(h->sw, A, A.ham.n_terms, h->stream, h->noise.eval_base, h->d_grad.p, h->err, h->gen);
+  if (rc) return rc;
+  HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
+  return VQE_OK;
+}
+
 int run_grad(vqe_t* h) {
   int rc;
   if ((rc = grad_refusal(h))) return rc;
   HIP_TRY(h, hipSetDevice(h->dev));
-  if ((rc = build_grad_tables(h))) return rc;
+  if (h->lds_path && (rc = build_grad_tables(h))) return rc;
   HIP_TRY(h, h->d_grad.reserve((size_t)h->total_params + 1));
   const BatchArgs A = make_args(h);
   h->last_run_dm = false;
+  if (!h->lds_path) return stream_grad(h, A);
   switch (h->n) {
 #define C(N) case N: return launch_grad<N>(h, A);
 #ifdef VQE_ONLY_N
@@ -801,6 +819,8 @@ int lbfgs_check(vqe_t* h, const vqe_lbfgs_opts_t* opts, vqe_lbfgs_opts_t* o) {
   if (opts) *o = *opts;
   int rc;
   if (h->amp_world > 1) return fail(h, VQE_ESTATE, "the device L-BFGS takes no amplitude shard");      // (only n >= 14 can hold one)
+  if (!h->lds_path)      // (with or without vqe_set_stream_grad: the optimiser's kernel holds the state in the LDS)
+    return fail(h, VQE_EINVAL, "the device L-BFGS runs for n_qubits <= 13 (LDS-resident path) only");
   if ((rc = grad_refusal(h))) return rc;
   if (h->shard_world > 1)
     return fail(h, VQE_ESTATE, "term-sharded handles hold partial energies: the line search of the device L-BFGS needs the full energy");
@@ -1174,6 +1194,12 @@ int vqe_set_amplitude_shard(vqe_t* h, int rank, int world) {
   h->amp_rank = rank;
   h->amp_world = world;
   ++h->gen;
+  return VQE_OK;
+}
+
+int vqe_set_stream_grad(vqe_t* h, int enable) {
+  if (!h) return VQE_EINVAL;
+  h->stream_grad = enable != 0;      // (n <= 13: the LDS-resident kernel serves every gradient; nothing to switch)
   return VQE_OK;
 }
 

@@ -47,11 +47,14 @@ struct StreamWork {
   const void* plan_src = nullptr; uint64_t plan_gen = ~0ull; bool plan_ops_ok = false, plan_energy_ok = false;
   void* trec = nullptr;       size_t trec_cap = 0;     // TermRec [batch][n_terms]
   int32_t* grec = nullptr;    size_t grec_cap = 0;     // [batch][n_groups]
+  // adjoint gradient (vqe_stream_grad.h)
+  double2* lam = nullptr;     size_t lam_cap = 0;      // [batch][2^n] lambda = H psi, pulled back op by op
+  double* gpart = nullptr;    size_t gpart_cap = 0;    // [batch][max_ops][blocks of k_sg_back]
   ~StreamWork() {
     (void)hipFree(states); (void)hipFree(ops); (void)hipFree(masks); (void)hipFree(meta);
     (void)hipFree(cs); (void)hipFree(gxp); (void)hipFree(tzp); (void)hipFree(tsg); (void)hipFree(partial);
     (void)hipFree(passes); (void)hipFree(opc); (void)hipFree(chunks); (void)hipFree(egrp); (void)hipFree(eterm); (void)hipFree(ewi); (void)hipFree(csop); (void)hipFree(npass); (void)hipFree(epasses); (void)hipFree(eorder);
-    (void)hipFree(gcx); (void)hipFree(trec); (void)hipFree(grec);
+    (void)hipFree(gcx); (void)hipFree(trec); (void)hipFree(grec); (void)hipFree(lam); (void)hipFree(gpart);
   }
 };
 
@@ -631,3 +634,4 @@ __global__ void __launch_bounds__(64) k_s_cobyla(int B, const int64_t* __restric
 }
 
 }  // namespace vqe
+#include "vqe_stream_grad.h"

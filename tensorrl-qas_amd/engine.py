@@ -143,6 +143,12 @@ class VQEEngine:
         self._chk(self._lib.vqe_hamiltonian_terms(self._h, C.byref(nt), C.byref(ng)))
         return nt.value, ng.value
 
+    def hamiltonian_terms(self):
+        """(n_terms, n_xgroups) of the Hamiltonian as the library holds it."""
+        nt, ng = C.c_int32(), C.c_int32()
+        self._chk(self._lib.vqe_hamiltonian_terms(self._h, C.byref(nt), C.byref(ng)))
+        return nt.value, ng.value
+
     def hamiltonian_layout(self):
         """How the LDS-resident kernels hold the Hamiltonian: table groups, units (mostly-zero groups), class groups."""
         out = (C.c_int32 * 4)()
@@ -181,6 +187,12 @@ class VQEEngine:
     def set_amplitude_shard(self, rank: int, world: int):
         self._chk(self._lib.vqe_set_amplitude_shard(self._h, int(rank), int(world)))
 
+    def set_stream_grad(self, enable: bool = True):
+        """n >= 14: let energy_grad / energy_grad_batch / batch_run_energy_grad run on the streaming path (one more
+        state-sized buffer per resident stream).  Off by default: those calls then raise at n >= 14.  No effect at
+        n <= 13."""
+        self._chk(self._lib.vqe_set_stream_grad(self._h, 1 if enable else 0))
+
     def set_noise(self, p1: float, p2: float, seed: int):
         self._chk(self._lib.vqe_set_noise(self._h, float(p1), float(p2), C.c_uint64(int(seed) & (2 ** 64 - 1))))
 
@@ -217,7 +229,8 @@ class VQEEngine:
         return out
 
     def energy_grad(self, theta):
-        """(E, dE/dtheta) at one parameter vector by the adjoint method on the GPU (n <= 13)."""
+        """(E, dE/dtheta) at one parameter vector by the adjoint method on the GPU (n <= 13; n >= 14 after
+        set_stream_grad())."""
         th = _f64(theta)
         if th.size != self._P:
             raise ValueError("theta has the wrong length")

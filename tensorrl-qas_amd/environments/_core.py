@@ -179,6 +179,8 @@ class CircuitEnvBase:
         if self.optim_method not in (None, "scipy_each_step"):
             raise NotImplementedError("only method = scipy_each_step is live in the reference (SURVEY 3.3 quirk 6)")
         self.optimizer_kind = optimizer_kind(self.optim_alg) if self.optim_method else None
+        if self._own_engine and self.optimizer_kind == "host_gradient" and n >= 14:
+            self.engine.set_stream_grad(True)      # the streaming path computes gradients on request only
         if self.optimizer_kind not in (None, "device_cobyla") and (self.NOISY or self.phys_noise or self.n_shots):
             raise NotImplementedError("noisy and finite-shot environments run COBYLA only (the device optimiser); "
                                       f"optim_alg = {self.optim_alg!r} is refused")

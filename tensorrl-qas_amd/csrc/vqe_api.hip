@@ -2,6 +2,7 @@
 // ham_layout.h), batch upload and kernel dispatch behind the C ABI of include/vqe_hip.h.
 #include "../../include/vqe_hip.h"
 #include "vqe_device.h"
+#include "vqe_devbuf.h"
 #include "vqe_stream.h"
 #include "vqe_dm.h"
 #include "vqe_grad.h"
@@ -11,14 +12,17 @@
 #include "env_step_host.h"
 
 #include <algorithm>
+#include <cassert>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <dlfcn.h>
 #include <map>
+#include <memory>
 #include <new>
 #include <string>
+#include <utility>
 #include <vector>
 
 using namespace vqe;
@@ -26,22 +30,6 @@ using namespace vqe;
 namespace {
 
 std::string g_create_error;
-
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  size_t cap = 0;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  hipError_t reserve(size_t n) {
-    if (n <= cap) return hipSuccess;
-    if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-    size_t want = n + n / 4 + 16;
-    hipError_t e = hipMalloc((void**)&p, want * sizeof(T));
-    if (e == hipSuccess) cap = want;
-    return e;
-  }
-};
-
 }  // namespace
 
 struct vqe_handle {
@@ -143,13 +131,6 @@ int fail(vqe_t* h, int code, const std::string& msg) {
   if (h) h->err = msg; else g_create_error = msg;
   return code;
 }
-#define HIP_TRY(h, expr)                                                               \
-  do {                                                                                 \
-    hipError_t _e = (expr);                                                            \
-    if (_e != hipSuccess)                                                              \
-      return fail(h, _e == hipErrorOutOfMemory ? VQE_ENOMEM : VQE_EHIP,                \
-                  std::string(#expr) + ": " + hipGetErrorString(_e));                  \
-  } while (0)
 
 template <class T>
 int upload(vqe_t* h, DevBuf<T>& b, const T* src, size_t n) {
@@ -157,6 +138,8 @@ int upload(vqe_t* h, DevBuf<T>& b, const T* src, size_t n) {
   if (n) HIP_TRY(h, hipMemcpyAsync(b.p, src, n * sizeof(T), hipMemcpyHostToDevice, h->stream));
   return VQE_OK;
 }
+template <class T>
+int upload(vqe_t* h, DevBuf<T>& b, const std::vector<T>& src) { return upload(h, b, src.data(), src.size()); }
 
 // Build (or rebuild after re-sharding) the device Hamiltonian: plan the layout on the host (ham_layout.h), upload it.
 int build_hamiltonian(vqe_t* h) {
@@ -167,18 +150,17 @@ int build_hamiltonian(vqe_t* h) {
   std::string err;
   if (!plan_hamiltonian(h->ham_host, h->n, h->lds_path, h->shard_rank, h->shard_world, units_on, L, err))
     return fail(h, VQE_EINVAL, err);
-  int rc;
-  if ((rc = upload(h, h->d_gx, L.gx.data(), L.gx.size()))) return rc;
-  if ((rc = upload(h, h->d_tab_r, L.tab_r.data(), L.tab_r.size()))) return rc;
-  if ((rc = upload(h, h->d_tab_i, L.tab_i.data(), L.tab_i.size()))) return rc;
-  if ((rc = upload(h, h->d_tables, L.tables.data(), L.tables.size()))) return rc;
-  if ((rc = upload(h, h->d_term_off, L.term_off.data(), L.term_off.size()))) return rc;
-  if ((rc = upload(h, h->d_term_z, L.term_z.data(), L.term_z.size()))) return rc;
-  if ((rc = upload(h, h->d_term_cr, L.term_cr.data(), L.term_cr.size()))) return rc;
-  if ((rc = upload(h, h->d_term_ci, L.term_ci.data(), L.term_ci.size()))) return rc;
-  if ((rc = upload(h, h->d_urec, L.urec.data(), L.urec.size()))) return rc;
-  if ((rc = upload(h, h->d_uaddr, L.uaddr.data(), L.uaddr.size()))) return rc;
-  if ((rc = upload(h, h->d_utab, L.utab.data(), L.utab.size()))) return rc;
+  VQE_TRY(upload(h, h->d_gx, L.gx));
+  VQE_TRY(upload(h, h->d_tab_r, L.tab_r));
+  VQE_TRY(upload(h, h->d_tab_i, L.tab_i));
+  VQE_TRY(upload(h, h->d_tables, L.tables));
+  VQE_TRY(upload(h, h->d_term_off, L.term_off));
+  VQE_TRY(upload(h, h->d_term_z, L.term_z));
+  VQE_TRY(upload(h, h->d_term_cr, L.term_cr));
+  VQE_TRY(upload(h, h->d_term_ci, L.term_ci));
+  VQE_TRY(upload(h, h->d_urec, L.urec));
+  VQE_TRY(upload(h, h->d_uaddr, L.uaddr));
+  VQE_TRY(upload(h, h->d_utab, L.utab));
   HIP_TRY(h, hipStreamSynchronize(h->stream));  // the layout goes out of scope
   HamDev& d = h->ham;
   d.n_groups = (int)L.gx.size();
@@ -216,12 +198,30 @@ int check_gates(vqe_t* h, int64_t n_gates, const int32_t* kind, const int32_t* q
 // of the full circuits; Reduce: the streaming path's Pauli-term reduction alone, on the states of the previous run).
 enum class Run { Energy, Minimize, State, EnvStep, Reduce };
 
+// the optimiser kernels, told to follow CircuitEnv.step
+void set_env_step(const vqe_t* h, BatchArgs& A) {
+  A.env_step = 1;
+  A.new_gate = h->has_new_gate ? h->d_new_gate.p : nullptr;
+}
+
+// The sizes of the LDS-resident kernels (kernel experiments, tools/build_only_n.sh: one size, seconds to build), and
+// h->n as a compile-time N among them: f(std::integral_constant<int, N>), or the caller's refusal for any other n.
+// (A left fold: the compiler then instantiates the kernels, and lays them out in the code object, in ascending N.)
+#ifdef VQE_ONLY_N
+using LdsSizes = std::integer_sequence<int, VQE_ONLY_N>;
+#else
+using LdsSizes = std::integer_sequence<int, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13>;
+#endif
+template <class F, int... Ns>
+int dispatch_n(vqe_t* h, const char* refusal, F f, std::integer_sequence<int, Ns...>) {
+  int rc = 0;
+  const bool found = (... || (h->n == Ns && ((rc = f(std::integral_constant<int, Ns>{})), true)));
+  return found ? rc : fail(h, VQE_EINVAL, refusal);
+}
+
 template <int N>
 int launch_lds(vqe_t* h, Run mode, BatchArgs A) {
-  if (mode == Run::EnvStep) {      // the minimize kernel, told to follow CircuitEnv.step
-    A.env_step = 1;
-    A.new_gate = h->has_new_gate ? h->d_new_gate.p : nullptr;
-  }
+  if (mode == Run::EnvStep) set_env_step(h, A);
   const bool minimize = mode == Run::Minimize || mode == Run::EnvStep;
   size_t lds = lds_bytes(N, A.max_ops, A.max_params, A.ham.n_groups, A.max_pair);
   // measurement knob: VQE_LDS_PAD=bytes of unused LDS per workgroup lowers the workgroups per CU
@@ -262,16 +262,8 @@ int launch_lds(vqe_t* h, Run mode, BatchArgs A) {
 }
 
 int dispatch_lds(vqe_t* h, Run mode, const BatchArgs& A) {
-  switch (h->n) {
-#define C(N) case N: return launch_lds<N>(h, mode, A);
-#ifdef VQE_ONLY_N      // kernel experiments (tools/build_only_n.sh): one size, seconds to build
-    C(VQE_ONLY_N)
-#else
-    C(1) C(2) C(3) C(4) C(5) C(6) C(7) C(8) C(9) C(10) C(11) C(12) C(13)
-#endif
-#undef C
-  }
-  return fail(h, VQE_EINVAL, "n_qubits outside the LDS-resident range");
+  return dispatch_n(h, "n_qubits outside the LDS-resident range",
+                    [&](auto n) -> int { return launch_lds<decltype(n)::value>(h, mode, A); }, LdsSizes{});
 }
 
 BatchArgs make_args(vqe_t* h) {
@@ -312,14 +304,20 @@ int load_batch(vqe_t* h, int batch, const std::vector<GateRec>& gates,
                const std::vector<int64_t>& gbeg, const std::vector<int32_t>& gcnt,
                const std::vector<int64_t>& pbeg, const std::vector<int32_t>& pcnt,
                const double* theta0, int64_t total_params) {
-  int rc;
   std::vector<int64_t> sbeg(batch);
   int64_t stot = 0;
   int max_ops = 1, max_par = 1, max_pair = 0;
   std::vector<double> cost(batch);
   for (int b = 0; b < batch; ++b) {
     sbeg[b] = stot;
-    stot += (int64_t)cby::scratch_doubles(pcnt[b], 16);   // the larger of the device contexts' paddings
+    // the larger of the device contexts' paddings, + 1: k_s_cobyla (one thread per stream, HostCtx) keeps the value told
+    // last right behind its optimiser's arrays (words(), which bind() lays out as scratch_doubles_ld counts them)
+    // The slot costs nothing: scratch_doubles(P, 16) = 2 nv^2 + 12 nv + 19 with nv a multiple of 16, so it is 3 mod 16
+    // and the rounding below ends on the same multiple of 16 with and without the + 1.
+    const size_t sdoubles = cby::scratch_doubles(pcnt[b], 16) + 1;
+    assert(cby::scratch_doubles_ld(pcnt[b], 1, cby::lead_dim(pcnt[b])) + 1 <= sdoubles);
+    assert(((sdoubles + 15) & ~(size_t)15) == ((sdoubles - 1 + 15) & ~(size_t)15));
+    stot += (int64_t)sdoubles;
     stot = (stot + 15) & ~(int64_t)15;  // 128-byte alignment: rows of the optimiser's global arrays are whole sectors / lines
     max_par = std::max(max_par, (int)pcnt[b]);
     int ops = 0, pair = 0;
@@ -342,14 +340,14 @@ int load_batch(vqe_t* h, int batch, const std::vector<GateRec>& gates,
   for (int b = 0; b < batch; ++b) order[b] = b;
   if (!getenv("VQE_NO_LPT"))   // experiments: launch in caller order
     std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return cost[x] > cost[y]; });
-  if ((rc = upload(h, h->d_gates, gates.data(), gates.size()))) return rc;
-  if ((rc = upload(h, h->d_gate_begin, gbeg.data(), gbeg.size()))) return rc;
-  if ((rc = upload(h, h->d_gate_count, gcnt.data(), gcnt.size()))) return rc;
-  if ((rc = upload(h, h->d_par_begin, pbeg.data(), pbeg.size()))) return rc;
-  if ((rc = upload(h, h->d_par_count, pcnt.data(), pcnt.size()))) return rc;
-  if ((rc = upload(h, h->d_order, order.data(), order.size()))) return rc;
-  if ((rc = upload(h, h->d_scratch_begin, sbeg.data(), sbeg.size()))) return rc;
-  if ((rc = upload(h, h->d_theta, theta0, (size_t)total_params))) return rc;
+  VQE_TRY(upload(h, h->d_gates, gates));
+  VQE_TRY(upload(h, h->d_gate_begin, gbeg));
+  VQE_TRY(upload(h, h->d_gate_count, gcnt));
+  VQE_TRY(upload(h, h->d_par_begin, pbeg));
+  VQE_TRY(upload(h, h->d_par_count, pcnt));
+  VQE_TRY(upload(h, h->d_order, order));
+  VQE_TRY(upload(h, h->d_scratch_begin, sbeg));
+  VQE_TRY(upload(h, h->d_theta, theta0, (size_t)total_params));
   HIP_TRY(h, h->d_scratch.reserve((size_t)stot + 2));
   HIP_TRY(h, h->d_x.reserve((size_t)total_params + 1));
   HIP_TRY(h, h->d_xraw.reserve((size_t)total_params + 1));
@@ -389,6 +387,20 @@ int ready(vqe_t* h) {
   return VQE_OK;
 }
 
+// one streaming-path evaluation of the batch that A describes, on the handle's work buffers and stream
+int evaluate(vqe_t* h, const BatchArgs& A, uint64_t eval_id, StreamWant what) {
+  return stream_evaluate(h->sw, A, h->stream, eval_id, what, h->err, h->gen);
+}
+
+// an owned host COBYLA (vqe_cobyla_create; null when the allocation failed)
+struct CobylaDestroy { void operator()(vqe_cobyla_t* c) const { vqe_cobyla_destroy(c); } };
+using CobylaPtr = std::unique_ptr<vqe_cobyla_t, CobylaDestroy>;
+CobylaPtr make_cobyla(int n, const double* x0, const BatchArgs& A) {
+  vqe_cobyla_t* c = nullptr;
+  (void)vqe_cobyla_create(n, x0, A.rhobeg, A.rhoend, A.maxfun, &c);
+  return CobylaPtr(c);
+}
+
 // COBYLA of all resident streams in lock-step (one batched evaluation per iteration): the streaming path's form of
 // scipy.optimize.minimize(..., method='COBYLA') (environment_qulacs_TN_notin_agent.py:478).  The optimiser state of
 // every stream lives on the device (k_s_cobyla: the host build's arithmetic, one thread per stream); the host only
@@ -400,29 +412,25 @@ constexpr int kStreamPoll = 8;
 int stream_cobyla_host(vqe_t* h, BatchArgs& A, const std::vector<int64_t>& pbeg, const std::vector<int32_t>& pcnt,
                        std::vector<double>& x, std::vector<double>& f, std::vector<int32_t>& nfev) {
   const int B = h->batch;
-  std::vector<vqe_cobyla_t*> cob(B, nullptr);
-  struct Guard { std::vector<vqe_cobyla_t*>& v; ~Guard() { for (auto* c : v) vqe_cobyla_destroy(c); } } guard{cob};
+  std::vector<CobylaPtr> cob(B);
   for (int b = 0; b < B; ++b)
-    if (vqe_cobyla_create(pcnt[b], x.data() + pbeg[b], A.rhobeg, A.rhoend, A.maxfun, &cob[b]))
-      return fail(h, VQE_ENOMEM, "host COBYLA allocation failed");
+    if (!(cob[b] = make_cobyla(pcnt[b], x.data() + pbeg[b], A))) return fail(h, VQE_ENOMEM, "host COBYLA allocation failed");
   HIP_TRY(h, h->d_x.reserve(x.size() + 1));
   uint64_t it = 0;
-  int rc = 0;
   for (;;) {
     int active = 0;
-    for (int b = 0; b < B; ++b) active += vqe_cobyla_ask(cob[b], x.data() + pbeg[b]) == 1;
+    for (int b = 0; b < B; ++b) active += vqe_cobyla_ask(cob[b].get(), x.data() + pbeg[b]) == 1;
     if (!active) break;
     if (!x.empty())
       HIP_TRY(h, hipMemcpyAsync(h->d_x.p, x.data(), x.size() * 8, hipMemcpyHostToDevice, h->stream));
     A.theta = h->d_x.p;  // trial points live in the output buffer; x0 stays untouched
-    rc = stream_evaluate(h->sw, A, A.ham.n_terms, h->stream, h->noise.eval_base + (++it), true, h->err, true, h->gen);
-    if (rc) return rc;
+    VQE_TRY(evaluate(h, A, h->noise.eval_base + (++it), StreamWant::Both));
     HIP_TRY(h, hipMemcpyAsync(f.data(), h->d_f.p, (size_t)B * 8, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     for (int b = 0; b < B; ++b)
-      if (vqe_cobyla_ask(cob[b], nullptr) == 1) vqe_cobyla_tell(cob[b], f[b]);
+      if (vqe_cobyla_ask(cob[b].get(), nullptr) == 1) vqe_cobyla_tell(cob[b].get(), f[b]);
   }
-  for (int b = 0; b < B; ++b) vqe_cobyla_result(cob[b], x.data() + pbeg[b], &f[b], &nfev[b], nullptr);
+  for (int b = 0; b < B; ++b) vqe_cobyla_result(cob[b].get(), x.data() + pbeg[b], &f[b], &nfev[b], nullptr);
   return VQE_OK;
 }
 
@@ -444,21 +452,22 @@ int stream_cobyla(vqe_t* h, BatchArgs& A, const std::vector<int64_t>& pbeg, cons
   // (trial points of streams that finish early stay where they are: the evaluations go on in lock-step over all streams)
   if (PT) HIP_TRY(h, hipMemcpyAsync(h->d_x.p, x.data(), PT * 8, hipMemcpyHostToDevice, h->stream));
   int32_t* n_active = h->d_cob_active.p + B;
-  const dim3 grid((unsigned)((B + 63) / 64)), block(64);
-  HIP_TRY(h, hipMemsetAsync(n_active, 0, 4, h->stream));
-  hipLaunchKernelGGL(k_s_cobyla<true>, grid, block, 0, h->stream, B, d_pbeg, d_pcnt, (const int64_t*)h->d_scratch_begin.p,
-                     h->d_scratch.p, (const double*)h->d_cob_x0.p, h->d_x.p, (const double*)h->d_f.p, A.rhobeg, A.rhoend,
-                     A.maxfun, h->d_cob_active.p, n_active, h->d_cob_xres.p, h->d_cob_f.p, h->d_cob_nfev.p);
+  auto cobyla_step = [&](bool first) {      // start() from x0, or tell() of the evaluation just made
+    HIP_TRY(h, hipMemsetAsync(n_active, 0, 4, h->stream));
+    const auto kernel = first ? k_s_cobyla<true> : k_s_cobyla<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, h->stream, B, d_pbeg, d_pcnt,
+                       (const int64_t*)h->d_scratch_begin.p, h->d_scratch.p, (const double*)h->d_cob_x0.p, h->d_x.p,
+                       (const double*)h->d_f.p, A.rhobeg, A.rhoend, A.maxfun, h->d_cob_active.p, n_active, h->d_cob_xres.p,
+                       h->d_cob_f.p, h->d_cob_nfev.p);
+    return (int)VQE_OK;
+  };
+  VQE_TRY(cobyla_step(true));
   A.theta = h->d_x.p;
   uint64_t it = 0;
   int32_t running = 1;
   while (running > 0) {
-    int rc = stream_evaluate(h->sw, A, A.ham.n_terms, h->stream, h->noise.eval_base + (++it), true, h->err, true, h->gen);
-    if (rc) return rc;
-    HIP_TRY(h, hipMemsetAsync(n_active, 0, 4, h->stream));
-    hipLaunchKernelGGL(k_s_cobyla<false>, grid, block, 0, h->stream, B, d_pbeg, d_pcnt, (const int64_t*)h->d_scratch_begin.p,
-                       h->d_scratch.p, (const double*)h->d_cob_x0.p, h->d_x.p, (const double*)h->d_f.p, A.rhobeg, A.rhoend,
-                       A.maxfun, h->d_cob_active.p, n_active, h->d_cob_xres.p, h->d_cob_f.p, h->d_cob_nfev.p);
+    VQE_TRY(evaluate(h, A, h->noise.eval_base + (++it), StreamWant::Both));
+    VQE_TRY(cobyla_step(false));
     if (it % kStreamPoll == 0 || it >= (uint64_t)A.maxfun) {
       HIP_TRY(h, hipMemcpyAsync(&running, n_active, 4, hipMemcpyDeviceToHost, h->stream));
       HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -482,24 +491,23 @@ int stream_run(vqe_t* h, Run mode, BatchArgs& A) {
   int rc = 0;
   if (mode != Run::Reduce) h->stream_states_undone = false;
   if (mode == Run::Energy) {
-    rc = stream_evaluate(h->sw, A, A.ham.n_terms, h->stream, h->noise.eval_base, true, h->err, true, h->gen);
+    rc = evaluate(h, A, h->noise.eval_base, StreamWant::Both);
   } else if (mode == Run::Reduce) {   // Pauli-term reduction only, on the states of the previous run
-    if (h->sw.states_cap < ((size_t)h->batch << h->n)) return fail(h, VQE_ESTATE, "no states: run the energy first");
-    rc = stream_evaluate(h->sw, A, A.ham.n_terms, h->stream, h->noise.eval_base, true, h->err, false, h->gen);
+    if (h->sw.states.cap < ((size_t)h->batch << h->n)) return fail(h, VQE_ESTATE, "no states: run the energy first");
+    rc = evaluate(h, A, h->noise.eval_base, StreamWant::Energy);
   } else if (mode == Run::State) {
-    rc = stream_evaluate(h->sw, A, A.ham.n_terms, h->stream, h->noise.eval_base, false, h->err, true, h->gen);
+    rc = evaluate(h, A, h->noise.eval_base, StreamWant::Circuit);
     if (!rc) {
       const size_t dim = (size_t)1 << h->n;
       hipLaunchKernelGGL(k_s_state_out, dim3((unsigned)(dim / kThreads)), dim3(kThreads), 0, h->stream, A,
-                         h->sw.states, h->sw.masks, h->sw.meta);
+                         h->sw.states.p, h->sw.masks.p, h->sw.meta.p);
       HIP_TRY(h, hipGetLastError());
     }
   } else if (mode == Run::Minimize) {
     const int B = h->batch;
     std::vector<double> x(h->h_theta), f(B, 0.0);
     std::vector<int32_t> nfev(B);
-    rc = stream_cobyla(h, A, h->h_par_begin, h->h_par_count, x, f, nfev, h->d_par_begin.p, h->d_par_count.p);
-    if (rc) return rc;
+    VQE_TRY(stream_cobyla(h, A, h->h_par_begin, h->h_par_count, x, f, nfev, h->d_par_begin.p, h->d_par_count.p));
     if (h->total_params)
       HIP_TRY(h, hipMemcpyAsync(h->d_x.p, x.data(), x.size() * 8, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipMemcpyAsync(h->d_f.p, f.data(), (size_t)B * 8, hipMemcpyHostToDevice, h->stream));
@@ -524,20 +532,18 @@ int stream_run(vqe_t* h, Run mode, BatchArgs& A) {
       gcnt2[b] = (int32_t)((int64_t)g2.size() - gbeg2[b]);
       pcnt2[b] = (int32_t)((int64_t)x0.size() - pbeg2[b]);
     }
-    int rc2;
     ++h->gen;      // d_gates2 changes content: plans made for it are stale
-    if ((rc2 = upload(h, h->d_gates2, g2.data(), g2.size()))) return rc2;
-    if ((rc2 = upload(h, h->d_gate_begin2, gbeg2.data(), gbeg2.size()))) return rc2;
-    if ((rc2 = upload(h, h->d_gate_count2, gcnt2.data(), gcnt2.size()))) return rc2;
-    if ((rc2 = upload(h, h->d_par_begin2, pbeg2.data(), pbeg2.size()))) return rc2;
-    if ((rc2 = upload(h, h->d_par_count2, pcnt2.data(), pcnt2.size()))) return rc2;
+    VQE_TRY(upload(h, h->d_gates2, g2));
+    VQE_TRY(upload(h, h->d_gate_begin2, gbeg2));
+    VQE_TRY(upload(h, h->d_gate_count2, gcnt2));
+    VQE_TRY(upload(h, h->d_par_begin2, pbeg2));
+    VQE_TRY(upload(h, h->d_par_count2, pcnt2));
     BatchArgs A2 = A;
     A2.gates = h->d_gates2.p; A2.gate_begin = h->d_gate_begin2.p; A2.gate_count = h->d_gate_count2.p;
     A2.par_begin = h->d_par_begin2.p; A2.par_count = h->d_par_count2.p;
     std::vector<double> f(B, 0.0);
     std::vector<int32_t> nfev(B);
-    rc = stream_cobyla(h, A2, pbeg2, pcnt2, x0, f, nfev, h->d_par_begin2.p, h->d_par_count2.p);
-    if (rc) return rc;
+    VQE_TRY(stream_cobyla(h, A2, pbeg2, pcnt2, x0, f, nfev, h->d_par_begin2.p, h->d_par_count2.p));
     std::vector<double> xraw(h->h_theta), xr32(h->h_theta);
     for (int b = 0; b < B; ++b) {
       const int64_t p0 = h->h_par_begin[b];
@@ -550,7 +556,7 @@ int stream_run(vqe_t* h, Run mode, BatchArgs& A) {
     HIP_TRY(h, hipMemcpyAsync(h->d_nfev.p, nfev.data(), (size_t)B * 4, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));      // host vectors stay alive until the copies are done
     A.theta = h->d_x.p;
-    rc = stream_evaluate(h->sw, A, A.ham.n_terms, h->stream, h->noise.eval_base + (uint64_t)A.maxfun + 1, true, h->err, true, h->gen);
+    rc = evaluate(h, A, h->noise.eval_base + (uint64_t)A.maxfun + 1, StreamWant::Both);
   }
   if (rc) return rc;
   HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
@@ -571,12 +577,11 @@ int dm_prepare_ham(vqe_t* h) {
     for (int k : H.group_terms[g]) { tz.push_back((uint32_t)H.hz[k]); cr.push_back(H.hcr[k]); ci.push_back(H.hci[k]); }
     toff.push_back((int32_t)tz.size());
   }
-  int rc;
-  if ((rc = upload(h, h->dm_gx, gx.data(), gx.size()))) return rc;
-  if ((rc = upload(h, h->dm_tz, tz.data(), tz.size()))) return rc;
-  if ((rc = upload(h, h->dm_toff, toff.data(), toff.size()))) return rc;
-  if ((rc = upload(h, h->dm_cr, cr.data(), cr.size()))) return rc;
-  if ((rc = upload(h, h->dm_ci, ci.data(), ci.size()))) return rc;
+  VQE_TRY(upload(h, h->dm_gx, gx));
+  VQE_TRY(upload(h, h->dm_tz, tz));
+  VQE_TRY(upload(h, h->dm_toff, toff));
+  VQE_TRY(upload(h, h->dm_cr, cr));
+  VQE_TRY(upload(h, h->dm_ci, ci));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   h->dm_groups = (int)gx.size();
   h->dm_ham_gen = h->gen;
@@ -598,8 +603,7 @@ int dm_energy_one(vqe_t* h, const GateRec* g, int G, const double* theta, double
   const int eb = (int)((((size_t)1 << n) + 255) / 256);
   HIP_TRY(h, h->dm_rho.reserve(total));
   HIP_TRY(h, h->dm_partial.reserve((size_t)eb + 1));
-  int rc;
-  if ((rc = upload(h, h->dm_S, S.data(), S.size()))) return rc;
+  VQE_TRY(upload(h, h->dm_S, S));
   const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, (size_t)h->cu_count * 16);
   if (!h->dm_ev0) { HIP_TRY(h, hipEventCreate(&h->dm_ev0)); HIP_TRY(h, hipEventCreate(&h->dm_ev1)); }
   HIP_TRY(h, hipEventRecord(h->dm_ev0, h->stream));
@@ -640,8 +644,7 @@ int dm_run(vqe_t* h, Run mode, const BatchArgs& A) {
       if (gate_is_rot2(h->h_gates[i].kind))
         return fail(h, VQE_EINVAL, "the exact channel mode does not take RXX / RYY / RZZ gates (use Pauli-trajectory noise, vqe_set_noise_mode 0)");
   if (h->amp_world > 1) return fail(h, VQE_ESTATE, "the exact channel mode has no amplitude sharding");
-  int rc = dm_prepare_ham(h);
-  if (rc) return rc;
+  VQE_TRY(dm_prepare_ham(h));
   HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
   h->dm_gpu_ms = 0.f;
   h->last_run_dm = true;
@@ -654,7 +657,7 @@ int dm_run(vqe_t* h, Run mode, const BatchArgs& A) {
     const int G = h->h_gate_count[b], P = h->h_par_count[b];
     double* xb = x.data() + h->h_par_begin[b];
     if (mode == Run::Energy) {
-      if ((rc = dm_energy_one(h, g, G, xb, &f[b]))) return rc;
+      VQE_TRY(dm_energy_one(h, g, G, xb, &f[b]));
       continue;
     }
     // the circuit COBYLA sees: the pre-action circuit (pre_action, vqe_geo.h) when this is an env-step
@@ -663,22 +666,21 @@ int dm_run(vqe_t* h, Run mode, const BatchArgs& A) {
     const int hole = pre_action_circuit(g, G, (env_step && h->has_new_gate) ? h->h_new_gate[b] : -1, xb, P, g2, xo).hole;
     double fo = 0.0;
     if (xo.empty()) {      // scipy returns after one evaluation
-      if ((rc = dm_energy_one(h, g2.data(), (int)g2.size(), xo.data(), &fo))) return rc;
+      VQE_TRY(dm_energy_one(h, g2.data(), (int)g2.size(), xo.data(), &fo));
     } else {
-      vqe_cobyla_t* cob = nullptr;
-      if (vqe_cobyla_create((int)xo.size(), xo.data(), A.rhobeg, A.rhoend, A.maxfun, &cob)) return fail(h, VQE_ENOMEM, "host COBYLA allocation failed");
+      const CobylaPtr cob = make_cobyla((int)xo.size(), xo.data(), A);
+      if (!cob) return fail(h, VQE_ENOMEM, "host COBYLA allocation failed");
       std::vector<double> xt(xo.size());
-      while (vqe_cobyla_ask(cob, xt.data()) == 1) {
+      while (vqe_cobyla_ask(cob.get(), xt.data()) == 1) {
         double e;
-        if ((rc = dm_energy_one(h, g2.data(), (int)g2.size(), xt.data(), &e))) { vqe_cobyla_destroy(cob); return rc; }
-        vqe_cobyla_tell(cob, e);
+        VQE_TRY(dm_energy_one(h, g2.data(), (int)g2.size(), xt.data(), &e));
+        vqe_cobyla_tell(cob.get(), e);
       }
-      vqe_cobyla_result(cob, xo.data(), &fo, &nfev[b], nullptr);
-      vqe_cobyla_destroy(cob);
+      vqe_cobyla_result(cob.get(), xo.data(), &fo, &nfev[b], nullptr);
     }
     merge_optimum(h->h_theta.data() + h->h_par_begin[b], P, hole, xo.data(), env_step, xb, xraw.data() + h->h_par_begin[b]);
     f[b] = fo;
-    if (env_step && (rc = dm_energy_one(h, g, G, xb, &f[b]))) return rc;
+    if (env_step) VQE_TRY(dm_energy_one(h, g, G, xb, &f[b]));
   }
   if (mode != Run::Energy && h->total_params) {
     HIP_TRY(h, hipMemcpyAsync(h->d_x.p, x.data(), x.size() * 8, hipMemcpyHostToDevice, h->stream));
@@ -688,6 +690,16 @@ int dm_run(vqe_t* h, Run mode, const BatchArgs& A) {
   HIP_TRY(h, hipMemcpyAsync(h->d_nfev.p, nfev.data(), (size_t)B * 4, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return VQE_OK;
+}
+
+// The evaluation trace of an optimiser run (vqe_batch_set_trace): [batch][maxfun][1 + max_params] doubles, zeroed
+int arm_trace(vqe_t* h, BatchArgs& A, int maxfun) {
+  const size_t stride = (size_t)1 + (size_t)h->max_params, words = (size_t)h->batch * (size_t)maxfun * stride;
+  HIP_TRY(h, h->d_trace.reserve(words));
+  HIP_TRY(h, hipMemsetAsync(h->d_trace.p, 0, words * sizeof(double), h->stream));
+  A.trace = h->d_trace.p;
+  h->trace_maxfun = maxfun; h->trace_stride = (int)stride; h->trace_batch = h->batch;
   return VQE_OK;
 }
 
@@ -701,18 +713,11 @@ int run(vqe_t* h, Run mode, double rhobeg, double rhoend, int maxfun) {
                                "vqe_cobyla_ask/tell and sum the partial energies of all ranks");
   if (mode == Run::Reduce && h->lds_path)
     return fail(h, VQE_ESTATE, "the reduction-only launch exists on the streaming path (n >= 14) only");
-  if (h->trace_on && optimise && h->lds_path) {
-    const size_t stride = (size_t)1 + (size_t)h->max_params, words = (size_t)h->batch * (size_t)maxfun * stride;
-    HIP_TRY(h, h->d_trace.reserve(words));
-    HIP_TRY(h, hipMemsetAsync(h->d_trace.p, 0, words * sizeof(double), h->stream));
-    A.trace = h->d_trace.p;
-    h->trace_maxfun = maxfun; h->trace_stride = (int)stride; h->trace_batch = h->batch;
-  }
+  if (h->trace_on && optimise && h->lds_path) VQE_TRY(arm_trace(h, A, maxfun));
   h->last_run_dm = false;
   h->lb_batch = 0;             // fout / nfev are about to be another run's: the L-BFGS info of an earlier one is stale
   if (h->noise_mode == 1 && (mode == Run::Energy || optimise)) return dm_run(h, mode, A);
-  const int rc = h->lds_path ? dispatch_lds(h, mode, A) : stream_run(h, mode, A);
-  if (rc) return rc;
+  VQE_TRY(h->lds_path ? dispatch_lds(h, mode, A) : stream_run(h, mode, A));
   // every evaluation of a stochastic run consumes fresh trajectory numbers
   if (mode != Run::Reduce) h->noise.eval_base += (optimise ? (uint64_t)maxfun + 1 : 1);
   return VQE_OK;
@@ -725,11 +730,10 @@ int build_grad_tables(vqe_t* h) {
   if (h->grad_ham_ver == h->ham_ver) return VQE_OK;
   GradTables T;
   plan_grad_tables(h->ham_host, h->n, h->lds_path, h->shard_rank, h->shard_world, T);
-  int rc;
-  if ((rc = upload(h, h->g_gx, T.gx.data(), T.gx.size()))) return rc;
-  if ((rc = upload(h, h->g_off, T.off.data(), T.off.size()))) return rc;
-  if ((rc = upload(h, h->g_cplx, T.cplx.data(), T.cplx.size()))) return rc;
-  if ((rc = upload(h, h->g_tab, T.tab.data(), T.tab.size()))) return rc;
+  VQE_TRY(upload(h, h->g_gx, T.gx));
+  VQE_TRY(upload(h, h->g_off, T.off));
+  VQE_TRY(upload(h, h->g_cplx, T.cplx));
+  VQE_TRY(upload(h, h->g_tab, T.tab));
   HIP_TRY(h, hipStreamSynchronize(h->stream));  // host vectors go out of scope
   h->gham = GradHam{(int)T.gx.size(), h->g_gx.p, h->g_off.p, h->g_cplx.p, h->g_tab.p};
   h->grad_ham_ver = h->ham_ver;
@@ -750,65 +754,65 @@ int grad_refusal(vqe_t* h) {
   return VQE_OK;
 }
 
-template <int N>
-int launch_grad(vqe_t* h, const BatchArgs& A) {
+// The launch of the two adjoint kernels (the gradient, the device L-BFGS): both come as <N, LAM_GLOBAL> pairs that take
+// (A, gham, x, lambda scratch) and size their LDS by a formula of grad_lds_bytes' form.  lambda lives in the LDS unless
+// N >= 13 or psi + lambda + ops exceed it; in global memory it is one slice per workgroup of a persistent grid.
+// prepare(grid, x): what the caller has to size by the chosen grid (a hipError_t).
+template <int N, class X, class Prepare>
+int launch_adjoint(vqe_t* h, const BatchArgs& A, size_t (*lds_bytes)(int, bool, int, int, int),
+                   void (*k_global)(BatchArgs, GradHam, X, double2*), void (*k_lds)(BatchArgs, GradHam, X, double2*),
+                   const char* too_large, X x, Prepare prepare) {
   constexpr int NW = Geo<N>::NW;
   bool lam_global = N >= 13;
-  size_t lds = grad_lds_bytes(N, lam_global, A.max_ops, A.max_params, NW);
+  size_t lds = lds_bytes(N, lam_global, A.max_ops, A.max_params, NW);
   if (!lam_global && lds > (size_t)h->lds_per_cu) {      // psi + lambda + ops do not fit: lambda moves to global memory
     lam_global = true;
-    lds = grad_lds_bytes(N, true, A.max_ops, A.max_params, NW);
+    lds = lds_bytes(N, true, A.max_ops, A.max_params, NW);
   }
-  if (lds > (size_t)h->lds_per_cu) return fail(h, VQE_EINVAL, "circuit too large for the adjoint gradient kernel (gates + parameters)");
+  if (lds > (size_t)h->lds_per_cu) return fail(h, VQE_EINVAL, too_large);
   const int wg_per_cu = std::max(1, (int)(h->lds_per_cu / lds));
-  const void* fn = lam_global ? (const void*)k_lds_energy_grad<N, true> : (const void*)k_lds_energy_grad<N, false>;
-  HIP_TRY(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  const auto kernel = lam_global ? k_global : k_lds;
+  HIP_TRY(h, hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   h->last_wg_per_cu = std::min(8, wg_per_cu);
   int grid = A.batch;
   if (lam_global) {
     grid = std::min(A.batch, h->cu_count * wg_per_cu);
     HIP_TRY(h, h->g_lam.reserve((size_t)grid << N));
   }
+  HIP_TRY(h, prepare(grid, x));
   HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
-  if (lam_global)
-    hipLaunchKernelGGL((k_lds_energy_grad<N, true>), dim3(grid), dim3(Geo<N>::NT), lds, h->stream, A, h->gham, h->d_grad.p, h->g_lam.p);
-  else
-    hipLaunchKernelGGL((k_lds_energy_grad<N, false>), dim3(grid), dim3(Geo<N>::NT), lds, h->stream, A, h->gham, h->d_grad.p,
-                       (double2*)nullptr);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(Geo<N>::NT), lds, h->stream, A, h->gham, x, lam_global ? h->g_lam.p : (double2*)nullptr);
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
   return VQE_OK;
+}
+
+template <int N>
+int launch_grad(vqe_t* h, const BatchArgs& A) {
+  return launch_adjoint<N>(h, A, grad_lds_bytes, k_lds_energy_grad<N, true>, k_lds_energy_grad<N, false>,
+                           "circuit too large for the adjoint gradient kernel (gates + parameters)", h->d_grad.p,
+                           [](int, double*) { return hipSuccess; });
 }
 
 // Streaming path (n >= 14, vqe_set_stream_grad): forward sweeps, lambda = H psi, backward sweeps (vqe_stream_grad.h)
 int stream_grad(vqe_t* h, const BatchArgs& A) {
   HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
   h->stream_states_undone = true;
-  const int rc = stream_energy_grad(h->sw, A, A.ham.n_terms, h->stream, h->noise.eval_base, h->d_grad.p, h->err, h->gen);
-  if (rc) return rc;
+  VQE_TRY(stream_energy_grad(h->sw, A, h->stream, h->noise.eval_base, h->d_grad.p, h->err, h->gen));
   HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
   return VQE_OK;
 }
 
 int run_grad(vqe_t* h) {
-  int rc;
-  if ((rc = grad_refusal(h))) return rc;
+  VQE_TRY(grad_refusal(h));
   HIP_TRY(h, hipSetDevice(h->dev));
-  if (h->lds_path && (rc = build_grad_tables(h))) return rc;
+  if (h->lds_path) VQE_TRY(build_grad_tables(h));
   HIP_TRY(h, h->d_grad.reserve((size_t)h->total_params + 1));
   const BatchArgs A = make_args(h);
   h->last_run_dm = false;
   if (!h->lds_path) return stream_grad(h, A);
-  switch (h->n) {
-#define C(N) case N: return launch_grad<N>(h, A);
-#ifdef VQE_ONLY_N
-    C(VQE_ONLY_N)
-#else
-    C(1) C(2) C(3) C(4) C(5) C(6) C(7) C(8) C(9) C(10) C(11) C(12) C(13)
-#endif
-#undef C
-  }
-  return fail(h, VQE_EINVAL, "energy gradients are computed for n_qubits <= 13 (LDS-resident path) only");
+  return dispatch_n(h, "energy gradients are computed for n_qubits <= 13 (LDS-resident path) only",
+                    [&](auto n) -> int { return launch_grad<decltype(n)::value>(h, A); }, LdsSizes{});
 }
 
 // ---- device L-BFGS (vqe_lbfgs.h) -------------------------------------------------------------
@@ -817,11 +821,10 @@ int run_grad(vqe_t* h) {
 int lbfgs_check(vqe_t* h, const vqe_lbfgs_opts_t* opts, vqe_lbfgs_opts_t* o) {
   (void)vqe_lbfgs_default_opts(o);
   if (opts) *o = *opts;
-  int rc;
   if (h->amp_world > 1) return fail(h, VQE_ESTATE, "the device L-BFGS takes no amplitude shard");      // (only n >= 14 can hold one)
   if (!h->lds_path)      // (with or without vqe_set_stream_grad: the optimiser's kernel holds the state in the LDS)
     return fail(h, VQE_EINVAL, "the device L-BFGS runs for n_qubits <= 13 (LDS-resident path) only");
-  if ((rc = grad_refusal(h))) return rc;
+  VQE_TRY(grad_refusal(h));
   if (h->shard_world > 1)
     return fail(h, VQE_ESTATE, "term-sharded handles hold partial energies: the line search of the device L-BFGS needs the full energy");
   if (o->history < 1 || o->history > kLbfgsMaxHistory) return fail(h, VQE_EINVAL, "L-BFGS history must be in [1, 16]");
@@ -832,71 +835,31 @@ int lbfgs_check(vqe_t* h, const vqe_lbfgs_opts_t* opts, vqe_lbfgs_opts_t* o) {
 }
 
 template <int N>
-int launch_lbfgs(vqe_t* h, const BatchArgs& A, LbfgsArgs O) {
-  constexpr int NW = Geo<N>::NW;
-  bool lam_global = N >= 13;
-  size_t lds = lbfgs_lds_bytes(N, lam_global, A.max_ops, A.max_params, NW);
-  if (!lam_global && lds > (size_t)h->lds_per_cu) {      // psi + lambda + ops do not fit: lambda moves to global memory
-    lam_global = true;
-    lds = lbfgs_lds_bytes(N, true, A.max_ops, A.max_params, NW);
-  }
-  if (lds > (size_t)h->lds_per_cu) return fail(h, VQE_EINVAL, "circuit too large for the device L-BFGS kernel (gates + parameters)");
-  const int wg_per_cu = std::max(1, (int)(h->lds_per_cu / lds));
-  const void* fn = lam_global ? (const void*)k_lds_minimize_lbfgs<N, true> : (const void*)k_lds_minimize_lbfgs<N, false>;
-  HIP_TRY(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  h->last_wg_per_cu = std::min(8, wg_per_cu);
-  int grid = A.batch;
-  if (lam_global) {
-    grid = std::min(A.batch, h->cu_count * wg_per_cu);
-    HIP_TRY(h, h->g_lam.reserve((size_t)grid << N));
-  }
-  HIP_TRY(h, h->lb_work.reserve((size_t)grid * lbfgs_work_doubles(A.max_params, O.m)));
-  O.work = h->lb_work.p;
-  HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
-  if (lam_global)
-    hipLaunchKernelGGL((k_lds_minimize_lbfgs<N, true>), dim3(grid), dim3(Geo<N>::NT), lds, h->stream, A, h->gham, O, h->g_lam.p);
-  else
-    hipLaunchKernelGGL((k_lds_minimize_lbfgs<N, false>), dim3(grid), dim3(Geo<N>::NT), lds, h->stream, A, h->gham, O, (double2*)nullptr);
-  HIP_TRY(h, hipGetLastError());
-  HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
-  return VQE_OK;
+int launch_lbfgs(vqe_t* h, const BatchArgs& A, const LbfgsArgs& O) {
+  return launch_adjoint<N>(h, A, lbfgs_lds_bytes, k_lds_minimize_lbfgs<N, true>, k_lds_minimize_lbfgs<N, false>,
+                           "circuit too large for the device L-BFGS kernel (gates + parameters)", O,
+                           [&](int grid, LbfgsArgs& o) {      // the optimiser's vectors: one slice per workgroup
+                             const hipError_t e = h->lb_work.reserve((size_t)grid * lbfgs_work_doubles(A.max_params, o.m));
+                             o.work = h->lb_work.p;
+                             return e;
+                           });
 }
 
 // o: options that passed lbfgs_check
 int run_lbfgs(vqe_t* h, bool env_step, const vqe_lbfgs_opts_t& o) {
-  int rc;
   HIP_TRY(h, hipSetDevice(h->dev));
-  if ((rc = build_grad_tables(h))) return rc;
+  VQE_TRY(build_grad_tables(h));
   BatchArgs A = make_args(h);
   A.maxfun = o.maxfun;
-  if (env_step) {
-    A.env_step = 1;
-    A.new_gate = h->has_new_gate ? h->d_new_gate.p : nullptr;
-  }
-  if (h->trace_on) {
-    const size_t stride = (size_t)1 + (size_t)h->max_params, words = (size_t)h->batch * (size_t)o.maxfun * stride;
-    HIP_TRY(h, h->d_trace.reserve(words));
-    HIP_TRY(h, hipMemsetAsync(h->d_trace.p, 0, words * sizeof(double), h->stream));
-    A.trace = h->d_trace.p;
-    h->trace_maxfun = o.maxfun; h->trace_stride = (int)stride; h->trace_batch = h->batch;
-  }
+  if (env_step) set_env_step(h, A);
+  if (h->trace_on) VQE_TRY(arm_trace(h, A, o.maxfun));
   HIP_TRY(h, h->lb_nit.reserve(h->batch));
   HIP_TRY(h, h->lb_status.reserve(h->batch));
-  LbfgsArgs O{o.history, o.maxiter, o.maxfun, o.max_ls, o.gtol, o.ftol, o.c1, nullptr, h->lb_nit.p, h->lb_status.p};
+  const LbfgsArgs O{o.history, o.maxiter, o.maxfun, o.max_ls, o.gtol, o.ftol, o.c1, nullptr, h->lb_nit.p, h->lb_status.p};
   h->last_run_dm = false;
   h->lb_batch = 0;
-  rc = VQE_EINVAL;
-  switch (h->n) {
-#define C(N) case N: rc = launch_lbfgs<N>(h, A, O); break;
-#ifdef VQE_ONLY_N
-    C(VQE_ONLY_N)
-#else
-    C(1) C(2) C(3) C(4) C(5) C(6) C(7) C(8) C(9) C(10) C(11) C(12) C(13)
-#endif
-#undef C
-    default: return fail(h, VQE_EINVAL, "the device L-BFGS serves n_qubits <= 13 (LDS-resident path) only");
-  }
-  if (rc) return rc;
+  VQE_TRY(dispatch_n(h, "the device L-BFGS serves n_qubits <= 13 (LDS-resident path) only",
+                     [&](auto n) -> int { return launch_lbfgs<decltype(n)::value>(h, A, O); }, LdsSizes{}));
   h->lb_batch = h->batch;
   return VQE_OK;
 }

@@ -16,57 +16,44 @@
 #include <string>
 #include <vector>
 #include "vqe_device.h"
+#include "vqe_devbuf.h"
 
 namespace vqe {
 
+struct TilePass; struct OpCoord; struct ChunkRec; struct EGroupRec; struct ETermRec; struct ETilePass; struct TermRec;   // vqe_tile.h
+
 struct StreamWork {
-  double2* states = nullptr;  size_t states_cap = 0;   // [batch][2^n]
-  Op* ops = nullptr;          size_t ops_cap = 0;      // [batch][max_ops]
-  uint32_t* masks = nullptr;  size_t masks_cap = 0;    // [batch][64]: xm[32], zm[32]
-  int32_t* meta = nullptr;    size_t meta_cap = 0;     // [batch][8]
-  double2* cs = nullptr;      size_t cs_cap = 0;       // [batch][max_params]
-  uint32_t* gxp = nullptr;    size_t gxp_cap = 0;      // [batch][n_groups] physical X masks
-  uint32_t* tzp = nullptr;    size_t tzp_cap = 0;      // [batch][n_terms] physical Z masks
-  double* tsg = nullptr;      size_t tsg_cap = 0;      // [batch][n_terms] (-1)^{z.c}
-  double* partial = nullptr;  size_t partial_cap = 0;  // [batch][blocks]
+  DevBufExact<double2> states;      // [batch][2^n]
+  DevBufExact<Op> ops;              // [batch][max_ops]
+  DevBufExact<uint32_t> masks;      // [batch][64]: xm[32], zm[32]
+  DevBufExact<int32_t> meta;        // [batch][8]
+  DevBufExact<double2> cs;          // [batch][max_params]
+  DevBufExact<uint32_t> gxp;        // [batch][n_groups] physical X masks
+  DevBufExact<uint32_t> tzp;        // [batch][n_terms] physical Z masks
+  DevBufExact<double> tsg;          // [batch][n_terms] (-1)^{z.c}
+  DevBufExact<double> partial;      // [batch][blocks]: the caller that launches a reduction sizes it for that launch
   bool plan_fused = false;    // the energy plan's pass 0 is the tile of the last circuit pass (vqe_tile.h: fused pass)
   // LDS-tiled kernels (vqe_tile.h)
-  void* passes = nullptr;     size_t passes_cap = 0;   // TilePass [batch][max_pass]
-  void* opc = nullptr;        size_t opc_cap = 0;      // OpCoord [batch][max_ops]
-  void* chunks = nullptr;     size_t chunks_cap = 0;   // ChunkRec [batch][max_ops]
-  void* egrp = nullptr;       size_t egrp_cap = 0;     // EGroupRec [batch][n_groups]
-  void* eterm = nullptr;      size_t eterm_cap = 0;    // ETermRec [batch][n_terms]
-  double* ewi = nullptr;      size_t ewi_cap = 0;      // imaginary weights [batch][n_terms]
-  double2* csop = nullptr;    size_t csop_cap = 0;     // (cos, sin) in op order [batch][max_ops]
-  int32_t* npass = nullptr;   size_t npass_cap = 0;    // [batch] op passes, [batch] energy passes
-  void* epasses = nullptr;    size_t epasses_cap = 0;  // TilePass [batch][kMaxEnergyPasses]
-  int32_t* eorder = nullptr;  size_t eorder_cap = 0;   // [batch][n_groups] group ids pass by pass, then [batch][n_groups] pass of a group
-  uint32_t* gcx = nullptr;    size_t gcx_cap = 0;      // [batch][n_groups]
+  DevBufExact<TilePass> passes;     // [batch][max_pass]
+  DevBufExact<OpCoord> opc;         // [batch][max_ops]
+  DevBufExact<ChunkRec> chunks;     // [batch][max_ops]
+  DevBufExact<EGroupRec> egrp;      // [batch][n_groups]
+  DevBufExact<ETermRec> eterm;      // [batch][n_terms]
+  DevBufExact<double> ewi;          // imaginary weights [batch][n_terms]
+  DevBufExact<double2> csop;        // (cos, sin) in op order [batch][max_ops]
+  DevBufExact<int32_t> npass;       // [batch] op passes, [batch] energy passes
+  DevBufExact<ETilePass> epasses;   // [batch][kMaxEnergyPasses]
+  DevBufExact<int32_t> eorder;      // [batch][n_groups] group ids pass by pass, then [batch][n_groups] pass of a group
+  DevBufExact<uint32_t> gcx;        // [batch][n_groups]
   // plans depend on the gate lists, the Hamiltonian shard and (through the drawn Paulis) on the noise, not on theta:
   // a noiseless re-evaluation of the same resident batch (COBYLA iterations, repeated runs) keeps them
   const void* plan_src = nullptr; uint64_t plan_gen = ~0ull; bool plan_ops_ok = false, plan_energy_ok = false;
-  void* trec = nullptr;       size_t trec_cap = 0;     // TermRec [batch][n_terms]
-  int32_t* grec = nullptr;    size_t grec_cap = 0;     // [batch][n_groups]
+  DevBufExact<TermRec> trec;        // [batch][n_terms]
+  DevBufExact<int32_t> grec;        // [batch][n_groups]
   // adjoint gradient (vqe_stream_grad.h)
-  double2* lam = nullptr;     size_t lam_cap = 0;      // [batch][2^n] lambda = H psi, pulled back op by op
-  double* gpart = nullptr;    size_t gpart_cap = 0;    // [batch][max_ops][blocks of k_sg_back]
-  ~StreamWork() {
-    (void)hipFree(states); (void)hipFree(ops); (void)hipFree(masks); (void)hipFree(meta);
-    (void)hipFree(cs); (void)hipFree(gxp); (void)hipFree(tzp); (void)hipFree(tsg); (void)hipFree(partial);
-    (void)hipFree(passes); (void)hipFree(opc); (void)hipFree(chunks); (void)hipFree(egrp); (void)hipFree(eterm); (void)hipFree(ewi); (void)hipFree(csop); (void)hipFree(npass); (void)hipFree(epasses); (void)hipFree(eorder);
-    (void)hipFree(gcx); (void)hipFree(trec); (void)hipFree(grec); (void)hipFree(lam); (void)hipFree(gpart);
-  }
+  DevBufExact<double2> lam;         // [batch][2^n] lambda = H psi, pulled back op by op
+  DevBufExact<double> gpart;        // [batch][max_ops][blocks of k_sg_back]
 };
-
-template <class T>
-inline hipError_t sw_reserve(T*& p, size_t& cap, size_t n) {
-  if (n <= cap) return hipSuccess;
-  if (p) (void)hipFree(p);
-  p = nullptr; cap = 0;
-  hipError_t e = hipMalloc((void**)&p, n * sizeof(T));
-  if (e == hipSuccess) cap = n;
-  return e;
-}
 
 // one thread per stream: gate list -> ops (+ zm rows, needed to move the Pauli masks)
 __global__ void k_s_compile(BatchArgs A, Op* ops, uint32_t* masks, int32_t* meta, uint64_t eval_id) {
@@ -411,15 +398,6 @@ __global__ void __launch_bounds__(kThreads) k_s_state_out(BatchArgs A, const dou
 #include "vqe_tile.h"
 namespace vqe {
 
-#define SW_TRY(expr)                                                            \
-  do {                                                                          \
-    hipError_t _e = (expr);                                                     \
-    if (_e != hipSuccess) {                                                     \
-      err = std::string(#expr) + ": " + hipGetErrorString(_e);                  \
-      return _e == hipErrorOutOfMemory ? -12 : -5;                              \
-    }                                                                           \
-  } while (0)
-
 // circuit + (partial) energy of every resident stream, results in A.fout (device).
 // Default: the LDS-tiled kernels of vqe_tile.h; VQE_STREAM_TILED=0 (or a Hamiltonian shard with too many
 // X-mask groups for the pass table) selects the one-sweep-per-four-ops kernels above.
@@ -429,85 +407,77 @@ inline bool stream_tiled(int n_groups, int n_terms) {
          n_terms <= 4096;
 }
 
-inline int stream_evaluate(StreamWork& sw, const BatchArgs& A, int n_terms, hipStream_t st,
-                           uint64_t eval_id, bool want_energy, std::string& err, bool want_circuit = true,
-                           uint64_t generation = 0) {
+// what one call launches: the circuit alone (states), the Pauli-term reduction alone (on the states of the previous
+// call), or both
+enum class StreamWant { Circuit, Energy, Both };
+
+inline int stream_evaluate(StreamWork& sw, const BatchArgs& A, hipStream_t st, uint64_t eval_id, StreamWant want,
+                           std::string& err, uint64_t generation) {
+  const bool want_circuit = want != StreamWant::Energy, want_energy = want != StreamWant::Circuit;
+  const int n_terms = A.ham.n_terms;
   const size_t dim = (size_t)1 << A.n;
   const bool noisy = A.noise.p1 > 0.0 || A.noise.p2 > 0.0;
   if (sw.plan_src != (const void*)A.gates || sw.plan_gen != generation || noisy) sw.plan_ops_ok = sw.plan_energy_ok = false;
   sw.plan_src = (const void*)A.gates;
   sw.plan_gen = generation;
   const int B = A.batch;
-  SW_TRY(sw_reserve(sw.states, sw.states_cap, (size_t)B * dim));
-  SW_TRY(sw_reserve(sw.ops, sw.ops_cap, (size_t)B * A.max_ops));
-  SW_TRY(sw_reserve(sw.masks, sw.masks_cap, (size_t)B * 64));
-  SW_TRY(sw_reserve(sw.meta, sw.meta_cap, (size_t)B * 8));
-  SW_TRY(sw_reserve(sw.cs, sw.cs_cap, (size_t)B * A.max_params));
+  HIP_TRY(err, sw.states.reserve((size_t)B * dim));
+  HIP_TRY(err, sw.ops.reserve((size_t)B * A.max_ops));
+  HIP_TRY(err, sw.masks.reserve((size_t)B * 64));
+  HIP_TRY(err, sw.meta.reserve((size_t)B * 8));
+  HIP_TRY(err, sw.cs.reserve((size_t)B * A.max_params));
   const int nt = n_terms > 0 ? n_terms : 1, ng = A.ham.n_groups > 0 ? A.ham.n_groups : 1;
-  SW_TRY(sw_reserve(sw.gxp, sw.gxp_cap, (size_t)B * ng));
-  SW_TRY(sw_reserve(sw.tzp, sw.tzp_cap, (size_t)B * nt));
-  SW_TRY(sw_reserve(sw.tsg, sw.tsg_cap, (size_t)B * nt));
+  HIP_TRY(err, sw.gxp.reserve((size_t)B * ng));
+  HIP_TRY(err, sw.tzp.reserve((size_t)B * nt));
+  HIP_TRY(err, sw.tsg.reserve((size_t)B * nt));
   const int world = A.amp_world > 0 ? A.amp_world : 1;
   const bool tiled = stream_tiled(A.ham.n_groups, n_terms);
   if (tiled) {
     const int tiles = (int)(dim >> kTileBits);
     const int max_pass = A.max_ops / kTileFree + 2;          // a pass is closed by its (kTileFree + 1)-th independent mask
     const int e_pass = std::min(kMaxEnergyPasses, (A.ham.n_groups + kETileFree - 1) / kETileFree + 1);
-    {
-      TilePass* tp = (TilePass*)sw.passes; size_t cap = sw.passes_cap;
-      SW_TRY(sw_reserve(tp, cap, (size_t)B * max_pass)); sw.passes = tp; sw.passes_cap = cap;
-      OpCoord* oc = (OpCoord*)sw.opc; cap = sw.opc_cap;
-      SW_TRY(sw_reserve(oc, cap, (size_t)B * A.max_ops)); sw.opc = oc; sw.opc_cap = cap;
-      ChunkRec* cr = (ChunkRec*)sw.chunks; cap = sw.chunks_cap;
-      SW_TRY(sw_reserve(cr, cap, (size_t)B * A.max_ops)); sw.chunks = cr; sw.chunks_cap = cap;
-      SW_TRY(sw_reserve(sw.csop, sw.csop_cap, (size_t)B * A.max_ops));
-      ETilePass* ep = (ETilePass*)sw.epasses; cap = sw.epasses_cap;
-      SW_TRY(sw_reserve(ep, cap, (size_t)B * kMaxEnergyPasses)); sw.epasses = ep; sw.epasses_cap = cap;
-    }
-    SW_TRY(sw_reserve(sw.npass, sw.npass_cap, (size_t)2 * B));
-    SW_TRY(sw_reserve(sw.eorder, sw.eorder_cap, (size_t)2 * B * ng));
-    SW_TRY(sw_reserve(sw.gcx, sw.gcx_cap, (size_t)B * ng));
-    {
-      TermRec* tr = (TermRec*)sw.trec; size_t cap = sw.trec_cap;
-      SW_TRY(sw_reserve(tr, cap, (size_t)B * nt)); sw.trec = tr; sw.trec_cap = cap;
-    }
-    SW_TRY(sw_reserve(sw.grec, sw.grec_cap, (size_t)B * ng));
-    {
-      EGroupRec* eg = (EGroupRec*)sw.egrp; size_t cap = sw.egrp_cap;
-      SW_TRY(sw_reserve(eg, cap, (size_t)B * ng)); sw.egrp = eg; sw.egrp_cap = cap;
-      ETermRec* et = (ETermRec*)sw.eterm; cap = sw.eterm_cap;
-      SW_TRY(sw_reserve(et, cap, (size_t)B * nt)); sw.eterm = et; sw.eterm_cap = cap;
-      SW_TRY(sw_reserve(sw.ewi, sw.ewi_cap, (size_t)B * nt));
-    }
+    HIP_TRY(err, sw.passes.reserve((size_t)B * max_pass));
+    HIP_TRY(err, sw.opc.reserve((size_t)B * A.max_ops));
+    HIP_TRY(err, sw.chunks.reserve((size_t)B * A.max_ops));
+    HIP_TRY(err, sw.csop.reserve((size_t)B * A.max_ops));
+    HIP_TRY(err, sw.epasses.reserve((size_t)B * kMaxEnergyPasses));
+    HIP_TRY(err, sw.npass.reserve((size_t)2 * B));
+    HIP_TRY(err, sw.eorder.reserve((size_t)2 * B * ng));
+    HIP_TRY(err, sw.gcx.reserve((size_t)B * ng));
+    HIP_TRY(err, sw.trec.reserve((size_t)B * nt));
+    HIP_TRY(err, sw.grec.reserve((size_t)B * ng));
+    HIP_TRY(err, sw.egrp.reserve((size_t)B * ng));
+    HIP_TRY(err, sw.eterm.reserve((size_t)B * nt));
+    HIP_TRY(err, sw.ewi.reserve((size_t)B * nt));
     const int tiles_rank = (int)(dim >> kETileBits) / world;     // tiles of the Pauli-term reduction in this rank's slice
     const int e_blocks = (tiles_rank + kTilesPerBlock - 1) / kTilesPerBlock;     // k_t_energy: one partial per workgroup
     const int o_blocks = (tiles + kOpsTilesPerBlock - 1) / kOpsTilesPerBlock;
     // partial sums of a stream: [e_pass][e_blocks] of k_t_energy, then [o_blocks] of the fused pass (the pair groups that
     // close inside the tile of the last circuit pass are evaluated there, before the final state leaves the LDS)
     const int p_stride = e_pass * e_blocks + o_blocks;
-    SW_TRY(sw_reserve(sw.partial, sw.partial_cap, (size_t)B * p_stride));
+    HIP_TRY(err, sw.partial.reserve((size_t)B * p_stride));
     static const bool fuse_on = [] { const char* e = getenv("VQE_STREAM_FUSE"); return !(e && e[0] == '0'); }();   // A/B knob
     auto plan_energy = [&](bool with_last_pass) {
-      hipLaunchKernelGGL(k_t_plan_energy, dim3((B + 63) / 64), dim3(64), 0, st, A, n_terms, sw.gxp, sw.tzp, sw.tsg,
-                         (ETilePass*)sw.epasses, sw.npass + B, sw.eorder, sw.gcx, sw.grec, (TermRec*)sw.trec,
-                         sw.eorder + (size_t)B * ng, (EGroupRec*)sw.egrp, (ETermRec*)sw.eterm, sw.ewi,
-                         with_last_pass ? (const TilePass*)sw.passes : (const TilePass*)nullptr, (const int32_t*)sw.npass, max_pass);
+      hipLaunchKernelGGL(k_t_plan_energy, dim3((B + 63) / 64), dim3(64), 0, st, A, n_terms, sw.gxp.p, sw.tzp.p, sw.tsg.p,
+                         sw.epasses.p, sw.npass.p + B, sw.eorder.p, sw.gcx.p, sw.grec.p, sw.trec.p,
+                         sw.eorder.p + (size_t)B * ng, sw.egrp.p, sw.eterm.p, sw.ewi.p,
+                         with_last_pass ? (const TilePass*)sw.passes.p : (const TilePass*)nullptr, (const int32_t*)sw.npass.p, max_pass);
       sw.plan_fused = with_last_pass;
     };
     const int m_terms = std::max(nt, ng);
     bool fused = false;
     bool energy_ready = sw.plan_energy_ok;      // (a noisy run plans anew in every call: the flags stay false)
     if (want_circuit) {
-      hipLaunchKernelGGL(k_s_sincos, dim3((A.max_params + 63) / 64, B), dim3(64), 0, st, A, sw.cs);
+      hipLaunchKernelGGL(k_s_sincos, dim3((A.max_params + 63) / 64, B), dim3(64), 0, st, A, sw.cs.p);
       if (!sw.plan_ops_ok) {
-        hipLaunchKernelGGL(k_s_compile, dim3((B + 63) / 64), dim3(64), 0, st, A, sw.ops, sw.masks, sw.meta, eval_id);
+        hipLaunchKernelGGL(k_s_compile, dim3((B + 63) / 64), dim3(64), 0, st, A, sw.ops.p, sw.masks.p, sw.meta.p, eval_id);
         const bool with_groups = want_energy && fuse_on;      // (the Pauli masks follow the layout the circuit leaves: sw.masks)
         if (with_groups)
-          hipLaunchKernelGGL(k_s_terms, dim3((m_terms + 63) / 64, B), dim3(64), 0, st, A, sw.masks, sw.meta, n_terms, sw.gxp,
-                             sw.tzp, sw.tsg);
-        hipLaunchKernelGGL(k_t_plan_ops, dim3((B + 63) / 64), dim3(64), 0, st, A, sw.ops, sw.meta, (TilePass*)sw.passes,
-                           (OpCoord*)sw.opc, (ChunkRec*)sw.chunks, sw.npass, max_pass,
-                           with_groups ? (const uint32_t*)sw.gxp : (const uint32_t*)nullptr);
+          hipLaunchKernelGGL(k_s_terms, dim3((m_terms + 63) / 64, B), dim3(64), 0, st, A, sw.masks.p, sw.meta.p, n_terms, sw.gxp.p,
+                             sw.tzp.p, sw.tsg.p);
+        hipLaunchKernelGGL(k_t_plan_ops, dim3((B + 63) / 64), dim3(64), 0, st, A, sw.ops.p, sw.meta.p, sw.passes.p,
+                           sw.opc.p, sw.chunks.p, sw.npass.p, max_pass,
+                           with_groups ? (const uint32_t*)sw.gxp.p : (const uint32_t*)nullptr);
         sw.plan_ops_ok = !noisy;
         sw.plan_energy_ok = false;
         energy_ready = false;
@@ -518,66 +488,66 @@ inline int stream_evaluate(StreamWork& sw, const BatchArgs& A, int n_terms, hipS
         }
       }
       if (want_energy && (!energy_ready || sw.plan_fused != fuse_on)) {      // (an op plan cached from a circuit-only call, or an
-        hipLaunchKernelGGL(k_s_terms, dim3((m_terms + 63) / 64, B), dim3(64), 0, st, A, sw.masks, sw.meta, n_terms, sw.gxp,   // energy-only plan)
-                           sw.tzp, sw.tsg);
+        hipLaunchKernelGGL(k_s_terms, dim3((m_terms + 63) / 64, B), dim3(64), 0, st, A, sw.masks.p, sw.meta.p, n_terms, sw.gxp.p,   // energy-only plan)
+                           sw.tzp.p, sw.tsg.p);
         plan_energy(fuse_on);
         sw.plan_energy_ok = !noisy && sw.plan_ops_ok;
         energy_ready = true;
       }
       fused = want_energy && sw.plan_fused;
-      hipLaunchKernelGGL(k_t_cs_ops, dim3((A.max_ops + 63) / 64, B), dim3(64), 0, st, A, sw.ops, sw.meta, sw.cs, sw.csop);
-      FusedEnergy F{fused ? sw.partial : nullptr, (const ETilePass*)sw.epasses, (const EGroupRec*)sw.egrp, (const ETermRec*)sw.eterm,
-                    (const double*)sw.ewi, n_terms, tiles_rank, p_stride, e_pass * e_blocks};
+      hipLaunchKernelGGL(k_t_cs_ops, dim3((A.max_ops + 63) / 64, B), dim3(64), 0, st, A, sw.ops.p, sw.meta.p, sw.cs.p, sw.csop.p);
+      FusedEnergy F{fused ? sw.partial.p : nullptr, (const ETilePass*)sw.epasses.p, (const EGroupRec*)sw.egrp.p, (const ETermRec*)sw.eterm.p,
+                    (const double*)sw.ewi.p, n_terms, tiles_rank, p_stride, e_pass * e_blocks};
       for (int p = 0; p < max_pass; ++p) {
         if (p + 1 < max_pass || !fused)      // (a stream's last pass is pass max_pass - 1 at the latest)
-          hipLaunchKernelGGL(k_t_ops<false>, dim3((unsigned)o_blocks, B), dim3(kThreads), 0, st, A, sw.states,
-                             (const ChunkRec*)sw.chunks, (const double2*)sw.csop, (const TilePass*)sw.passes, sw.npass, p,
+          hipLaunchKernelGGL(k_t_ops<false>, dim3((unsigned)o_blocks, B), dim3(kThreads), 0, st, A, sw.states.p,
+                             (const ChunkRec*)sw.chunks.p, (const double2*)sw.csop.p, (const TilePass*)sw.passes.p, sw.npass.p, p,
                              max_pass, tiles, F);
         if (fused)
-          hipLaunchKernelGGL(k_t_ops<true>, dim3((unsigned)o_blocks, B), dim3(kThreads), 0, st, A, sw.states,
-                             (const ChunkRec*)sw.chunks, (const double2*)sw.csop, (const TilePass*)sw.passes, sw.npass, p,
+          hipLaunchKernelGGL(k_t_ops<true>, dim3((unsigned)o_blocks, B), dim3(kThreads), 0, st, A, sw.states.p,
+                             (const ChunkRec*)sw.chunks.p, (const double2*)sw.csop.p, (const TilePass*)sw.passes.p, sw.npass.p, p,
                              max_pass, tiles, F);
       }
     }
     if (want_energy) {
       if (!energy_ready || (!fused && sw.plan_fused)) {      // (energy of the resident states without their circuits: a plan whose
-        hipLaunchKernelGGL(k_s_terms, dim3((m_terms + 63) / 64, B), dim3(64), 0, st, A, sw.masks, sw.meta, n_terms, sw.gxp,   // pass 0 is a tile of k_t_energy's own)
-                           sw.tzp, sw.tsg);
+        hipLaunchKernelGGL(k_s_terms, dim3((m_terms + 63) / 64, B), dim3(64), 0, st, A, sw.masks.p, sw.meta.p, n_terms, sw.gxp.p,   // pass 0 is a tile of k_t_energy's own)
+                           sw.tzp.p, sw.tsg.p);
         plan_energy(false);
         sw.plan_energy_ok = !noisy && sw.plan_ops_ok;
       }
-      if (!fused) SW_TRY(hipMemsetAsync(sw.partial, 0, (size_t)B * p_stride * sizeof(double), st));     // (the fused pass's slots)
-      hipLaunchKernelGGL(k_t_energy, dim3((unsigned)e_blocks, B, e_pass), dim3(kThreads), 0, st, A, sw.states, n_terms,
-                         (const ETilePass*)sw.epasses, sw.npass + B, (const EGroupRec*)sw.egrp, (const ETermRec*)sw.eterm,
-                         sw.ewi, sw.partial, tiles_rank, p_stride, fused ? 1 : 0);
-      hipLaunchKernelGGL(k_s_reduce, dim3(B), dim3(kThreads), 0, st, sw.partial, p_stride, A.fout, A.noise,
+      if (!fused) HIP_TRY(err, hipMemsetAsync(sw.partial.p, 0, (size_t)B * p_stride * sizeof(double), st));     // (the fused pass's slots)
+      hipLaunchKernelGGL(k_t_energy, dim3((unsigned)e_blocks, B, e_pass), dim3(kThreads), 0, st, A, sw.states.p, n_terms,
+                         (const ETilePass*)sw.epasses.p, sw.npass.p + B, (const EGroupRec*)sw.egrp.p, (const ETermRec*)sw.eterm.p,
+                         sw.ewi.p, sw.partial.p, tiles_rank, p_stride, fused ? 1 : 0);
+      hipLaunchKernelGGL(k_s_reduce, dim3(B), dim3(kThreads), 0, st, sw.partial.p, p_stride, A.fout, A.noise,
                          eval_id, A.amp_rank == 0 ? 1 : 0);
     }
-    SW_TRY(hipGetLastError());
+    HIP_TRY(err, hipGetLastError());
     return 0;
   }
   const int eblk = (int)(dim / (kThreads * kEnergyApt)) / world;
-  SW_TRY(sw_reserve(sw.partial, sw.partial_cap, (size_t)B * eblk));
+  HIP_TRY(err, sw.partial.reserve((size_t)B * eblk));
 
   if (want_circuit) {
-    hipLaunchKernelGGL(k_s_compile, dim3((B + 63) / 64), dim3(64), 0, st, A, sw.ops, sw.masks, sw.meta, eval_id);
-    hipLaunchKernelGGL(k_s_sincos, dim3((A.max_params + 63) / 64, B), dim3(64), 0, st, A, sw.cs);
-    hipLaunchKernelGGL(k_s_init, dim3((unsigned)(dim / kThreads), B), dim3(kThreads), 0, st, A, sw.states);
+    hipLaunchKernelGGL(k_s_compile, dim3((B + 63) / 64), dim3(64), 0, st, A, sw.ops.p, sw.masks.p, sw.meta.p, eval_id);
+    hipLaunchKernelGGL(k_s_sincos, dim3((A.max_params + 63) / 64, B), dim3(64), 0, st, A, sw.cs.p);
+    hipLaunchKernelGGL(k_s_init, dim3((unsigned)(dim / kThreads), B), dim3(kThreads), 0, st, A, sw.states.p);
     for (int o = 0; o < A.max_ops; o += kOpsPerSweep)
       hipLaunchKernelGGL(k_s_opk<kOpsPerSweep>, dim3((unsigned)((dim >> kOpsPerSweep) / kThreads), B), dim3(kThreads), 0, st,
-                         A, sw.states, sw.ops, sw.meta, sw.cs, o);
+                         A, sw.states.p, sw.ops.p, sw.meta.p, sw.cs.p, o);
   }
   if (want_energy) {
     const int m = std::max(nt, ng);
-    hipLaunchKernelGGL(k_s_terms, dim3((m + 63) / 64, B), dim3(64), 0, st, A, sw.masks, sw.meta, n_terms,
-                       sw.gxp, sw.tzp, sw.tsg);
-    hipLaunchKernelGGL(k_s_energy, dim3(eblk, B), dim3(kThreads), 0, st, A, sw.states, n_terms, sw.gxp,
-                       sw.tzp, sw.tsg, sw.partial);
+    hipLaunchKernelGGL(k_s_terms, dim3((m + 63) / 64, B), dim3(64), 0, st, A, sw.masks.p, sw.meta.p, n_terms,
+                       sw.gxp.p, sw.tzp.p, sw.tsg.p);
+    hipLaunchKernelGGL(k_s_energy, dim3(eblk, B), dim3(kThreads), 0, st, A, sw.states.p, n_terms, sw.gxp.p,
+                       sw.tzp.p, sw.tsg.p, sw.partial.p);
     // shot noise belongs to the full energy: only an unsharded handle (or slice 0) adds it
-    hipLaunchKernelGGL(k_s_reduce, dim3(B), dim3(kThreads), 0, st, sw.partial, eblk, A.fout, A.noise, eval_id,
+    hipLaunchKernelGGL(k_s_reduce, dim3(B), dim3(kThreads), 0, st, sw.partial.p, eblk, A.fout, A.noise, eval_id,
                        A.amp_rank == 0 ? 1 : 0);
   }
-  SW_TRY(hipGetLastError());
+  HIP_TRY(err, hipGetLastError());
   return 0;
 }
 

@@ -297,30 +297,30 @@ __global__ void __launch_bounds__(kThreads) k_sg_reduce(BatchArgs A, const Op* o
 }
 
 // E (A.fout) and dE/dtheta (grad, the layout of the batch's theta) of every resident stream.
-inline int stream_energy_grad(StreamWork& sw, const BatchArgs& A, int n_terms, hipStream_t st, uint64_t eval_id,
-                              double* grad, std::string& err, uint64_t generation) {
+inline int stream_energy_grad(StreamWork& sw, const BatchArgs& A, hipStream_t st, uint64_t eval_id, double* grad,
+                              std::string& err, uint64_t generation) {
   constexpr int K = kGradOpsPerSweep;
-  const int rc = stream_evaluate(sw, A, n_terms, st, eval_id, /*want_energy=*/false, err, /*want_circuit=*/true, generation);
-  if (rc) return rc;
+  VQE_TRY(stream_evaluate(sw, A, st, eval_id, StreamWant::Circuit, err, generation));
+  const int n_terms = A.ham.n_terms;
   const size_t dim = (size_t)1 << A.n;
   const int B = A.batch;
   const int lblk = (int)((dim + (size_t)kThreads * kLambdaApt - 1) / ((size_t)kThreads * kLambdaApt));
   const int gblk = (int)(((dim >> K) + kThreads - 1) / kThreads);
-  SW_TRY(sw_reserve(sw.lam, sw.lam_cap, (size_t)B * dim));
-  SW_TRY(sw_reserve(sw.gpart, sw.gpart_cap, (size_t)B * A.max_ops * gblk));
-  SW_TRY(sw_reserve(sw.partial, sw.partial_cap, (size_t)B * lblk));
+  HIP_TRY(err, sw.lam.reserve((size_t)B * dim));
+  HIP_TRY(err, sw.gpart.reserve((size_t)B * A.max_ops * gblk));
+  HIP_TRY(err, sw.partial.reserve((size_t)B * lblk));
   const int nt = n_terms > 0 ? n_terms : 1, ng = A.ham.n_groups > 0 ? A.ham.n_groups : 1;
-  hipLaunchKernelGGL(k_s_terms, dim3((std::max(nt, ng) + 63) / 64, B), dim3(64), 0, st, A, sw.masks, sw.meta, n_terms,
-                     sw.gxp, sw.tzp, sw.tsg);
-  hipLaunchKernelGGL(k_sg_lambda, dim3(lblk, B), dim3(kThreads), 0, st, A, (const double2*)sw.states, n_terms,
-                     (const uint32_t*)sw.gxp, (const uint32_t*)sw.tzp, (const double*)sw.tsg, sw.lam, sw.partial);
-  hipLaunchKernelGGL(k_s_reduce, dim3(B), dim3(kThreads), 0, st, sw.partial, lblk, A.fout, A.noise, eval_id, 0);
+  hipLaunchKernelGGL(k_s_terms, dim3((std::max(nt, ng) + 63) / 64, B), dim3(64), 0, st, A, sw.masks.p, sw.meta.p, n_terms,
+                     sw.gxp.p, sw.tzp.p, sw.tsg.p);
+  hipLaunchKernelGGL(k_sg_lambda, dim3(lblk, B), dim3(kThreads), 0, st, A, (const double2*)sw.states.p, n_terms,
+                     (const uint32_t*)sw.gxp.p, (const uint32_t*)sw.tzp.p, (const double*)sw.tsg.p, sw.lam.p, sw.partial.p);
+  hipLaunchKernelGGL(k_s_reduce, dim3(B), dim3(kThreads), 0, st, sw.partial.p, lblk, A.fout, A.noise, eval_id, 0);
   for (int o = ((A.max_ops - 1) / K) * K; o >= 0; o -= K)      // the op groups of the forward sweeps, last first
-    hipLaunchKernelGGL(k_sg_back<K>, dim3(gblk, B), dim3(kThreads), 0, st, A, sw.states, sw.lam, (const Op*)sw.ops,
-                       (const int32_t*)sw.meta, (const double2*)sw.cs, sw.gpart, o);
-  hipLaunchKernelGGL(k_sg_reduce, dim3(A.max_params, B), dim3(kThreads), 0, st, A, (const Op*)sw.ops,
-                     (const int32_t*)sw.meta, (const double*)sw.gpart, gblk, grad);
-  SW_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_sg_back<K>, dim3(gblk, B), dim3(kThreads), 0, st, A, sw.states.p, sw.lam.p, (const Op*)sw.ops.p,
+                       (const int32_t*)sw.meta.p, (const double2*)sw.cs.p, sw.gpart.p, o);
+  hipLaunchKernelGGL(k_sg_reduce, dim3(A.max_params, B), dim3(kThreads), 0, st, A, (const Op*)sw.ops.p,
+                     (const int32_t*)sw.meta.p, (const double*)sw.gpart.p, gblk, grad);
+  HIP_TRY(err, hipGetLastError());
   return 0;
 }
 

@@ -141,6 +141,47 @@ def test_two_qubit_rotations():
     assert abs(e - eng.energy(th)) <= 1e-10 * scale
 
 
+def test_work_buffers_across_alternating_uses():
+    """One handle, energy and gradient runs of different batch sizes in turn: the streaming work buffers grow, are used
+    again by a smaller batch, and the block partials are sized by the energy run and by the gradient run in turn.
+    Energy of one stream, energy and gradient of three, the energy of the three again (the gradient's backward sweep
+    undid their states: the energy run makes them anew), energy of one.  Tolerances: those of test_two_qubit_rotations
+    here and of test_streaming_path (tests/test_hip_parity.py) at n = 14."""
+    n = 14
+    rng = np.random.default_rng(1414)
+    #       RY  RX  CNOT RXX     RZ  RY  RZZ     RX
+    kind = np.array([2, 1, 0, s4.RXX, 3, 2, s4.RZZ, 1], np.int32)
+    q0 = np.array([0, 13, 0, 5, 7, 9, 12, 3], np.int32)
+    q1 = np.array([-1, -1, 7, 11, -1, -1, 2, -1], np.int32)
+    pidx = np.array([0, 1, -1, 2, 3, 4, 5, 6], np.int32)
+    P = 7
+    xs, zs = [], []
+    for x in (0, 0, 1 << 5 | 1 << 11, 1 << 5 | 1 << 11, 1 | 1 << 7 | 1 << 12, 1 | 1 << 7 | 1 << 12):      # two X masks besides the diagonal
+        z = int(rng.integers(0, 1 << n))
+        if bin(x & z).count("1") % 2:          # an even number of Y factors: every term Hermitian on its own
+            z ^= x & -x
+        xs.append(x); zs.append(z)
+    ham = (np.array(xs, np.uint64), np.array(zs, np.uint64), rng.normal(size=len(xs)))
+    assert len(set(xs) - {0}) >= 2
+    psi0 = random_state(n, rng)
+    eng = _engine(n, ham, psi0, _circuit(kind, q0, q1, pidx, P))
+    assert not eng.device_info()["lds_path"]
+    scale = _scale(ham)
+    th1 = rng.uniform(-np.pi, np.pi, P)
+    th3 = rng.uniform(-np.pi, np.pi, (3, P))
+    e1_ref = s4.energy(psi0, kind, q0, q1, pidx, th1, ham)
+    e3_ref = np.array([s4.energy(psi0, kind, q0, q1, pidx, t, ham) for t in th3])
+    assert abs(eng.energy(th1) - e1_ref) <= 1e-10
+    e, g = eng.energy_grad_batch(th3)
+    for b in range(3):
+        g_ref = s4.shift_grad(psi0, kind, q0, q1, pidx, th3[b], ham)
+        print("stream", b, "grad err", np.abs(g[b] - g_ref).max(), "energy err", abs(e[b] - e3_ref[b]), "scale", scale)
+        assert np.abs(g[b] - g_ref).max() <= 1e-10 * scale
+    assert np.abs(e - e3_ref).max() <= 1e-10 * scale
+    assert np.abs(eng.energy_batch(th3) - e3_ref).max() <= 1e-10
+    assert abs(eng.energy(th1) - e1_ref) <= 1e-10
+
+
 def test_untiled_forward_path():
     """More than 4096 terms: stream_tiled() is false, the forward pass is k_s_opk's.  The oracle pays for every term
     at every shifted angle, hence the short circuit."""

@@ -16,7 +16,10 @@
  * Conventions (quimb): MPS site 0 is the most significant bit of the dense index; a gate on
  * sites (i, i+1) is a row-major 4x4 complex matrix indexed by 2*s_i + s_{i+1}.  Complex
  * numbers are interleaved (re, im) doubles.  Plain C types only; functions return 0 or a
- * negative errno-style code (same values as vqe_hip.h) and never throw across the ABI.
+ * negative errno-style code (same values as vqe_hip.h) and never throw across the ABI:
+ * -22 bad argument or a circuit that does not fit LDS, -19 no usable HIP device, -12 a device or
+ * pinned-host allocation failed (hipErrorOutOfMemory, as in libvqe_hip), -5 any other failure of
+ * a HIP runtime call.
  */
 #ifndef MPS2QC_HIP_H
 #define MPS2QC_HIP_H

@@ -17,20 +17,19 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <string>
 #include <vector>
 
 #include "../../include/mps2qc_hip.h"
+#include "mps2qc_plan.h"
+#include "vqe_devbuf.h"
 
 namespace {
 
-enum { E_OK = 0, E_INVAL = -22, E_NOMEM = -12, E_NODEV = -19, E_HIP = -5 };
-thread_local char g_err[256] = "";
+using namespace mps2qc;
+using vqe::DevBufExact;
 
 typedef double d4 __attribute__((ext_vector_type(4)));
-
-constexpr int kMat = 16;          // complex entries of a gate
-constexpr int kSlotMats = 10;     // LDS matrices per 16-lane update group
-constexpr int kLdsLimit = 160 * 1024;
 
 struct FitArgs {
   int G, max_iter, frozen, use_mfma, target_shared;
@@ -716,15 +715,78 @@ __global__ __launch_bounds__(NT) void k_fit(FitArgs A) {
   }
 }
 
-#define HIP_TRY(x)                                                                        \
-  do {                                                                                    \
-    hipError_t e_ = (x);                                                                  \
-    if (e_ != hipSuccess) {                                                               \
-      snprintf(g_err, sizeof g_err, "%s: %s", #x, hipGetErrorString(e_));                 \
-      rc = E_HIP;                                                                         \
-      goto done;                                                                          \
-    }                                                                                     \
-  } while (0)
+// ---- host layer ----------------------------------------------------------------------------------------
+thread_local char g_err[256] = "";
+
+// what HIP_TRY and the entry points hand to fail(): the message goes to the calling thread's g_err
+struct ErrOut {};
+int fail(ErrOut, int code, const std::string& msg) {
+  snprintf(g_err, sizeof g_err, "%s", msg.c_str());
+  return code;
+}
+
+// owner of a HIP resource that is not a device buffer
+template <class T, hipError_t (*Destroy)(T)>
+struct Owned {
+  T h = nullptr;
+  Owned() = default;
+  Owned(const Owned&) = delete;
+  Owned& operator=(const Owned&) = delete;
+  ~Owned() { if (h) (void)Destroy(h); }
+};
+using Stream = Owned<hipStream_t, hipStreamDestroy>;
+using Event = Owned<hipEvent_t, hipEventDestroy>;
+using Graph = Owned<hipGraph_t, hipGraphDestroy>;
+using GraphExec = Owned<hipGraphExec_t, hipGraphExecDestroy>;
+using Pinned = Owned<void*, hipHostFree>;
+
+// The experiment knobs.
+//   MPS2QC_GROUPED       the half-layer scheme pays at 12 qubits (-9 % per step); at 10 / 11 qubits it leaves too many
+//                        threads idle in the pair sweeps and is 5-20 % slower.  Unset: from 12 qubits; a value that
+//                        atoi reads as 0: never; any other value: from 10 qubits.  Read at every call.
+//   MPS2QC_RED2          set (any value): two MFMA partial buffers even where LDS has room for one per gate of the
+//                        largest run.  Read at every call.
+//   MPS2QC_STREAM_GRAPH  first character '0': the streaming fit enqueues every step with plain launches instead of
+//                        replaying a graph.  Read once per process, by the first streaming fit.
+struct Knobs {
+  int grouped_min_n;
+  bool red2, stream_graph;
+};
+Knobs read_knobs(bool streaming) {
+  Knobs k{12, false, true};
+  if (const char* g = getenv("MPS2QC_GROUPED")) k.grouped_min_n = atoi(g) == 0 ? MPS2QC_MAX_QUBITS + 1 : 10;
+  k.red2 = getenv("MPS2QC_RED2") != nullptr;
+  if (streaming) {
+    static const bool graph_on = [] { const char* e = getenv("MPS2QC_STREAM_GRAPH"); return !(e && e[0] == '0'); }();
+    k.stream_graph = graph_on;
+  }
+  return k;
+}
+
+// first steps of both entry points: clear the message, check the arguments (-> lo), check the device
+int begin_fit(const char* fn, int n_max, int device_id, int n, int G, int batch, int max_iter, const int32_t* sites,
+              const void* target, const void* init_gates, std::vector<int>& lo) {
+  g_err[0] = 0;
+  std::string msg;
+  if (!check_fit_args(fn, n, n_max, G, batch, max_iter, sites, target, init_gates, lo, msg)) return fail(ErrOut{}, VQE_EINVAL, msg);
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1 || device_id < 0 || device_id >= ndev)
+    return fail(ErrOut{}, VQE_ENODEV, std::string(fn) + ": no usable HIP device (there is no CPU fallback)");
+  return 0;
+}
+
+template <class T>
+int upload(DevBufExact<T>& b, const void* src, size_t count, hipStream_t st) {
+  ErrOut err;
+  HIP_TRY(err, b.reserve(count));
+  HIP_TRY(err, hipMemcpyAsync(b.p, src, count * sizeof(T), hipMemcpyHostToDevice, st));
+  return 0;
+}
+// device -> the caller's array, where the caller asked for it
+template <class T>
+hipError_t download(void* dst, const DevBufExact<T>& src, size_t count) {
+  return dst ? hipMemcpy(dst, src.p, count * sizeof(T), hipMemcpyDeviceToHost) : hipSuccess;
+}
 
 template <int N, int NT, bool MFMA, bool GRP>
 hipError_t launch2(const FitArgs& A, int batch, size_t lds, hipStream_t st) {
@@ -743,6 +805,15 @@ hipError_t launch(const FitArgs& A, int batch, size_t lds, hipStream_t st, bool 
   }
   return A.use_mfma ? launch2<N, NT, true, false>(A, batch, lds, st) : launch2<N, NT, false, false>(A, batch, lds, st);
 }
+// k_fit<n, threads_per_fit(n)>: the block size the LDS layout was planned for
+hipError_t launch_fit(int n, const FitArgs& A, int batch, size_t lds, hipStream_t st, bool grouped) {
+  switch (n) {
+#define CASE(NN) case NN: return launch<NN, threads_per_fit(NN)>(A, batch, lds, st, grouped);
+    CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8) CASE(9) CASE(10) CASE(11) CASE(12)
+#undef CASE
+  }
+  return hipErrorInvalidValue;
+}
 
 }  // namespace
 
@@ -751,10 +822,7 @@ extern "C" {
 const char* mps2qc_last_error(void) { return g_err; }
 
 int mps2qc_brickwork_sites(int n_qubits, int n_layers, int32_t* sites, int cap) {
-  if (n_qubits < 2 || n_layers < 0 || (!sites && cap > 0)) {
-    snprintf(g_err, sizeof g_err, "mps2qc_brickwork_sites: bad argument");
-    return E_INVAL;
-  }
+  if (n_qubits < 2 || n_layers < 0 || (!sites && cap > 0)) return fail(ErrOut{}, VQE_EINVAL, "mps2qc_brickwork_sites: bad argument");
   int cnt = 0;
   for (int l = 0; l < n_layers; ++l)
     for (int par = 0; par < 2; ++par)
@@ -771,167 +839,74 @@ int mps2qc_fit_brickwork(int device_id, int n, int G, const int32_t* sites, int 
                          double tol, double param_tol, int use_mfma, double* opt_gates,
                          double* final_gates, double* loss_history, double* best_val, int32_t* n_iter,
                          double* last_envs, double* last_overlap, float* kernel_ms) {
-  int rc = E_OK;
-  g_err[0] = 0;
-  if (n < 2 || n > MPS2QC_MAX_QUBITS || G < 1 || batch < 1 || max_iter < 1 || !sites || !target ||
-      !init_gates) {
-    snprintf(g_err, sizeof g_err, "mps2qc_fit_brickwork: bad argument (2 <= n <= %d, G, batch, max_iter >= 1)",
-             MPS2QC_MAX_QUBITS);
-    return E_INVAL;
-  }
-  std::vector<int> lo(G);
-  for (int k = 0; k < G; ++k) {
-    if (sites[k] < 0 || sites[k] > n - 2) {
-      snprintf(g_err, sizeof g_err, "mps2qc_fit_brickwork: gate %d on sites (%d,%d) outside the register", k,
-               sites[k], sites[k] + 1);
-      return E_INVAL;
-    }
-    lo[k] = n - 2 - sites[k];
-  }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1 || device_id < 0 || device_id >= ndev) {
-    snprintf(g_err, sizeof g_err, "mps2qc_fit_brickwork: no usable HIP device (there is no CPU fallback)");
-    return E_NODEV;
-  }
-  // bias-corrected learning rate of every step (stiefel_opt.py:333-335); t = 1 when frozen
-  std::vector<double> lr_t(max_iter);
-  for (int it = 0; it < max_iter; ++it) {
-    const double t = jit_frozen ? 1.0 : (double)(it + 1);
-    lr_t[it] = lr * sqrt(1.0 - pow(beta2, t)) / (1.0 - pow(beta1, t));
-  }
+  ErrOut err;
+  std::vector<int> lo;
+  VQE_TRY(begin_fit("mps2qc_fit_brickwork", MPS2QC_MAX_QUBITS, device_id, n, G, batch, max_iter, sites, target, init_gates, lo));
 
-  // threads per fit: enough waves per SIMD to hide the LDS latency of the gate sweeps
-  // threads per fit: enough waves per SIMD to hide the LDS latency of the gate sweeps
-  const int NT = n <= 8 ? 64 : n <= 10 ? 256 : 512;
-  // runs of mutually disjoint gates (brickwork half layers) for the half-layer scheme
-  std::vector<int> grp;
-  {
-    unsigned used = 0;
-    for (int k = 0; k < G; ++k) {
-      const unsigned bits = 3u << lo[k];
-      if (grp.empty() || (used & bits)) {
-        grp.push_back(k), grp.push_back(0);
-        used = 0;
-      }
-      used |= bits;
-      ++grp.back();
-    }
-  }
-  // the half-layer scheme pays at 12 qubits (-9 % per step); at 10 / 11 qubits it leaves too many
-  // threads idle in the pair sweeps and is 5-20 % slower
-  bool grouped = use_mfma && n >= (getenv("MPS2QC_GROUPED") ? 10 : 12) && !(getenv("MPS2QC_GROUPED") && atoi(getenv("MPS2QC_GROUPED")) == 0);
-  const size_t dim = (size_t)1 << n;
+  // plan: runs of disjoint gates, the LDS layout for this block size, the learning rate of every step
+  const Knobs knobs = read_knobs(false);
+  const std::vector<int> runs = disjoint_runs(lo);
+  const bool grouped = use_mfma && n >= knobs.grouped_min_n;
+  FitLds L;
+  std::string msg;
+  if (!plan_fit_lds(n, G, runs, threads_per_fit(n), grouped, knobs.red2, L, msg)) return fail(err, VQE_EINVAL, msg);
+  std::vector<double> lr_t(max_iter);
+  for (int it = 0; it < max_iter; ++it) lr_t[it] = lr_schedule(lr, beta1, beta2, jit_frozen != 0, it);
+
+  // allocate and upload
+  const size_t gcount = (size_t)batch * G * kMat, hcount = (size_t)batch * max_iter;
+  const size_t tcount = (target_shared ? 1 : (size_t)batch) << n;
+  Stream st;
+  Event e0, e1;
+  DevBufExact<int> d_lo, d_grp, d_ni;
+  DevBufExact<double> d_lr, d_hist, d_bv;
+  DevBufExact<double2> d_t, d_init, d_fin, d_best, d_m, d_v, d_env, d_ov;
+  HIP_TRY(err, hipSetDevice(device_id));
+  HIP_TRY(err, hipStreamCreate(&st.h));
+  HIP_TRY(err, hipEventCreate(&e0.h));
+  HIP_TRY(err, hipEventCreate(&e1.h));
+  VQE_TRY(upload(d_lo, lo.data(), G, st.h));
+  VQE_TRY(upload(d_grp, runs.data(), runs.size(), st.h));
+  VQE_TRY(upload(d_lr, lr_t.data(), max_iter, st.h));
+  VQE_TRY(upload(d_t, target, tcount, st.h));
+  VQE_TRY(upload(d_init, init_gates, gcount, st.h));
+  VQE_TRY(upload(d_best, init_gates, gcount, st.h));
+  HIP_TRY(err, d_hist.reserve(hcount));
+  HIP_TRY(err, hipMemsetAsync(d_hist.p, 0, hcount * sizeof(double), st.h));
+  HIP_TRY(err, d_bv.reserve(batch));
+  HIP_TRY(err, d_ni.reserve(batch));
+  HIP_TRY(err, d_ov.reserve(batch));
+  for (DevBufExact<double2>* b : {&d_fin, &d_m, &d_v, &d_env}) HIP_TRY(err, b->reserve(gcount));
+
   FitArgs A;
   memset(&A, 0, sizeof A);
-  size_t off = 2 * dim * 16;
-  A.off_u = (int)off, off += (size_t)G * kMat * 16;
-  A.off_e = (int)off, off += (size_t)G * kMat * 16;
-  A.off_red = (int)off;
-  const size_t red_off = off;
-  off += (size_t)2 * (NT / 64) * 64 * 8;  // double buffered (half-layer scheme)
-  A.off_sc = (int)off, off += 2 * 16 * 8;  // one complex partial per wave (<= 16 waves)
-  A.off_dn = (int)off, off += (size_t)((G + 1) & ~1) * 8;
-  A.off_lo = (int)off, off += (size_t)((G + 3) & ~3) * 4;
-  A.off_grp = (int)off, off += (size_t)((grp.size() + 3) & ~(size_t)3) * 4;
-  const size_t scratch = (size_t)(NT / 16 < 16 ? NT / 16 : 16) * kSlotMats * kMat * 16;
-  if (2 * dim * 16 >= scratch) A.off_scratch = 0;  // overlay on psi / phi, idle during the update
-  else A.off_scratch = (int)off, off += scratch;
-  int red_slots = 2;
-  if (grouped && !getenv("MPS2QC_RED2")) {  // one partial buffer per gate of the largest run when LDS has room: moves everything behind red
-    int big = 2;
-    for (size_t g = 1; g < grp.size(); g += 2) big = grp[g] > big ? grp[g] : big;
-    const size_t extra = (size_t)(big - 2) * (NT / 64) * 64 * 8;
-    if (off + extra <= (size_t)kLdsLimit) {
-      red_slots = big;
-      off += extra;
-      A.off_sc += (int)extra, A.off_dn += (int)extra, A.off_lo += (int)extra, A.off_grp += (int)extra;
-      if (A.off_scratch) A.off_scratch += (int)extra;
-    }
-  }
-  (void)red_off;
-  if (off > (size_t)kLdsLimit) {
-    snprintf(g_err, sizeof g_err, "mps2qc_fit_brickwork: %d gates at %d qubits need %zu B of LDS (limit %d)", G, n,
-             off, kLdsLimit);
-    return E_INVAL;
-  }
-
-  const size_t gsz = (size_t)batch * G * kMat * 16;
-  const size_t tsz = (target_shared ? 1 : (size_t)batch) * dim * 16;
-  int *d_lo = nullptr, *d_grp = nullptr;
-  double *d_lr = nullptr, *d_hist = nullptr, *d_bv = nullptr;
-  double2 *d_t = nullptr, *d_init = nullptr, *d_fin = nullptr, *d_best = nullptr, *d_m = nullptr, *d_v = nullptr,
-          *d_env = nullptr, *d_ov = nullptr;
-  int* d_ni = nullptr;
-  hipStream_t st = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  float ms = 0.f;
-
-  HIP_TRY(hipSetDevice(device_id));
-  HIP_TRY(hipStreamCreate(&st));
-  HIP_TRY(hipEventCreate(&e0));
-  HIP_TRY(hipEventCreate(&e1));
-  HIP_TRY(hipMalloc(&d_lo, G * sizeof(int)));
-  HIP_TRY(hipMalloc(&d_grp, grp.size() * sizeof(int)));
-  HIP_TRY(hipMalloc(&d_lr, max_iter * sizeof(double)));
-  HIP_TRY(hipMalloc(&d_hist, (size_t)batch * max_iter * sizeof(double)));
-  HIP_TRY(hipMalloc(&d_bv, batch * sizeof(double)));
-  HIP_TRY(hipMalloc(&d_ni, batch * sizeof(int)));
-  HIP_TRY(hipMalloc(&d_t, tsz));
-  HIP_TRY(hipMalloc(&d_init, gsz));
-  HIP_TRY(hipMalloc(&d_fin, gsz));
-  HIP_TRY(hipMalloc(&d_best, gsz));
-  HIP_TRY(hipMalloc(&d_m, gsz));
-  HIP_TRY(hipMalloc(&d_v, gsz));
-  HIP_TRY(hipMalloc(&d_env, gsz));
-  HIP_TRY(hipMalloc(&d_ov, batch * 16));
-  HIP_TRY(hipMemcpyAsync(d_lo, lo.data(), G * sizeof(int), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(d_grp, grp.data(), grp.size() * sizeof(int), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(d_lr, lr_t.data(), max_iter * sizeof(double), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(d_t, target, tsz, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(d_init, init_gates, gsz, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemsetAsync(d_hist, 0, (size_t)batch * max_iter * sizeof(double), st));
-  HIP_TRY(hipMemcpyAsync(d_best, init_gates, gsz, hipMemcpyHostToDevice, st));
-
   A.G = G, A.max_iter = max_iter, A.frozen = jit_frozen ? 1 : 0, A.use_mfma = use_mfma ? 1 : 0;
   A.target_shared = target_shared ? 1 : 0;
   A.beta1 = beta1, A.beta2 = beta2, A.eps = eps, A.tol = tol, A.param_tol = param_tol;
-  A.grp = d_grp, A.n_groups = (int)grp.size() / 2, A.red_slots = red_slots;
-  A.lo = d_lo, A.lr_t = d_lr, A.target = d_t, A.init = d_init, A.final_g = d_fin, A.best_g = d_best;
-  A.mom = d_m, A.vel = d_v, A.hist = d_hist, A.best_val = d_bv, A.n_iter = d_ni, A.envs = d_env, A.overlap = d_ov;
+  A.lo = d_lo.p, A.lr_t = d_lr.p, A.target = d_t.p, A.init = d_init.p, A.final_g = d_fin.p, A.best_g = d_best.p;
+  A.mom = d_m.p, A.vel = d_v.p, A.hist = d_hist.p, A.best_val = d_bv.p, A.n_iter = d_ni.p, A.envs = d_env.p, A.overlap = d_ov.p;
+  A.off_u = L.off_u, A.off_e = L.off_e, A.off_red = L.off_red, A.off_sc = L.off_sc, A.off_dn = L.off_dn, A.off_lo = L.off_lo;
+  A.off_scratch = L.off_scratch, A.off_grp = L.off_grp;
+  A.grp = d_grp.p, A.n_groups = (int)runs.size() / 2, A.red_slots = L.red_slots;
 
-  HIP_TRY(hipEventRecord(e0, st));
-  {
-    hipError_t le = hipErrorInvalidValue;
-    switch (n) {
-#define CASE(NN, TT) case NN: le = launch<NN, TT>(A, batch, off, st, grouped); break;
-      CASE(2, 64) CASE(3, 64) CASE(4, 64) CASE(5, 64) CASE(6, 64) CASE(7, 64) CASE(8, 64)
-      CASE(9, 256) CASE(10, 256) CASE(11, 512)
-      CASE(12, 512)
-#undef CASE
-    }
-    HIP_TRY(le);
-  }
-  HIP_TRY(hipEventRecord(e1, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+  // launch
+  float ms = 0.f;
+  HIP_TRY(err, hipEventRecord(e0.h, st.h));
+  HIP_TRY(err, launch_fit(n, A, batch, L.total, st.h, grouped));
+  HIP_TRY(err, hipEventRecord(e1.h, st.h));
+  HIP_TRY(err, hipStreamSynchronize(st.h));
+  HIP_TRY(err, hipEventElapsedTime(&ms, e0.h, e1.h));
   if (kernel_ms) *kernel_ms = ms;
-  if (opt_gates) HIP_TRY(hipMemcpy(opt_gates, d_best, gsz, hipMemcpyDeviceToHost));
-  if (final_gates) HIP_TRY(hipMemcpy(final_gates, d_fin, gsz, hipMemcpyDeviceToHost));
-  if (loss_history)
-    HIP_TRY(hipMemcpy(loss_history, d_hist, (size_t)batch * max_iter * sizeof(double), hipMemcpyDeviceToHost));
-  if (best_val) HIP_TRY(hipMemcpy(best_val, d_bv, batch * sizeof(double), hipMemcpyDeviceToHost));
-  if (n_iter) HIP_TRY(hipMemcpy(n_iter, d_ni, batch * sizeof(int), hipMemcpyDeviceToHost));
-  if (last_envs) HIP_TRY(hipMemcpy(last_envs, d_env, gsz, hipMemcpyDeviceToHost));
-  if (last_overlap) HIP_TRY(hipMemcpy(last_overlap, d_ov, (size_t)batch * 16, hipMemcpyDeviceToHost));
 
-done:
-  for (void* p : {(void*)d_grp, (void*)d_lo, (void*)d_lr, (void*)d_hist, (void*)d_bv, (void*)d_ni, (void*)d_t, (void*)d_init,
-                  (void*)d_fin, (void*)d_best, (void*)d_m, (void*)d_v, (void*)d_env, (void*)d_ov})
-    (void)hipFree(p);
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  if (st) (void)hipStreamDestroy(st);
-  return rc;
+  // download
+  HIP_TRY(err, download(opt_gates, d_best, gcount));
+  HIP_TRY(err, download(final_gates, d_fin, gcount));
+  HIP_TRY(err, download(loss_history, d_hist, hcount));
+  HIP_TRY(err, download(best_val, d_bv, batch));
+  HIP_TRY(err, download(n_iter, d_ni, batch));
+  HIP_TRY(err, download(last_envs, d_env, gcount));
+  HIP_TRY(err, download(last_overlap, d_ov, batch));
+  return 0;
 }
 
 }  // extern "C"
@@ -1159,6 +1134,105 @@ inline C4 h_update(const C4& p, const C4& g, C4& mom_io, C4& vel_io, bool frozen
   return y;
 }
 
+
+// One optimiser step on the device: gates in (h_gin), overlaps and environments out (h_ov, h_env).  It is the same
+// 3 G + 5 launches and three copies every time - only the gate values change - so capture() records the sequence ONCE
+// into a hipGraph and run() replays it (a launch of ~10 us on a 4 MiB vector otherwise waits for the host to enqueue
+// it).  The graph's copy nodes need page-locked host buffers.
+struct SfStep {
+  int B, G, target_shared;
+  size_t dim;
+  const int* lo;                                         // [G], host
+  double2 *psi, *phi, *tgt, *gates, *part, *ov, *env;    // device
+  double2 *h_gin, *h_ov, *h_env;                         // page-locked: [B][G][16], [B], [B][G][16]
+  Graph graph;
+  GraphExec exec;
+
+  static unsigned blocks(size_t items) { return (unsigned)((items + kSfThreads - 1) / kSfThreads); }
+
+  hipError_t enqueue(hipStream_t st) const {
+    const size_t gcount = (size_t)B * G * kMat;
+    const unsigned blk_amp = blocks(dim), blk_vec = blocks(dim / 4);
+    hipError_t e = hipMemcpyAsync(gates, h_gin, gcount * 16, hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_sf_zero_state, dim3(blk_amp, B), dim3(kSfThreads), 0, st, psi, dim);
+    for (int k = 0; k < G; ++k)
+      hipLaunchKernelGGL(k_sf_apply, dim3(blk_vec, B), dim3(kSfThreads), 0, st, psi, dim, gates, G, k, lo[k], 0);
+    hipLaunchKernelGGL(k_sf_dot, dim3(blk_amp, B), dim3(kSfThreads), 0, st, tgt, target_shared, psi, dim, part);
+    hipLaunchKernelGGL(k_sf_reduce, dim3(B), dim3(kSfThreads), 0, st, part, (int)blk_amp, 1, ov, 1, 0);
+    hipLaunchKernelGGL(k_sf_copy, dim3(blk_amp, B), dim3(kSfThreads), 0, st, phi, tgt, dim, target_shared);
+    for (int k = G - 1; k >= 0; --k) {
+      hipLaunchKernelGGL(k_sf_back, dim3(blk_vec, B), dim3(kSfThreads), 0, st, psi, phi, dim, gates, G, k, lo[k], part);
+      hipLaunchKernelGGL(k_sf_reduce, dim3(B), dim3(kSfThreads), 0, st, part, (int)blk_vec, 16, env, G * kMat, k);
+    }
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = hipMemcpyAsync(h_ov, ov, (size_t)B * 16, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
+    return hipMemcpyAsync(h_env, env, gcount * 16, hipMemcpyDeviceToHost, st);
+  }
+  // st must be idle.  A capture that fails is dropped without a word: run() then enqueues plain launches.
+  void capture(hipStream_t st) {
+    if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+      const hipError_t e = enqueue(st), e2 = hipStreamEndCapture(st, &graph.h);
+      if (e == hipSuccess && e2 == hipSuccess && graph.h && hipGraphInstantiate(&exec.h, graph.h, nullptr, nullptr, 0) == hipSuccess) return;
+      exec.h = nullptr;
+    }
+    (void)hipGetLastError();
+  }
+  hipError_t run(hipStream_t st) const { return exec.h ? hipGraphLaunch(exec.h, st) : enqueue(st); }
+};
+
+// The host half of the streaming fit: every fit's gates and moments, and what minimize() keeps (stiefel_opt.py:91-152)
+struct SfHost {
+  int B, G, max_iter;
+  bool frozen;
+  double lr, beta1, beta2, eps, tol, param_tol;
+  double* loss_history;                      // the caller's, or null
+  const double2 *h_ov, *h_env;               // what the device step left
+  std::vector<C4> U, Ubest, mom, vel;        // [B][G]
+  std::vector<double> bv;
+  std::vector<int> nit, active;
+
+  SfHost(int B_, int G_, const double* init_gates) : B(B_), G(G_), U((size_t)B_ * G_), mom(U.size()), vel(U.size()), bv(B_, 10000.0), nit(B_, 0), active(B_, 1) {
+    memcpy(U.data(), init_gates, U.size() * sizeof(C4));
+    Ubest = U;
+    memset(mom.data(), 0, mom.size() * sizeof(C4));
+    memset(vel.data(), 0, vel.size() * sizeof(C4));
+  }
+  bool any_active() const {
+    int any = 0;
+    for (int b = 0; b < B; ++b) any |= active[b];
+    return any != 0;
+  }
+  // fit b after device step `it`: StiefelAdam.update of every gate, then the bookkeeping of minimize()
+  void host_step(int b, int it) {
+    const double lr_t = lr_schedule(lr, beta1, beta2, frozen, it);
+    const double2 o = h_ov[b];
+    const double ao = hypot(o.x, o.y), val = 1.0 - ao;
+    const double2 ph = make_double2(o.x / ao, o.y / ao);
+    double dsum = 0.0;
+    for (int k = 0; k < G; ++k) {
+      C4 g;      // -(o/|o|) conj(E_k): what step() hands to update() (:107-109)
+      for (int e = 0; e < 16; ++e) {
+        const double2 E = h_env[((size_t)b * G + k) * kMat + e];
+        const double2 v = h_mul(ph, make_double2(E.x, -E.y));
+        g.a[e] = make_double2(-v.x, -v.y);
+      }
+      double dn;
+      U[(size_t)b * G + k] = h_update(U[(size_t)b * G + k], g, mom[(size_t)b * G + k], vel[(size_t)b * G + k], frozen, lr_t,
+                                      beta1, beta2, eps, &dn);
+      dsum += dn;
+    }
+    // bookkeeping of minimize() (:124-147)
+    if (loss_history) loss_history[(size_t)b * max_iter + it] = val;
+    nit[b] = it + 1;
+    if (val < bv[b]) {
+      bv[b] = val;
+      for (int k = 0; k < G; ++k) Ubest[(size_t)b * G + k] = U[(size_t)b * G + k];
+    }
+    if (val < tol || dsum / G < param_tol) active[b] = 0;
+  }
+};
+
 }  // namespace
 
 extern "C" int mps2qc_fit_brickwork_stream(int device_id, int n, int G, const int32_t* sites, int batch, const double* target,
@@ -1166,157 +1240,66 @@ extern "C" int mps2qc_fit_brickwork_stream(int device_id, int n, int G, const in
                                            double eps, int jit_frozen, int max_iter, double tol, double param_tol,
                                            double* opt_gates, double* final_gates, double* loss_history, double* best_val,
                                            int32_t* n_iter, double* last_envs, double* last_overlap, float* total_ms) {
-  int rc = E_OK;
-  g_err[0] = 0;
-  if (n < 2 || n > MPS2QC_STREAM_MAX_QUBITS || G < 1 || batch < 1 || max_iter < 1 || !sites || !target || !init_gates) {
-    snprintf(g_err, sizeof g_err, "mps2qc_fit_brickwork_stream: bad argument (2 <= n <= %d, G, batch, max_iter >= 1)",
-             MPS2QC_STREAM_MAX_QUBITS);
-    return E_INVAL;
-  }
-  std::vector<int> lo(G);
-  for (int k = 0; k < G; ++k) {
-    if (sites[k] < 0 || sites[k] > n - 2) {
-      snprintf(g_err, sizeof g_err, "mps2qc_fit_brickwork_stream: gate %d on sites (%d,%d) outside the register", k, sites[k], sites[k] + 1);
-      return E_INVAL;
-    }
-    lo[k] = n - 2 - sites[k];
-  }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1 || device_id < 0 || device_id >= ndev) {
-    snprintf(g_err, sizeof g_err, "mps2qc_fit_brickwork_stream: no usable HIP device (there is no CPU fallback)");
-    return E_NODEV;
-  }
-  const size_t dim = (size_t)1 << n;
-  const int B = batch;
-  const size_t gcount = (size_t)B * G * kMat;
-  const unsigned blk_amp = (unsigned)((dim + kSfThreads - 1) / kSfThreads), blk_vec = (unsigned)((dim / 4 + kSfThreads - 1) / kSfThreads);
-  std::vector<C4> U((size_t)B * G), Ubest((size_t)B * G), mom((size_t)B * G), vel((size_t)B * G);
-  memcpy(U.data(), init_gates, gcount * 16);
-  Ubest = U;
-  memset(mom.data(), 0, gcount * 16);
-  memset(vel.data(), 0, gcount * 16);
-  std::vector<double> bv(B, 10000.0);
-  std::vector<int> nit(B, 0), active(B, 1);
-  if (loss_history) memset(loss_history, 0, (size_t)B * max_iter * sizeof(double));
-  // One optimiser step is the same 3 G + 5 launches and three copies every time - only the gate values change: the
-  // sequence is captured ONCE into a hipGraph and replayed (a launch of ~10 us on a 4 MiB vector otherwise waits for
-  // the host to enqueue it; MPS2QC_STREAM_GRAPH=0: plain launches, for comparison).  The graph's copy nodes need
-  // page-locked host buffers: h_pin = [gates in | overlaps out | environments out].
-  double2 *h_pin = nullptr, *h_gin = nullptr, *h_ov = nullptr, *h_env = nullptr;
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t gexec = nullptr;
-  static const bool graph_on = [] { const char* e = getenv("MPS2QC_STREAM_GRAPH"); return !(e && e[0] == '0'); }();
+  ErrOut err;
+  std::vector<int> lo;
+  VQE_TRY(begin_fit("mps2qc_fit_brickwork_stream", MPS2QC_STREAM_MAX_QUBITS, device_id, n, G, batch, max_iter, sites, target, init_gates, lo));
+  const Knobs knobs = read_knobs(true);
+  const size_t dim = (size_t)1 << n, gcount = (size_t)batch * G * kMat;
+  const size_t tcount = (target_shared ? 1 : (size_t)batch) * dim;
+  const size_t nblk = SfStep::blocks(dim);      // >= the blocks of a sweep over 4-vectors
 
-  double2 *d_psi = nullptr, *d_phi = nullptr, *d_t = nullptr, *d_g = nullptr, *d_part = nullptr, *d_ov = nullptr, *d_env = nullptr;
-  hipStream_t st = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
+  SfHost H(batch, G, init_gates);
+  H.max_iter = max_iter, H.frozen = jit_frozen != 0, H.lr = lr, H.beta1 = beta1, H.beta2 = beta2, H.eps = eps;
+  H.tol = tol, H.param_tol = param_tol, H.loss_history = loss_history;
+  if (loss_history) memset(loss_history, 0, (size_t)batch * max_iter * sizeof(double));
+
+  // allocate and upload; pin = [gates in | overlaps out | environments out]
+  Stream st;
+  Event e0, e1;
+  Pinned pin;
+  SfStep S;
+  DevBufExact<double2> d_psi, d_phi, d_t, d_g, d_part, d_ov, d_env;
+  HIP_TRY(err, hipSetDevice(device_id));
+  HIP_TRY(err, hipStreamCreate(&st.h));
+  HIP_TRY(err, hipEventCreate(&e0.h));
+  HIP_TRY(err, hipEventCreate(&e1.h));
+  HIP_TRY(err, d_psi.reserve((size_t)batch * dim));
+  HIP_TRY(err, d_phi.reserve((size_t)batch * dim));
+  HIP_TRY(err, d_g.reserve(gcount));
+  HIP_TRY(err, d_part.reserve((size_t)batch * nblk * 16));
+  HIP_TRY(err, d_ov.reserve(batch));
+  HIP_TRY(err, d_env.reserve(gcount));
+  HIP_TRY(err, hipHostMalloc(&pin.h, (2 * gcount + (size_t)batch) * 16, hipHostMallocDefault));
+  VQE_TRY(upload(d_t, target, tcount, st.h));
+  S.B = batch, S.G = G, S.target_shared = target_shared ? 1 : 0, S.dim = dim, S.lo = lo.data();
+  S.psi = d_psi.p, S.phi = d_phi.p, S.tgt = d_t.p, S.gates = d_g.p, S.part = d_part.p, S.ov = d_ov.p, S.env = d_env.p;
+  S.h_gin = static_cast<double2*>(pin.h), S.h_ov = S.h_gin + gcount, S.h_env = S.h_ov + batch;
+  H.h_ov = S.h_ov, H.h_env = S.h_env;
+
+  // the loop: device step, then the host step of every fit that has not stopped
   float ms = 0.f;
-  const size_t tsz = (target_shared ? 1 : (size_t)B) * dim * 16;
-  HIP_TRY(hipSetDevice(device_id));
-  HIP_TRY(hipStreamCreate(&st));
-  HIP_TRY(hipEventCreate(&e0));
-  HIP_TRY(hipEventCreate(&e1));
-  HIP_TRY(hipMalloc(&d_psi, (size_t)B * dim * 16));
-  HIP_TRY(hipMalloc(&d_phi, (size_t)B * dim * 16));
-  HIP_TRY(hipMalloc(&d_t, tsz));
-  HIP_TRY(hipMalloc(&d_g, gcount * 16));
-  HIP_TRY(hipMalloc(&d_part, (size_t)B * (blk_vec > blk_amp ? blk_vec : blk_amp) * 16 * 16));
-  HIP_TRY(hipMalloc(&d_ov, (size_t)B * 16));
-  HIP_TRY(hipMalloc(&d_env, gcount * 16));
-  HIP_TRY(hipHostMalloc((void**)&h_pin, (2 * gcount + (size_t)B) * 16, hipHostMallocDefault));
-  h_gin = h_pin; h_ov = h_pin + gcount; h_env = h_ov + B;
-  HIP_TRY(hipMemcpyAsync(d_t, target, tsz, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipEventRecord(e0, st));
-  {
-    auto enqueue_step = [&]() -> hipError_t {
-      hipError_t e = hipMemcpyAsync(d_g, h_gin, gcount * 16, hipMemcpyHostToDevice, st);
-      if (e != hipSuccess) return e;
-      hipLaunchKernelGGL(k_sf_zero_state, dim3(blk_amp, B), dim3(kSfThreads), 0, st, d_psi, dim);
-      for (int k = 0; k < G; ++k)
-        hipLaunchKernelGGL(k_sf_apply, dim3(blk_vec, B), dim3(kSfThreads), 0, st, d_psi, dim, d_g, G, k, lo[k], 0);
-      hipLaunchKernelGGL(k_sf_dot, dim3(blk_amp, B), dim3(kSfThreads), 0, st, d_t, target_shared ? 1 : 0, d_psi, dim, d_part);
-      hipLaunchKernelGGL(k_sf_reduce, dim3(B), dim3(kSfThreads), 0, st, d_part, (int)blk_amp, 1, d_ov, 1, 0);
-      hipLaunchKernelGGL(k_sf_copy, dim3(blk_amp, B), dim3(kSfThreads), 0, st, d_phi, d_t, dim, target_shared ? 1 : 0);
-      for (int k = G - 1; k >= 0; --k) {
-        hipLaunchKernelGGL(k_sf_back, dim3(blk_vec, B), dim3(kSfThreads), 0, st, d_psi, d_phi, dim, d_g, G, k, lo[k], d_part);
-        hipLaunchKernelGGL(k_sf_reduce, dim3(B), dim3(kSfThreads), 0, st, d_part, (int)blk_vec, 16, d_env, G * kMat, k);
-      }
-      if ((e = hipGetLastError()) != hipSuccess) return e;
-      if ((e = hipMemcpyAsync(h_ov, d_ov, (size_t)B * 16, hipMemcpyDeviceToHost, st)) != hipSuccess) return e;
-      return hipMemcpyAsync(h_env, d_env, gcount * 16, hipMemcpyDeviceToHost, st);
-    };
-    if (graph_on) {
-      // (the target copy above must have been issued before the capture begins; a failed capture falls back to plain launches)
-      HIP_TRY(hipStreamSynchronize(st));
-      if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-        const hipError_t e = enqueue_step();
-        hipGraph_t g = nullptr;
-        const hipError_t e2 = hipStreamEndCapture(st, &g);
-        if (e == hipSuccess && e2 == hipSuccess && g && hipGraphInstantiate(&gexec, g, nullptr, nullptr, 0) == hipSuccess) graph = g;
-        else {
-          if (g) (void)hipGraphDestroy(g);
-          gexec = nullptr;
-          (void)hipGetLastError();
-        }
-      } else (void)hipGetLastError();
-    }
-  for (int it = 0; it < max_iter; ++it) {
-    int any = 0;
-    for (int b = 0; b < B; ++b) any |= active[b];
-    if (!any) break;
-    memcpy(h_gin, U.data(), gcount * 16);
-    if (gexec) HIP_TRY(hipGraphLaunch(gexec, st));
-    else HIP_TRY(enqueue_step());
-    HIP_TRY(hipStreamSynchronize(st));
-    const double t = jit_frozen ? 1.0 : (double)(it + 1);
-    const double lr_t = lr * sqrt(1.0 - pow(beta2, t)) / (1.0 - pow(beta1, t));      // (stiefel_opt.py:333-335)
-    for (int b = 0; b < B; ++b) {
-      if (!active[b]) continue;
-      const double2 o = h_ov[b];
-      const double ao = hypot(o.x, o.y), val = 1.0 - ao;
-      const double2 ph = make_double2(o.x / ao, o.y / ao);
-      double dsum = 0.0;
-      for (int k = 0; k < G; ++k) {
-        C4 g;      // -(o/|o|) conj(E_k): what step() hands to update() (:107-109)
-        for (int e = 0; e < 16; ++e) {
-          const double2 E = h_env[((size_t)b * G + k) * kMat + e];
-          const double2 v = h_mul(ph, make_double2(E.x, -E.y));
-          g.a[e] = make_double2(-v.x, -v.y);
-        }
-        double dn;
-        U[(size_t)b * G + k] = h_update(U[(size_t)b * G + k], g, mom[(size_t)b * G + k], vel[(size_t)b * G + k], jit_frozen != 0, lr_t,
-                                        beta1, beta2, eps, &dn);
-        dsum += dn;
-      }
-      // bookkeeping of minimize() (:124-147)
-      if (loss_history) loss_history[(size_t)b * max_iter + it] = val;
-      nit[b] = it + 1;
-      if (val < bv[b]) {
-        bv[b] = val;
-        for (int k = 0; k < G; ++k) Ubest[(size_t)b * G + k] = U[(size_t)b * G + k];
-      }
-      if (val < tol || dsum / G < param_tol) active[b] = 0;
-    }
+  HIP_TRY(err, hipEventRecord(e0.h, st.h));
+  if (knobs.stream_graph) {
+    HIP_TRY(err, hipStreamSynchronize(st.h));      // the target copy must not become part of the capture
+    S.capture(st.h);
   }
+  for (int it = 0; it < max_iter && H.any_active(); ++it) {
+    memcpy(S.h_gin, H.U.data(), gcount * 16);
+    HIP_TRY(err, S.run(st.h));
+    HIP_TRY(err, hipStreamSynchronize(st.h));
+    for (int b = 0; b < batch; ++b)
+      if (H.active[b]) H.host_step(b, it);
   }
-  HIP_TRY(hipEventRecord(e1, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+  HIP_TRY(err, hipEventRecord(e1.h, st.h));
+  HIP_TRY(err, hipStreamSynchronize(st.h));
+  HIP_TRY(err, hipEventElapsedTime(&ms, e0.h, e1.h));
   if (total_ms) *total_ms = ms;
-  if (opt_gates) memcpy(opt_gates, Ubest.data(), gcount * 16);
-  if (final_gates) memcpy(final_gates, U.data(), gcount * 16);
-  if (best_val) memcpy(best_val, bv.data(), B * sizeof(double));
-  if (n_iter) for (int b = 0; b < B; ++b) n_iter[b] = nit[b];
-  if (last_envs) memcpy(last_envs, h_env, gcount * 16);
-  if (last_overlap) memcpy(last_overlap, h_ov, (size_t)B * 16);
 
-done:
-  for (void* p : {(void*)d_psi, (void*)d_phi, (void*)d_t, (void*)d_g, (void*)d_part, (void*)d_ov, (void*)d_env}) (void)hipFree(p);
-  if (gexec) (void)hipGraphExecDestroy(gexec);
-  if (graph) (void)hipGraphDestroy(graph);
-  if (h_pin) (void)hipHostFree(h_pin);
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  if (st) (void)hipStreamDestroy(st);
-  return rc;
+  if (opt_gates) memcpy(opt_gates, H.Ubest.data(), gcount * 16);
+  if (final_gates) memcpy(final_gates, H.U.data(), gcount * 16);
+  if (best_val) memcpy(best_val, H.bv.data(), batch * sizeof(double));
+  if (n_iter) for (int b = 0; b < batch; ++b) n_iter[b] = H.nit[b];
+  if (last_envs) memcpy(last_envs, S.h_env, gcount * 16);
+  if (last_overlap) memcpy(last_overlap, S.h_ov, (size_t)batch * 16);
+  return 0;
 }

@@ -165,3 +165,27 @@ class OracleShardBackend:
 
     def to_host(self, shard):
         return np.asarray(shard)
+
+
+MPS2QC_OUTPUTS = ("opt_gates", "final_gates", "loss_history", "best_val", "n_iter", "last_envs", "last_overlap")
+
+
+def mps2qc_raw_fit(stream, n, sites, target, init, steps, only=MPS2QC_OUTPUTS, frozen=False):
+    """One fit through the raw C ABI of libmps2qc_hip.so (3e-3, 0.9, 0.999, 1e-8; tol 1e-30 and param_tol 0: every
+    step runs).  ``only``: the outputs that get a pointer, every other one is passed as NULL.  Returns the return
+    code and the arrays that were asked for."""
+    import ctypes as C
+    from tensorrl_qas_amd import _lib
+    lib = _lib.load_mps2qc()
+    sites = np.ascontiguousarray(sites, np.int32)
+    target, init = np.ascontiguousarray(target, np.complex128), np.ascontiguousarray(init, np.complex128)
+    B, G = init.shape[0], len(sites)
+    out = dict(opt_gates=np.zeros_like(init), final_gates=np.zeros_like(init), loss_history=np.zeros((B, steps)),
+               best_val=np.zeros(B), n_iter=np.zeros(B, np.int32), last_envs=np.zeros_like(init),
+               last_overlap=np.zeros(B, np.complex128))
+    ptr = {k: (v.ctypes.data_as(_lib.c_i32p if k == "n_iter" else _lib.c_f64p) if k in only else None) for k, v in out.items()}
+    head = (0, n, G, sites.ctypes.data_as(_lib.c_i32p), B, target.ctypes.data_as(_lib.c_f64p), int(target.ndim == 1),
+            init.ctypes.data_as(_lib.c_f64p), 3e-3, 0.9, 0.999, 1e-8, int(frozen), steps, 1e-30, 0.0)
+    tail = tuple(ptr[k] for k in MPS2QC_OUTPUTS) + (None,)
+    rc = lib.mps2qc_fit_brickwork_stream(*head, *tail) if stream else lib.mps2qc_fit_brickwork(*head, 1, *tail)
+    return rc, {k: v for k, v in out.items() if k in only}

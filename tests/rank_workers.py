@@ -180,7 +180,26 @@ def amp_sharded_cpu(rank, world, port):
     return out
 
 
-WORKERS = {"sharded_gpu": sharded_gpu, "sharding_cpu": sharding_cpu, "amp_sharded_cpu": amp_sharded_cpu}
+def mps2qc_stream_fit(rank, world, port):
+    """One process, no process group: the streaming MPS -> PQC fit at 6 qubits (2 layers, batch 2, 5 steps) through
+    the C ABI, every output as the hex of its bytes.  MPS2QC_STREAM_GRAPH is read once per process, so each of its
+    settings needs an interpreter of its own."""
+    for p in (ROOT, os.path.join(ROOT, "oracle"), HERE):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    import numpy as np
+    import stiefel_oracle as so
+    from helpers import mps2qc_raw_fit
+    n, layers, rng = 6, 2, np.random.default_rng(606)
+    sites = so.brickwork_pairs(n, layers)
+    tg = np.array([so.circuit_state(n, sites, so.random_unitaries(len(sites), rng)) for _ in range(2)])
+    init = np.array([so.random_unitaries(len(sites), rng) for _ in range(2)])
+    rc, out = mps2qc_raw_fit(True, n, sites, tg, init, 5)
+    return dict(rc=rc, **{k: v.tobytes().hex() for k, v in out.items()})
+
+
+WORKERS = {"sharded_gpu": sharded_gpu, "sharding_cpu": sharding_cpu, "amp_sharded_cpu": amp_sharded_cpu,
+           "mps2qc_stream_fit": mps2qc_stream_fit}
 
 
 def main(argv):

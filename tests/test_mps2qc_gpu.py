@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 import stiefel_oracle as so
-from helpers import load_case, oracle_init_state
+from helpers import MPS2QC_OUTPUTS, load_case, mps2qc_raw_fit, oracle_init_state
 
 pytestmark = pytest.mark.gpu
 
@@ -288,3 +288,88 @@ def test_ground_state_to_init_circuit_to_environment(tmp_path):
     assert e0 - 1e-9 <= e_fit < float(env2.prev_energy) - 1.0          # a fitted start beats a random one by a lot
     assert fid > 0.5
     assert e_fit - e0 <= (1.0 - fid ** 2) * (env.max_eig - e0) + 1e-9
+
+
+# ---- the host layer, through the raw C ABI ---------------------------------------------------------
+def _raw_problem(n, layers, seed):
+    rng = np.random.default_rng(seed)
+    sites = so.brickwork_pairs(n, layers)
+    tg = np.array([so.circuit_state(n, sites, so.random_unitaries(len(sites), rng)) for _ in range(2)])
+    init = np.array([so.random_unitaries(len(sites), rng) for _ in range(2)])
+    return sites, tg, init
+
+
+_ORACLE4 = {}
+
+
+def _assert_valid_fit4(stream):
+    """A valid 4-qubit fit (2 layers, batch 2, 3 steps) returns 0, matches the oracle and clears the message."""
+    from tensorrl_qas_amd import _lib
+    sites, tg, init = _raw_problem(4, 2, 404)
+    if not _ORACLE4:
+        for b in range(2):
+            ref = so.StiefelAdam(3e-3, 0.9, 0.999, 1e-8)
+            ref.init(init[b])
+            _ORACLE4[b] = ref.minimize(4, list(sites), tg[b], init[b], max_iter=3, tol=1e-30, param_tol=0.0)
+    rc, out = mps2qc_raw_fit(stream, 4, sites, tg, init, 3)
+    assert rc == 0 and _lib.load_mps2qc().mps2qc_last_error() == b""
+    for b in range(2):
+        bv, bp, hist, fin = _ORACLE4[b]
+        assert out["n_iter"][b] == 3 and abs(out["best_val"][b] - bv) < 1e-12
+        assert np.max(np.abs(out["loss_history"][b] - np.array(hist))) < 1e-12
+        assert np.max(np.abs(out["final_gates"][b] - np.array(fin))) < 1e-11
+        assert np.max(np.abs(out["opt_gates"][b] - np.array(bp))) < 1e-11
+
+
+@pytest.mark.parametrize("stream", [False, True])
+def test_null_outputs_through_the_c_abi(stream):
+    """Every output pointer NULL except best_val: the call returns 0 and best_val is, bit for bit, that of the call
+    with all outputs."""
+    sites, tg, init = _raw_problem(4, 2, 404)
+    rc_all, full = mps2qc_raw_fit(stream, 4, sites, tg, init, 3)
+    rc_one, one = mps2qc_raw_fit(stream, 4, sites, tg, init, 3, only=("best_val",))
+    assert rc_all == 0 and rc_one == 0
+    assert list(one) == ["best_val"] and one["best_val"].tobytes() == full["best_val"].tobytes()
+    assert np.all(full["best_val"] > 0) and np.all(full["n_iter"] == 3)
+
+
+def test_error_then_success_on_one_thread():
+    """A refused layout (12 qubits, 66 gates) and a gate outside the register leave a message and no debris: the
+    valid fit that follows on the same thread matches the oracle and mps2qc_last_error() is empty again."""
+    from tensorrl_qas_amd import _lib
+    lib = _lib.load_mps2qc()
+    s12 = so.brickwork_pairs(12, 6)
+    flat = np.ones(1 << 12, complex) / 64
+    rc, _ = mps2qc_raw_fit(False, 12, s12, flat, np.tile(np.eye(4), (1, len(s12), 1, 1)), 1)
+    assert len(s12) == 66 and rc == -22 and b"LDS" in lib.mps2qc_last_error()
+    _assert_valid_fit4(False)
+    sites, tg, init = _raw_problem(4, 2, 404)
+    for stream in (False, True):
+        bad = np.array(sites, np.int32)
+        bad[3] = 3      # the pair (3, 4) of a 4-qubit register
+        rc, _ = mps2qc_raw_fit(stream, 4, bad, tg, init, 3)
+        assert rc == -22 and b"gate 3 on sites (3,4) outside the register" in lib.mps2qc_last_error()
+        _assert_valid_fit4(stream)
+
+
+def test_stream_graph_replay_equals_plain_launches(tmp_path):
+    """MPS2QC_STREAM_GRAPH is read once per process: two fresh interpreters (tests/rank_workers.py), one with the
+    knob at 0, run the same streaming fit; every output is bit-identical."""
+    from rank_workers import run_ranks
+    res = []
+    for knob in ("1", "0"):
+        d = tmp_path / f"graph{knob}"
+        d.mkdir()
+        res.append(run_ranks("mps2qc_stream_fit", 1, d, timeout=120, extra_env={"MPS2QC_STREAM_GRAPH": knob})[0])
+    assert res[0]["rc"] == 0 and res[1]["rc"] == 0
+    assert set(res[0]) == {"rc", *MPS2QC_OUTPUTS} and res[0] == res[1]
+    assert np.all(np.frombuffer(bytes.fromhex(res[0]["n_iter"]), np.int32) == 5)
+
+
+def test_alternating_paths_in_one_process():
+    """LDS fit, streaming fit, LDS fit at 6 qubits: the first and the third are bit-identical."""
+    sites, tg, init = _raw_problem(6, 2, 606)
+    runs = [mps2qc_raw_fit(stream, 6, sites, tg, init, 5) for stream in (False, True, False)]
+    assert [rc for rc, _ in runs] == [0, 0, 0]
+    for k in MPS2QC_OUTPUTS:
+        assert runs[0][1][k].tobytes() == runs[2][1][k].tobytes(), k

@@ -117,6 +117,10 @@ int vqe_set_amplitude_shard(vqe_t* h, int rank, int world);
 /* n >= 14: allow vqe_energy_grad_batch / vqe_batch_run_energy_grad on the streaming path (a second
  * state-sized buffer per resident stream).  0 (default): VQE_EINVAL as before.  n <= 13: accepted, no effect. */
 int vqe_set_stream_grad(vqe_t* h, int enable);
+/* n >= 14: allow vqe_minimize_lbfgs / vqe_batch_run_minimize_lbfgs / vqe_batch_run_env_step_lbfgs on the streaming
+ * path (a second state-sized buffer per resident stream, as vqe_set_stream_grad).  0 (default): VQE_EINVAL as before,
+ * whatever vqe_set_stream_grad says.  n <= 13: accepted, no effect.  Independent of vqe_set_stream_grad. */
+int vqe_set_stream_lbfgs(vqe_t* h, int enable);
 /* The one collective of the term-sharded sum as a library call (RCCL over xGMI; librccl is opened lazily).  Rank 0
  * makes the 128-byte id (vqe_comm_unique_id) and hands it to the other ranks by any means; every rank calls
  * vqe_comm_init on its handle; vqe_comm_allreduce_energy sums the batch's energy array (float64[batch], what
@@ -241,7 +245,11 @@ int vqe_batch_fetch_xopt(vqe_t* h, double* x /* sum of n_params */);
  * status: 0 max|g_j| <= gtol; 1 f - f_new <= ftol max(|f|, |f_new|, 1); 2 no step accepted in max_ls trials (x, f
  * unchanged); 3 maxfun evaluations used; 4 maxiter accepted steps made.  x is always the best point (Armijo makes f
  * monotone).  Parameters that no gate uses never move.
- * 1 <= n <= 13 (n >= 14: VQE_EINVAL).  Refused with VQE_ESTATE, before anything is launched, while Pauli noise, the
+ * 1 <= n <= 13: the one-launch kernel.  n >= 14: VQE_EINVAL unless vqe_set_stream_lbfgs(h, 1) was called; then the same
+ * algorithm runs on the streaming path, all resident streams in lock-step: per evaluation the streaming adjoint gradient
+ * and one small update kernel (csrc/vqe_stream_lbfgs.h), nothing copied to the host in between.  A
+ * vqe_batch_run_reduction right after such a minimise run is refused with VQE_ESTATE (its last launch was a gradient);
+ * after an env-step it is accepted.  Refused with VQE_ESTATE, before anything is launched, while Pauli noise, the
  * exact channel mode, shot noise, an amplitude shard or a term shard (the line search needs the full energy) is set;
  * VQE_EINVAL for history outside 1..16, maxiter < 0, maxfun < 1, max_ls < 1, a negative tolerance or c1 outside (0, 1).
  * opts == NULL: the defaults. */

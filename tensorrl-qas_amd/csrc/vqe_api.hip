@@ -7,6 +7,7 @@
 #include "vqe_dm.h"
 #include "vqe_grad.h"
 #include "vqe_lbfgs.h"
+#include "vqe_stream_lbfgs.h"
 #include "ham_layout.h"
 #include "dm_host.h"
 #include "env_step_host.h"
@@ -120,6 +121,12 @@ struct vqe_handle {
   // adjoint gradient of the streaming path (vqe_stream_grad.h): opt-in (vqe_set_stream_grad); its backward sweep undoes
   // the circuit in place, so the states it leaves are not those a reduction-only launch may take
   bool stream_grad = false, stream_states_undone = false;
+  // device L-BFGS of the streaming path (vqe_stream_lbfgs.h): opt-in (vqe_set_stream_lbfgs); per-stream records, the
+  // results of the streams that stopped, the count of running streams
+  bool stream_lbfgs = false;
+  DevBufExact<StreamLbfgsRec> lb_rec;
+  DevBufExact<double> lb_xres, lb_fres;
+  DevBufExact<int32_t> lb_nfres, lb_running;
 };
 
 #ifdef VQE_STAMPS
@@ -482,6 +489,58 @@ int stream_cobyla(vqe_t* h, BatchArgs& A, const std::vector<int64_t>& pbeg, cons
   return VQE_OK;
 }
 
+// The pre-action circuits of a streaming env-step (pre_action, vqe_geo.h; built by env_step_host.h) as a second
+// resident batch: gates, layout and start point on the host, the device copies in d_*2, and A2 pointed at them.
+struct PreActionBatch {
+  std::vector<GateRec> gates;
+  std::vector<int64_t> gbeg, pbeg;
+  std::vector<int32_t> gcnt, pcnt, hole;
+  std::vector<double> x0;
+};
+int load_pre_action_batch(vqe_t* h, PreActionBatch& pre, BatchArgs& A2) {
+  const int B = h->batch;
+  pre.gbeg.resize(B); pre.pbeg.resize(B); pre.gcnt.resize(B); pre.pcnt.resize(B); pre.hole.resize(B);
+  pre.gates.reserve(h->h_gates.size());
+  for (int b = 0; b < B; ++b) {
+    pre.gbeg[b] = (int64_t)pre.gates.size();
+    pre.pbeg[b] = (int64_t)pre.x0.size();
+    pre.hole[b] = pre_action_circuit(h->h_gates.data() + h->h_gate_begin[b], h->h_gate_count[b],
+                                     h->has_new_gate ? h->h_new_gate[b] : -1, h->h_theta.data() + h->h_par_begin[b],
+                                     h->h_par_count[b], pre.gates, pre.x0).hole;
+    pre.gcnt[b] = (int32_t)((int64_t)pre.gates.size() - pre.gbeg[b]);
+    pre.pcnt[b] = (int32_t)((int64_t)pre.x0.size() - pre.pbeg[b]);
+  }
+  ++h->gen;      // d_gates2 changes content: plans made for it are stale
+  VQE_TRY(upload(h, h->d_gates2, pre.gates));
+  VQE_TRY(upload(h, h->d_gate_begin2, pre.gbeg));
+  VQE_TRY(upload(h, h->d_gate_count2, pre.gcnt));
+  VQE_TRY(upload(h, h->d_par_begin2, pre.pbeg));
+  VQE_TRY(upload(h, h->d_par_count2, pre.pcnt));
+  A2.gates = h->d_gates2.p; A2.gate_begin = h->d_gate_begin2.p; A2.gate_count = h->d_gate_count2.p;
+  A2.par_begin = h->d_par_begin2.p; A2.par_count = h->d_par_count2.p;
+  return VQE_OK;
+}
+
+// The end of a streaming env-step: pre.x0 holds the optima of the pre-action circuits.  They are merged into the full
+// parameter vectors (the new gate's angle keeps its theta0 value), raw to d_xraw and rounded to float32 to d_x, and the
+// full circuits are evaluated at the rounded angles (f of the env-step, d_f); nfev goes to d_nfev.
+int finish_env_step(vqe_t* h, BatchArgs& A, const PreActionBatch& pre, const std::vector<int32_t>& nfev, uint64_t eval_id) {
+  const int B = h->batch;
+  std::vector<double> xraw(h->h_theta), xr32(h->h_theta);
+  for (int b = 0; b < B; ++b) {
+    const int64_t p0 = h->h_par_begin[b];
+    merge_optimum(h->h_theta.data() + p0, h->h_par_count[b], pre.hole[b], pre.x0.data() + pre.pbeg[b], true, xr32.data() + p0, xraw.data() + p0);
+  }
+  if (h->total_params) {
+    HIP_TRY(h, hipMemcpyAsync(h->d_x.p, xr32.data(), xr32.size() * 8, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->d_xraw.p, xraw.data(), xraw.size() * 8, hipMemcpyHostToDevice, h->stream));
+  }
+  HIP_TRY(h, hipMemcpyAsync(h->d_nfev.p, nfev.data(), (size_t)B * 4, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));      // host vectors stay alive until the copies are done
+  A.theta = h->d_x.p;
+  return evaluate(h, A, eval_id, StreamWant::Both);
+}
+
 // Streaming path (n >= 14): kernels per op; the COBYLA loop runs all streams in lock-step (one batched
 // evaluation per iteration), its state on the device (stream_cobyla).
 int stream_run(vqe_t* h, Run mode, BatchArgs& A) {
@@ -517,46 +576,13 @@ int stream_run(vqe_t* h, Run mode, BatchArgs& A) {
     // Run::EnvStep: one CircuitEnv.step() per stream on the streaming path
     // (environment_qulacs_TN_notin_agent.py:283-291): host-driven COBYLA on the PRE-action circuits (pre_action,
     // vqe_geo.h; built by env_step_host.h), float32 round trip, then the full circuits.
-    const int B = h->batch;
-    std::vector<GateRec> g2;
-    std::vector<int64_t> gbeg2(B), pbeg2(B);
-    std::vector<int32_t> gcnt2(B), pcnt2(B), hole(B);
-    std::vector<double> x0;
-    g2.reserve(h->h_gates.size());
-    for (int b = 0; b < B; ++b) {
-      gbeg2[b] = (int64_t)g2.size();
-      pbeg2[b] = (int64_t)x0.size();
-      hole[b] = pre_action_circuit(h->h_gates.data() + h->h_gate_begin[b], h->h_gate_count[b],
-                                   h->has_new_gate ? h->h_new_gate[b] : -1, h->h_theta.data() + h->h_par_begin[b],
-                                   h->h_par_count[b], g2, x0).hole;
-      gcnt2[b] = (int32_t)((int64_t)g2.size() - gbeg2[b]);
-      pcnt2[b] = (int32_t)((int64_t)x0.size() - pbeg2[b]);
-    }
-    ++h->gen;      // d_gates2 changes content: plans made for it are stale
-    VQE_TRY(upload(h, h->d_gates2, g2));
-    VQE_TRY(upload(h, h->d_gate_begin2, gbeg2));
-    VQE_TRY(upload(h, h->d_gate_count2, gcnt2));
-    VQE_TRY(upload(h, h->d_par_begin2, pbeg2));
-    VQE_TRY(upload(h, h->d_par_count2, pcnt2));
+    PreActionBatch pre;
     BatchArgs A2 = A;
-    A2.gates = h->d_gates2.p; A2.gate_begin = h->d_gate_begin2.p; A2.gate_count = h->d_gate_count2.p;
-    A2.par_begin = h->d_par_begin2.p; A2.par_count = h->d_par_count2.p;
-    std::vector<double> f(B, 0.0);
-    std::vector<int32_t> nfev(B);
-    VQE_TRY(stream_cobyla(h, A2, pbeg2, pcnt2, x0, f, nfev, h->d_par_begin2.p, h->d_par_count2.p));
-    std::vector<double> xraw(h->h_theta), xr32(h->h_theta);
-    for (int b = 0; b < B; ++b) {
-      const int64_t p0 = h->h_par_begin[b];
-      merge_optimum(h->h_theta.data() + p0, h->h_par_count[b], hole[b], x0.data() + pbeg2[b], true, xr32.data() + p0, xraw.data() + p0);
-    }
-    if (h->total_params) {
-      HIP_TRY(h, hipMemcpyAsync(h->d_x.p, xr32.data(), xr32.size() * 8, hipMemcpyHostToDevice, h->stream));
-      HIP_TRY(h, hipMemcpyAsync(h->d_xraw.p, xraw.data(), xraw.size() * 8, hipMemcpyHostToDevice, h->stream));
-    }
-    HIP_TRY(h, hipMemcpyAsync(h->d_nfev.p, nfev.data(), (size_t)B * 4, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));      // host vectors stay alive until the copies are done
-    A.theta = h->d_x.p;
-    rc = evaluate(h, A, h->noise.eval_base + (uint64_t)A.maxfun + 1, StreamWant::Both);
+    VQE_TRY(load_pre_action_batch(h, pre, A2));
+    std::vector<double> f(h->batch, 0.0);
+    std::vector<int32_t> nfev(h->batch);
+    VQE_TRY(stream_cobyla(h, A2, pre.pbeg, pre.pcnt, pre.x0, f, nfev, h->d_par_begin2.p, h->d_par_count2.p));
+    rc = finish_env_step(h, A, pre, nfev, h->noise.eval_base + (uint64_t)A.maxfun + 1);
   }
   if (rc) return rc;
   HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
@@ -743,15 +769,19 @@ int build_grad_tables(vqe_t* h) {
 // What the adjoint kernels cannot serve: a gradient of a stochastic trajectory is of no use to an optimiser, and the
 // streaming path (n >= 14) computes gradients only after vqe_set_stream_grad (a second state-sized buffer per stream).
 // Checked before anything is loaded, so a refused call leaves the handle as it was.
-int grad_refusal(vqe_t* h) {
-  if (!h->lds_path && !h->stream_grad)
-    return fail(h, VQE_EINVAL, "energy gradients are computed for n_qubits <= 13 (LDS-resident path) only");
+// (grad_state_refusal: everything but the path test - the device L-BFGS has a switch of its own for n >= 14)
+int grad_state_refusal(vqe_t* h) {
   if (h->noise.p1 > 0.0 || h->noise.p2 > 0.0)
     return fail(h, VQE_ESTATE, "energy gradients of Pauli-noise trajectories are refused (set p1 = p2 = 0)");
   if (h->noise_mode == 1) return fail(h, VQE_ESTATE, "energy gradients are not available in the exact channel noise mode");
   if (h->noise.shot_sigma != 0.0) return fail(h, VQE_ESTATE, "energy gradients with shot noise are refused (set sigma_total = 0)");
   if (h->amp_world > 1) return fail(h, VQE_ESTATE, "energy gradients of an amplitude shard are refused");
   return VQE_OK;
+}
+int grad_refusal(vqe_t* h) {
+  if (!h->lds_path && !h->stream_grad)
+    return fail(h, VQE_EINVAL, "energy gradients are computed for n_qubits <= 13 (LDS-resident path) only");
+  return grad_state_refusal(h);
 }
 
 // The launch of the two adjoint kernels (the gradient, the device L-BFGS): both come as <N, LAM_GLOBAL> pairs that take
@@ -822,9 +852,10 @@ int lbfgs_check(vqe_t* h, const vqe_lbfgs_opts_t* opts, vqe_lbfgs_opts_t* o) {
   (void)vqe_lbfgs_default_opts(o);
   if (opts) *o = *opts;
   if (h->amp_world > 1) return fail(h, VQE_ESTATE, "the device L-BFGS takes no amplitude shard");      // (only n >= 14 can hold one)
-  if (!h->lds_path)      // (with or without vqe_set_stream_grad: the optimiser's kernel holds the state in the LDS)
-    return fail(h, VQE_EINVAL, "the device L-BFGS runs for n_qubits <= 13 (LDS-resident path) only");
-  VQE_TRY(grad_refusal(h));
+  if (!h->lds_path && !h->stream_lbfgs)      // (with or without vqe_set_stream_grad: the optimiser has a switch of its own)
+    return fail(h, VQE_EINVAL, "the device L-BFGS runs for n_qubits <= 13 (LDS-resident path) only; "
+                               "n_qubits >= 14 after vqe_set_stream_lbfgs");
+  VQE_TRY(grad_state_refusal(h));
   if (h->shard_world > 1)
     return fail(h, VQE_ESTATE, "term-sharded handles hold partial energies: the line search of the device L-BFGS needs the full energy");
   if (o->history < 1 || o->history > kLbfgsMaxHistory) return fail(h, VQE_EINVAL, "L-BFGS history must be in [1, 16]");
@@ -845,9 +876,93 @@ int launch_lbfgs(vqe_t* h, const BatchArgs& A, const LbfgsArgs& O) {
                            });
 }
 
+// The device L-BFGS of all resident streams in lock-step (vqe_stream_lbfgs.h), the shape of stream_cobyla: per
+// evaluation stream_energy_grad on the trial points (E into d_f, the gradient into d_grad), the running count zeroed,
+// k_sl_step - nothing travels between host and device and nothing is waited for, but for the running count every
+// kStreamPoll evaluations and at maxfun.  A: the batch to optimise (its par_begin / par_count lay out x); x: in x0, out
+// the result; nit / status stay on the device (lb_nit / lb_status).  The last launch is a gradient: the states are
+// the undone ones.
+int stream_lbfgs(vqe_t* h, BatchArgs& A, const vqe_lbfgs_opts_t& o, std::vector<double>& x, std::vector<double>& f,
+                 std::vector<int32_t>& nfev) {
+  const int B = h->batch;
+  const size_t PT = x.size();
+  HIP_TRY(h, h->d_x.reserve(PT + 1));
+  HIP_TRY(h, h->d_grad.reserve(PT + 1));
+  HIP_TRY(h, h->lb_work.reserve((size_t)B * lbfgs_work_doubles(A.max_params, o.history)));
+  HIP_TRY(h, h->lb_nit.reserve(B));
+  HIP_TRY(h, h->lb_status.reserve(B));
+  HIP_TRY(h, h->lb_rec.reserve(B));
+  HIP_TRY(h, h->lb_xres.reserve(PT + 1));
+  HIP_TRY(h, h->lb_fres.reserve(B));
+  HIP_TRY(h, h->lb_nfres.reserve(B));
+  HIP_TRY(h, h->lb_running.reserve(1));
+  // (trial points of streams that finish early stay where they are: the evaluations go on in lock-step over all streams)
+  if (PT) HIP_TRY(h, hipMemcpyAsync(h->d_x.p, x.data(), PT * 8, hipMemcpyHostToDevice, h->stream));
+  A.theta = h->d_x.p;
+  const StreamLbfgsArgs T{A.par_begin, A.par_count, A.max_params, h->lb_rec.p, h->d_x.p, h->d_f.p, h->d_grad.p,
+                          h->lb_running.p, h->lb_xres.p, h->lb_fres.p, h->lb_nfres.p};
+  const LbfgsArgs O{o.history, o.maxiter, o.maxfun, o.max_ls, o.gtol, o.ftol, o.c1, h->lb_work.p, h->lb_nit.p, h->lb_status.p};
+  h->stream_states_undone = true;
+  uint64_t it = 0;
+  int32_t running = 1;
+  while (running > 0) {
+    ++it;
+    VQE_TRY(stream_energy_grad(h->sw, A, h->stream, h->noise.eval_base + it, h->d_grad.p, h->err, h->gen));
+    HIP_TRY(h, hipMemsetAsync(h->lb_running.p, 0, 4, h->stream));
+    hipLaunchKernelGGL(it == 1 ? k_sl_step<true> : k_sl_step<false>, dim3((unsigned)B), dim3(64), 0, h->stream, T, O);
+    if (it % kStreamPoll == 0 || it >= (uint64_t)o.maxfun) {
+      HIP_TRY(h, hipMemcpyAsync(&running, h->lb_running.p, 4, hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(h, hipStreamSynchronize(h->stream));
+    }
+    if (it > (uint64_t)o.maxfun + kStreamPoll) return fail(h, VQE_ESTATE, "device L-BFGS did not terminate");
+  }
+  HIP_TRY(h, hipGetLastError());
+  if (PT) HIP_TRY(h, hipMemcpyAsync(x.data(), h->lb_xres.p, PT * 8, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(f.data(), h->lb_fres.p, (size_t)B * 8, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(nfev.data(), h->lb_nfres.p, (size_t)B * 4, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return VQE_OK;
+}
+
+// run_lbfgs on the streaming path (n >= 14, vqe_set_stream_lbfgs).  env_step: the rule of the streaming Run::EnvStep with
+// the L-BFGS in COBYLA's place - pre-action circuits built on the host (the kernel knows no hole), float32 round trip,
+// one evaluation of the full circuits.
+int stream_run_lbfgs(vqe_t* h, bool env_step, const vqe_lbfgs_opts_t& o) {
+  BatchArgs A = make_args(h);
+  A.maxfun = o.maxfun;
+  const int B = h->batch;
+  h->last_run_dm = false;
+  h->lb_batch = 0;
+  std::vector<double> f(B, 0.0);
+  std::vector<int32_t> nfev(B);
+  HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
+  if (!env_step) {
+    std::vector<double> x(h->h_theta);
+    VQE_TRY(stream_lbfgs(h, A, o, x, f, nfev));
+    if (h->total_params) {
+      HIP_TRY(h, hipMemcpyAsync(h->d_x.p, x.data(), x.size() * 8, hipMemcpyHostToDevice, h->stream));
+      HIP_TRY(h, hipMemcpyAsync(h->d_xraw.p, x.data(), x.size() * 8, hipMemcpyHostToDevice, h->stream));
+    }
+    HIP_TRY(h, hipMemcpyAsync(h->d_f.p, f.data(), (size_t)B * 8, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->d_nfev.p, nfev.data(), (size_t)B * 4, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+  } else {
+    PreActionBatch pre;
+    BatchArgs A2 = A;
+    VQE_TRY(load_pre_action_batch(h, pre, A2));
+    VQE_TRY(stream_lbfgs(h, A2, o, pre.x0, f, nfev));
+    VQE_TRY(finish_env_step(h, A, pre, nfev, h->noise.eval_base + (uint64_t)o.maxfun + 1));
+    h->stream_states_undone = false;      // (the last launch was an energy: the states are those of the full circuits)
+  }
+  HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
+  h->lb_batch = B;
+  return VQE_OK;
+}
+
 // o: options that passed lbfgs_check
 int run_lbfgs(vqe_t* h, bool env_step, const vqe_lbfgs_opts_t& o) {
   HIP_TRY(h, hipSetDevice(h->dev));
+  if (!h->lds_path) return stream_run_lbfgs(h, env_step, o);
   VQE_TRY(build_grad_tables(h));
   BatchArgs A = make_args(h);
   A.maxfun = o.maxfun;
@@ -1163,6 +1278,12 @@ int vqe_set_amplitude_shard(vqe_t* h, int rank, int world) {
 int vqe_set_stream_grad(vqe_t* h, int enable) {
   if (!h) return VQE_EINVAL;
   h->stream_grad = enable != 0;      // (n <= 13: the LDS-resident kernel serves every gradient; nothing to switch)
+  return VQE_OK;
+}
+
+int vqe_set_stream_lbfgs(vqe_t* h, int enable) {
+  if (!h) return VQE_EINVAL;
+  h->stream_lbfgs = enable != 0;     // (n <= 13: k_lds_minimize_lbfgs serves every run; nothing to switch)
   return VQE_OK;
 }
 

@@ -193,6 +193,13 @@ class VQEEngine:
         n <= 13."""
         self._chk(self._lib.vqe_set_stream_grad(self._h, 1 if enable else 0))
 
+    def set_stream_lbfgs(self, enable: bool = True):
+        """n >= 14: let minimize_lbfgs / batch_run_minimize_lbfgs / batch_run_env_step_lbfgs run on the streaming path
+        (all resident streams in lock-step, one adjoint gradient per evaluation; one more state-sized buffer per
+        resident stream).  Off by default: those calls then raise at n >= 14, whatever set_stream_grad says.  No
+        effect at n <= 13."""
+        self._chk(self._lib.vqe_set_stream_lbfgs(self._h, 1 if enable else 0))
+
     def set_noise(self, p1: float, p2: float, seed: int):
         self._chk(self._lib.vqe_set_noise(self._h, float(p1), float(p2), C.c_uint64(int(seed) & (2 ** 64 - 1))))
 

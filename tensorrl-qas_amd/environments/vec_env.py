@@ -78,7 +78,7 @@ class VecCircuitEnv:
     """``device_optimizer``: the optimiser of every step's fused launch, a property of the batch and not of the
     reference's config file - "cobyla" (default: batch_run_env_step, the config's optim_alg = COBYLA) or "lbfgs"
     (batch_run_env_step_lbfgs: the device L-BFGS on adjoint gradients, noiseless configurations only; NOT scipy's
-    L-BFGS-B).  ``lbfgs_opts``: options of VQEEngine.lbfgs_opts; ``maxfun`` defaults to the config's global_iters so
+    L-BFGS-B; at 14 qubits and more the engine's set_stream_lbfgs is switched on for it).  ``lbfgs_opts``: options of VQEEngine.lbfgs_opts; ``maxfun`` defaults to the config's global_iters so
     that nfev stays comparable with COBYLA's budget."""
 
     def __init__(self, env_cls, conf, device, num_envs: int, seed: int = 0, native: bool | None = None,
@@ -101,6 +101,8 @@ class VecCircuitEnv:
                                           "finite-shot configurations are served by the device COBYLA")
             self._lbfgs_opts = {"maxfun": int(first.global_iters), **(lbfgs_opts or {})}
         self.engine = first.engine
+        if device_optimizer == "lbfgs" and first.num_qubits >= 14:
+            self.engine.set_stream_lbfgs(True)           # the streaming path runs the device L-BFGS on request only
         self._proto = first
         self.num_envs = num_envs
         self.device = device

@@ -142,9 +142,27 @@ int vqe_set_noise(vqe_t* h, double p1, double p2, uint64_t seed);
  * from - density-matrix evolution rho -> (1-p) rho + p/3 sum_P P rho P (two qubits: p/15 over the 15 non-identity
  * Paulis), E = tr(rho H); 2 <= n <= 13 (4^n complex128 in HBM), runs of gates inside a two-qubit window fused into
  * 16 x 16 superoperators applied with FP64 MFMA; vqe_energy*, vqe_batch_run_energy, vqe_minimize_cobyla,
- * vqe_batch_run_minimize / _env_step (COBYLA then driven by the host on the exact energies).  The seed of
- * vqe_set_noise and vqe_set_shot_noise play no part in mode 1. */
+ * vqe_batch_run_minimize / _env_step.  By default COBYLA is driven by the host on the exact energies, one circuit and
+ * one evaluation at a time; after vqe_set_dm_batched the resident batch is evaluated in lock-step and COBYLA runs on
+ * the device.  The seed of vqe_set_noise and vqe_set_shot_noise play no part in mode 1. */
 int vqe_set_noise_mode(vqe_t* h, int mode);
+/* Exact channel mode only: evaluate the resident batch in lock-step on the device.
+ * max_resident  0 (default): the serial host-driven path, as before.
+ *              -1: as many density matrices resident as fit into a quarter of the free device
+ *                  memory at the first batched run (at least 1, at most the batch);
+ *             R>=1: at most R.
+ * Accepted in any noise mode and for any n; it takes effect when mode 1 runs (2 <= n <= 13 as before).  The block
+ * structure of every circuit is planned once per resident batch, the 16 x 16 matrices are rebuilt on the device for
+ * every trial point, all circuits of a chunk of R sweep side by side and COBYLA of vqe_minimize_cobyla /
+ * vqe_batch_run_minimize / _env_step runs on the device (one thread per circuit, the host build's arithmetic).  The
+ * energy of a circuit has the same bits whatever the batch around it, its position and R; the bits of the serial path
+ * are not promised (the device-built matrices may differ from the host-built ones in the last place). */
+int vqe_set_dm_batched(vqe_t* h, int max_resident);
+/* out[0] density matrices resident per chunk in the last batched run, [1] chunks per lock-step
+ * evaluation, [2] lock-step evaluations of the last run that evaluated at least one circuit (1 for an energy run; the
+ * largest nfev of a minimisation, one more for an env-step), [3] block levels (sweeps per chunk and evaluation: the
+ * largest block count of a resident circuit).  All 0 after a serial run. */
+int vqe_dm_batch_info(vqe_t* h, int64_t out[4]);
 /* host only (needs no device): the superoperator blocks the exact channel mode would sweep for this circuit - windows[2k],
  * windows[2k+1] = the two qubits (a, b) of block k, S[k][2][16][16] = real and imaginary part of its 16 x 16 matrix, entry
  * index = ket_a + 2 ket_b + 4 bra_a + 8 bra_b.  windows == NULL or S == NULL: only the count.  For tests of the fusion. */

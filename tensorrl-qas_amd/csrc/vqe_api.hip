@@ -5,6 +5,7 @@
 #include "vqe_devbuf.h"
 #include "vqe_stream.h"
 #include "vqe_dm.h"
+#include "vqe_dm_batch.h"
 #include "vqe_grad.h"
 #include "vqe_lbfgs.h"
 #include "vqe_stream_lbfgs.h"
@@ -32,6 +33,17 @@ namespace {
 
 std::string g_create_error;
 }  // namespace
+
+// The plan of one resident batch on the batched exact channel path (dm_host.h: DmBatchTables) on the device, with the
+// matrices k_dm_build fills; made for the batch / noise setting of handle generation `gen`.
+struct DmPlanSlot {
+  uint64_t gen = ~0ull;
+  DevBuf<int32_t> blk_begin, blk_circ, blk_win, mem_begin, mem;
+  DevBuf<double> dep, S;
+  std::vector<int32_t> h_blk_begin;
+  int n_blocks = 0, max_blocks = 0;
+  DmBatchDev dev{};
+};
 
 struct vqe_handle {
   int n = 0, dev = 0;
@@ -100,6 +112,14 @@ struct vqe_handle {
   bool last_run_dm = false;
   hipEvent_t dm_ev0 = nullptr, dm_ev1 = nullptr;
   uint64_t dm_ham_gen = ~0ull;
+  // batched lock-step form of the exact channel mode (vqe_set_dm_batched, vqe_dm_batch.h): the resident density matrices
+  // of a chunk, the partials of their energies, the plans of the resident batch and of an env-step's pre-action batch
+  int dm_batched = 0;          // max_resident: 0 serial path, -1 a quarter of the free memory, R >= 1
+  size_t dm_auto_cap = 0;      // -1: the density matrices that fit, fixed at the first batched run
+  int64_t dm_info[4] = {0, 0, 0, 0};
+  DevBufExact<double2> dmb_rho;
+  DevBuf<double> dmb_partial;
+  DmPlanSlot dmb_full, dmb_pre;
   DevBuf<double> d_cob_x0, d_cob_xres, d_cob_f;      // device-resident lock-step COBYLA of the streaming path
   DevBuf<int32_t> d_cob_nfev, d_cob_active;
   void* comm = nullptr;      // RCCL communicator of vqe_comm_init (ncclComm_t)
@@ -441,12 +461,13 @@ int stream_cobyla_host(vqe_t* h, BatchArgs& A, const std::vector<int64_t>& pbeg,
   return VQE_OK;
 }
 
-// d_pbeg / d_pcnt: the device copies of pbeg / pcnt (the batch that A describes)
-int stream_cobyla(vqe_t* h, BatchArgs& A, const std::vector<int64_t>& pbeg, const std::vector<int32_t>& pcnt,
-                  std::vector<double>& x, std::vector<double>& f, std::vector<int32_t>& nfev,
-                  const int64_t* d_pbeg, const int32_t* d_pcnt) {
-  static const bool host_loop = [] { const char* e = std::getenv("VQE_STREAM_HOST_COBYLA"); return e && e[0] == '1'; }();
-  if (host_loop) return stream_cobyla_host(h, A, pbeg, pcnt, x, f, nfev);
+// d_pbeg / d_pcnt: the device copies of pbeg / pcnt (the batch that A describes).
+// eval(A, it, active): queue the it-th batched evaluation (it = 1, 2, ...) of the trial points A.theta into d_f;
+// active[b] != 0 for the streams whose optimiser waits for that value - an evaluation may skip the others (the batched
+// exact channel mode does, the streaming path evaluates all of them).
+template <class Eval>
+int lockstep_cobyla(vqe_t* h, BatchArgs& A, std::vector<double>& x, std::vector<double>& f, std::vector<int32_t>& nfev,
+                    const int64_t* d_pbeg, const int32_t* d_pcnt, Eval eval) {
   const int B = h->batch;
   const size_t PT = x.size();
   HIP_TRY(h, h->d_x.reserve(PT + 1));
@@ -473,7 +494,7 @@ int stream_cobyla(vqe_t* h, BatchArgs& A, const std::vector<int64_t>& pbeg, cons
   uint64_t it = 0;
   int32_t running = 1;
   while (running > 0) {
-    VQE_TRY(evaluate(h, A, h->noise.eval_base + (++it), StreamWant::Both));
+    VQE_TRY(eval(A, ++it, (const int32_t*)h->d_cob_active.p));
     VQE_TRY(cobyla_step(false));
     if (it % kStreamPoll == 0 || it >= (uint64_t)A.maxfun) {
       HIP_TRY(h, hipMemcpyAsync(&running, n_active, 4, hipMemcpyDeviceToHost, h->stream));
@@ -487,6 +508,17 @@ int stream_cobyla(vqe_t* h, BatchArgs& A, const std::vector<int64_t>& pbeg, cons
   HIP_TRY(h, hipMemcpyAsync(nfev.data(), h->d_cob_nfev.p, (size_t)B * 4, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   return VQE_OK;
+}
+
+// the streaming path's lock-step COBYLA: every evaluation is stream_evaluate on all streams
+int stream_cobyla(vqe_t* h, BatchArgs& A, const std::vector<int64_t>& pbeg, const std::vector<int32_t>& pcnt,
+                  std::vector<double>& x, std::vector<double>& f, std::vector<int32_t>& nfev,
+                  const int64_t* d_pbeg, const int32_t* d_pcnt) {
+  static const bool host_loop = [] { const char* e = std::getenv("VQE_STREAM_HOST_COBYLA"); return e && e[0] == '1'; }();
+  if (host_loop) return stream_cobyla_host(h, A, pbeg, pcnt, x, f, nfev);
+  return lockstep_cobyla(h, A, x, f, nfev, d_pbeg, d_pcnt, [h](const BatchArgs& a, uint64_t it, const int32_t*) {
+    return evaluate(h, a, h->noise.eval_base + it, StreamWant::Both);
+  });
 }
 
 // The pre-action circuits of a streaming env-step (pre_action, vqe_geo.h; built by env_step_host.h) as a second
@@ -524,7 +556,9 @@ int load_pre_action_batch(vqe_t* h, PreActionBatch& pre, BatchArgs& A2) {
 // The end of a streaming env-step: pre.x0 holds the optima of the pre-action circuits.  They are merged into the full
 // parameter vectors (the new gate's angle keeps its theta0 value), raw to d_xraw and rounded to float32 to d_x, and the
 // full circuits are evaluated at the rounded angles (f of the env-step, d_f); nfev goes to d_nfev.
-int finish_env_step(vqe_t* h, BatchArgs& A, const PreActionBatch& pre, const std::vector<int32_t>& nfev, uint64_t eval_id) {
+// eval(A): queue the evaluation of the batch that A describes at A.theta into d_f.
+template <class Eval>
+int finish_env_step(vqe_t* h, BatchArgs& A, const PreActionBatch& pre, const std::vector<int32_t>& nfev, Eval eval) {
   const int B = h->batch;
   std::vector<double> xraw(h->h_theta), xr32(h->h_theta);
   for (int b = 0; b < B; ++b) {
@@ -538,7 +572,7 @@ int finish_env_step(vqe_t* h, BatchArgs& A, const PreActionBatch& pre, const std
   HIP_TRY(h, hipMemcpyAsync(h->d_nfev.p, nfev.data(), (size_t)B * 4, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));      // host vectors stay alive until the copies are done
   A.theta = h->d_x.p;
-  return evaluate(h, A, eval_id, StreamWant::Both);
+  return eval(A);
 }
 
 // Streaming path (n >= 14): kernels per op; the COBYLA loop runs all streams in lock-step (one batched
@@ -582,7 +616,9 @@ int stream_run(vqe_t* h, Run mode, BatchArgs& A) {
     std::vector<double> f(h->batch, 0.0);
     std::vector<int32_t> nfev(h->batch);
     VQE_TRY(stream_cobyla(h, A2, pre.pbeg, pre.pcnt, pre.x0, f, nfev, h->d_par_begin2.p, h->d_par_count2.p));
-    rc = finish_env_step(h, A, pre, nfev, h->noise.eval_base + (uint64_t)A.maxfun + 1);
+    rc = finish_env_step(h, A, pre, nfev, [h](const BatchArgs& a) {
+      return evaluate(h, a, h->noise.eval_base + (uint64_t)a.maxfun + 1, StreamWant::Both);
+    });
   }
   if (rc) return rc;
   HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
@@ -660,8 +696,131 @@ int dm_energy_one(vqe_t* h, const GateRec* g, int G, const double* theta, double
   return VQE_OK;
 }
 
+// ---- the batched lock-step form (vqe_set_dm_batched; kernels: vqe_dm_batch.h) --------
+
+// The plan of the batch (gates, gbeg, gcnt) in slot P, made once per handle generation.
+int dm_batch_plan(vqe_t* h, DmPlanSlot& P, const std::vector<GateRec>& gates, const std::vector<int64_t>& gbeg,
+                  const std::vector<int32_t>& gcnt) {
+  if (P.gen == h->gen) return VQE_OK;
+  DmBatchTables T;
+  dm_flatten_plans(h->n, h->batch, gates.data(), gbeg.data(), gcnt.data(), h->noise.p1, h->noise.p2, T);
+  VQE_TRY(upload(h, P.blk_begin, T.blk_begin));
+  VQE_TRY(upload(h, P.blk_circ, T.blk_circ));
+  VQE_TRY(upload(h, P.blk_win, T.blk_win));
+  VQE_TRY(upload(h, P.mem_begin, T.mem_begin));
+  VQE_TRY(upload(h, P.mem, T.mem));
+  VQE_TRY(upload(h, P.dep, T.dep));
+  P.n_blocks = (int)T.blk_circ.size();
+  P.max_blocks = T.max_blocks;
+  HIP_TRY(h, P.S.reserve((size_t)std::max(1, P.n_blocks) * 512));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));      // the tables go out of scope
+  P.h_blk_begin = std::move(T.blk_begin);
+  P.dev = DmBatchDev{P.blk_begin.p, P.blk_circ.p, P.blk_win.p, P.mem_begin.p, P.mem.p, P.dep.p, P.S.p};
+  P.gen = h->gen;
+  return VQE_OK;
+}
+
+// The resident density matrices R of this run and their buffers; info[0], [1].
+int dm_batch_reserve(vqe_t* h) {
+  const size_t total = (size_t)1 << (2 * h->n);
+  if (h->dm_batched < 0 && !h->dm_auto_cap) {
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(h, hipMemGetInfo(&free_b, &total_b));
+    h->dm_auto_cap = std::max<size_t>(1, (free_b / 4) / (total * sizeof(double2)));
+  }
+  const size_t cap = h->dm_batched > 0 ? (size_t)h->dm_batched : h->dm_auto_cap;
+  const int R = (int)std::min<size_t>(std::min<size_t>(cap, (size_t)h->batch), 65535);      // a chunk is the y extent of a grid
+  const size_t eb = (((size_t)1 << h->n) + 255) / 256;
+  HIP_TRY(h, h->dmb_rho.reserve((size_t)R * total));
+  HIP_TRY(h, h->dmb_partial.reserve((size_t)R * eb));
+  h->dm_info[0] = R;
+  h->dm_info[1] = (h->batch + R - 1) / R;
+  return VQE_OK;
+}
+
+// One lock-step evaluation: the circuits of plan P (the batch A describes) at A.theta, tr(rho H) into A.fout[b] for
+// every active circuit.  Queued on the handle's stream; nothing is copied back.
+int dm_batch_eval(vqe_t* h, const DmPlanSlot& P, const BatchArgs& A, const int32_t* active) {
+  const int n = h->n, B = h->batch, R = (int)h->dm_info[0];
+  const size_t total = (size_t)1 << (2 * n);
+  const uint32_t n_groups = (uint32_t)(total / 16);
+  const size_t tiles = ((size_t)n_groups + 15) / 16;
+  const unsigned eb = (unsigned)((((size_t)1 << n) + 255) / 256);
+  if (P.n_blocks)
+    hipLaunchKernelGGL(k_dm_build, dim3((unsigned)P.n_blocks), dim3(256), 0, h->stream, P.dev, (const double*)A.theta,
+                       (const int64_t*)A.par_begin, active);
+  for (int c0 = 0; c0 < B; c0 += R) {
+    const int cnt = std::min(R, B - c0);
+    int levels = 0;
+    for (int b = c0; b < c0 + cnt; ++b) levels = std::max(levels, P.h_blk_begin[b + 1] - P.h_blk_begin[b]);
+    // workgroups per circuit: what the serial path launches for one circuit, shared out when the chunk fills the device
+    const size_t share = (size_t)h->cu_count * 16 / (size_t)cnt;
+    const unsigned gi = (unsigned)std::max<size_t>(1, std::min<size_t>((total + 255) / 256, std::max<size_t>(8, share)));
+    const unsigned gb = (unsigned)std::max<size_t>(1, std::min<size_t>((tiles + 3) / 4, std::max<size_t>(8, share / 2)));
+    hipLaunchKernelGGL(k_dm_init_b, dim3(gi, (unsigned)cnt), dim3(256), 0, h->stream, h->dmb_rho.p, (const double2*)h->init.p, n, c0, active);
+    for (int l = 0; l < levels; ++l)
+      hipLaunchKernelGGL(k_dm_block_b, dim3(gb, (unsigned)cnt), dim3(256), 0, h->stream, h->dmb_rho.p, P.dev, n, n_groups, l, c0, active);
+    hipLaunchKernelGGL(k_dm_energy_b, dim3(eb, (unsigned)cnt), dim3(256), 0, h->stream, (const double2*)h->dmb_rho.p, n, h->dm_groups,
+                       (const uint32_t*)h->dm_gx.p, (const int32_t*)h->dm_toff.p, (const uint32_t*)h->dm_tz.p,
+                       (const double*)h->dm_cr.p, (const double*)h->dm_ci.p, h->dmb_partial.p, c0, active);
+    hipLaunchKernelGGL(k_dm_sum_b, dim3((unsigned)((cnt + 63) / 64)), dim3(64), 0, h->stream, (const double*)h->dmb_partial.p, (int)eb,
+                       cnt, c0, active, A.fout);
+  }
+  HIP_TRY(h, hipGetLastError());
+  return VQE_OK;
+}
+
+// Run::Energy / Minimize / EnvStep of the batched path, in the shape of stream_run's branches: the optimiser of every
+// circuit lives on the device (k_s_cobyla through lockstep_cobyla), an evaluation is dm_batch_eval.
+int dm_run_batched(vqe_t* h, Run mode, BatchArgs A) {
+  const int B = h->batch;
+  VQE_TRY(dm_batch_reserve(h));
+  HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
+  int64_t evals = 1;
+  if (mode == Run::Energy) {
+    VQE_TRY(dm_batch_plan(h, h->dmb_full, h->h_gates, h->h_gate_begin, h->h_gate_count));
+    VQE_TRY(dm_batch_eval(h, h->dmb_full, A, nullptr));
+  } else if (mode == Run::Minimize) {
+    VQE_TRY(dm_batch_plan(h, h->dmb_full, h->h_gates, h->h_gate_begin, h->h_gate_count));
+    std::vector<double> x(h->h_theta), f(B, 0.0);
+    std::vector<int32_t> nfev(B);
+    VQE_TRY(lockstep_cobyla(h, A, x, f, nfev, h->d_par_begin.p, h->d_par_count.p, [h](const BatchArgs& a, uint64_t, const int32_t* active) {
+      return dm_batch_eval(h, h->dmb_full, a, active);
+    }));
+    if (h->total_params) {
+      HIP_TRY(h, hipMemcpyAsync(h->d_x.p, x.data(), x.size() * 8, hipMemcpyHostToDevice, h->stream));
+      HIP_TRY(h, hipMemcpyAsync(h->d_xraw.p, x.data(), x.size() * 8, hipMemcpyHostToDevice, h->stream));
+    }
+    HIP_TRY(h, hipMemcpyAsync(h->d_f.p, f.data(), (size_t)B * 8, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->d_nfev.p, nfev.data(), (size_t)B * 4, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    evals = *std::max_element(nfev.begin(), nfev.end());
+  } else {
+    // Run::EnvStep: COBYLA on the pre-action circuits (a second resident batch with a plan of its own), float32 round
+    // trip, one evaluation of the full circuits
+    PreActionBatch pre;
+    BatchArgs A2 = A;
+    VQE_TRY(load_pre_action_batch(h, pre, A2));
+    VQE_TRY(dm_batch_plan(h, h->dmb_pre, pre.gates, pre.gbeg, pre.gcnt));
+    std::vector<double> f(B, 0.0);
+    std::vector<int32_t> nfev(B);
+    VQE_TRY(lockstep_cobyla(h, A2, pre.x0, f, nfev, h->d_par_begin2.p, h->d_par_count2.p, [h](const BatchArgs& a, uint64_t, const int32_t* active) {
+      return dm_batch_eval(h, h->dmb_pre, a, active);
+    }));
+    VQE_TRY(dm_batch_plan(h, h->dmb_full, h->h_gates, h->h_gate_begin, h->h_gate_count));
+    VQE_TRY(finish_env_step(h, A, pre, nfev, [h](const BatchArgs& a) { return dm_batch_eval(h, h->dmb_full, a, nullptr); }));
+    evals = *std::max_element(nfev.begin(), nfev.end()) + 1;
+  }
+  HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
+  h->dm_info[2] = evals;
+  h->dm_info[3] = h->dmb_full.max_blocks;
+  h->dm_blocks_last = h->dmb_full.max_blocks;
+  return VQE_OK;
+}
+
 // The resident batch in exact channel mode: Run::Energy, or COBYLA (host-driven on exact energies; Run::EnvStep: on the
-// pre-action circuit, then float32 round trip and the energy of the full circuit, as the fused kernel does).
+// pre-action circuit, then float32 round trip and the energy of the full circuit, as the fused kernel does).  After
+// vqe_set_dm_batched: dm_run_batched, behind the same refusals.
 int dm_run(vqe_t* h, Run mode, const BatchArgs& A) {
   if (h->n < 2 || h->n > 13) return fail(h, VQE_EINVAL, "the exact channel mode (density matrix) serves 2 <= n_qubits <= 13");
   // the superoperator blocks (dm_host.h) are built from CNOT, RX, RY, RZ and the two channels only: refused before anything is launched
@@ -671,6 +830,8 @@ int dm_run(vqe_t* h, Run mode, const BatchArgs& A) {
         return fail(h, VQE_EINVAL, "the exact channel mode does not take RXX / RYY / RZZ gates (use Pauli-trajectory noise, vqe_set_noise_mode 0)");
   if (h->amp_world > 1) return fail(h, VQE_ESTATE, "the exact channel mode has no amplitude sharding");
   VQE_TRY(dm_prepare_ham(h));
+  std::fill(h->dm_info, h->dm_info + 4, (int64_t)0);
+  if (h->dm_batched != 0) return dm_run_batched(h, mode, A);
   HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
   h->dm_gpu_ms = 0.f;
   h->last_run_dm = true;
@@ -951,7 +1112,8 @@ int stream_run_lbfgs(vqe_t* h, bool env_step, const vqe_lbfgs_opts_t& o) {
     BatchArgs A2 = A;
     VQE_TRY(load_pre_action_batch(h, pre, A2));
     VQE_TRY(stream_lbfgs(h, A2, o, pre.x0, f, nfev));
-    VQE_TRY(finish_env_step(h, A, pre, nfev, h->noise.eval_base + (uint64_t)o.maxfun + 1));
+    const uint64_t eval_id = h->noise.eval_base + (uint64_t)o.maxfun + 1;
+    VQE_TRY(finish_env_step(h, A, pre, nfev, [h, eval_id](const BatchArgs& a) { return evaluate(h, a, eval_id, StreamWant::Both); }));
     h->stream_states_undone = false;      // (the last launch was an energy: the states are those of the full circuits)
   }
   HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
@@ -1300,6 +1462,20 @@ int vqe_set_noise_mode(vqe_t* h, int mode) {
   if (mode != 0 && mode != 1) return fail(h, VQE_EINVAL, "noise mode: 0 (Pauli trajectories) or 1 (exact channel)");
   if (mode == 1 && (h->n < 2 || h->n > 13)) return fail(h, VQE_EINVAL, "the exact channel mode (density matrix) serves 2 <= n_qubits <= 13");
   h->noise_mode = mode;
+  return VQE_OK;
+}
+
+int vqe_set_dm_batched(vqe_t* h, int max_resident) {
+  if (!h) return VQE_EINVAL;
+  if (max_resident < -1) return fail(h, VQE_EINVAL, "max_resident: 0 (serial path), -1 (a quarter of the free device memory) or R >= 1");
+  h->dm_batched = max_resident;
+  h->dm_auto_cap = 0;
+  return VQE_OK;
+}
+
+int vqe_dm_batch_info(vqe_t* h, int64_t out[4]) {
+  if (!h || !out) return VQE_EINVAL;
+  std::copy(h->dm_info, h->dm_info + 4, out);
   return VQE_OK;
 }
 

@@ -212,6 +212,19 @@ class VQEEngine:
         self._chk(self._lib.vqe_noise_mode_info(self._h, out))
         return {"mode": out[0], "blocks_last_evaluation": out[1]}
 
+    def set_dm_batched(self, max_resident: int = -1):
+        """Exact channel mode (set_noise_mode(1)): evaluate the resident batch in lock-step on the device, COBYLA of
+        minimize_cobyla / batch_run_minimize / batch_run_env_step on the device too.  ``max_resident``: density matrices
+        held at a time - 0 the serial host-driven path (default of a new engine), -1 what fits a quarter of the free
+        device memory, R >= 1 at most R (a batch larger than that is evaluated in chunks)."""
+        self._chk(self._lib.vqe_set_dm_batched(self._h, int(max_resident)))
+
+    def dm_batch_info(self):
+        """The last batched exact-channel run (all 0 after a serial one)."""
+        out = (C.c_int64 * 4)()
+        self._chk(self._lib.vqe_dm_batch_info(self._h, out))
+        return {"resident": out[0], "chunks": out[1], "evaluations": out[2], "levels": out[3]}
+
     def set_shot_noise(self, sigma_total: float, seed: int):
         self._chk(self._lib.vqe_set_shot_noise(self._h, float(sigma_total), C.c_uint64(int(seed) & (2 ** 64 - 1))))
 

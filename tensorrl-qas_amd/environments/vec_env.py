@@ -79,16 +79,24 @@ class VecCircuitEnv:
     reference's config file - "cobyla" (default: batch_run_env_step, the config's optim_alg = COBYLA) or "lbfgs"
     (batch_run_env_step_lbfgs: the device L-BFGS on adjoint gradients, noiseless configurations only; NOT scipy's
     L-BFGS-B; at 14 qubits and more the engine's set_stream_lbfgs is switched on for it).  ``lbfgs_opts``: options of VQEEngine.lbfgs_opts; ``maxfun`` defaults to the config's global_iters so
-    that nfev stays comparable with COBYLA's budget."""
+    that nfev stays comparable with COBYLA's budget.
+    ``noise_channel``: how the noisy environment classes evaluate their depolarising channels - "trajectory" (default:
+    one Pauli trajectory per evaluation, as the reference's qulacs circuits do) or "exact" (the channel those draws
+    sample from: the engine's exact channel mode on the batched lock-step path, set_noise_mode(1) + set_dm_batched(-1);
+    deterministic energies, 2 <= n <= 13)."""
 
     def __init__(self, env_cls, conf, device, num_envs: int, seed: int = 0, native: bool | None = None,
-                 device_optimizer: str = "cobyla", lbfgs_opts: dict | None = None):
+                 device_optimizer: str = "cobyla", lbfgs_opts: dict | None = None, noise_channel: str = "trajectory"):
         if not issubclass(env_cls, CircuitEnvBase):
             raise TypeError("env_cls must be one of the CircuitEnv classes of this package")
         if device_optimizer not in ("cobyla", "lbfgs"):
             raise ValueError('device_optimizer must be "cobyla" or "lbfgs"')
         if lbfgs_opts is not None and device_optimizer != "lbfgs":
             raise ValueError('lbfgs_opts needs device_optimizer = "lbfgs"')
+        if noise_channel not in ("trajectory", "exact"):
+            raise ValueError('noise_channel must be "trajectory" or "exact"')
+        if noise_channel == "exact" and not getattr(env_cls, "NOISY", False):
+            raise ValueError('noise_channel = "exact" is for the noisy environment classes (Pauli noise behind every gate)')
         first = env_cls(conf, device, seed=seed)
         if first.optimizer_kind not in (None, "device_cobyla"):
             raise NotImplementedError(f"VecCircuitEnv runs the device COBYLA of batch_run_env_step only; optim_alg = "
@@ -101,6 +109,10 @@ class VecCircuitEnv:
                                           "finite-shot configurations are served by the device COBYLA")
             self._lbfgs_opts = {"maxfun": int(first.global_iters), **(lbfgs_opts or {})}
         self.engine = first.engine
+        self.noise_channel = noise_channel
+        if noise_channel == "exact":
+            self.engine.set_noise_mode(1)
+            self.engine.set_dm_batched(-1)
         if device_optimizer == "lbfgs" and first.num_qubits >= 14:
             self.engine.set_stream_lbfgs(True)           # the streaming path runs the device L-BFGS on request only
         self._proto = first

@@ -101,6 +101,30 @@ int vqe_hamiltonian_terms(vqe_t* h, int32_t* n_terms, int32_t* n_xgroups);
  * if there is a diagonal group.  The reference has no counterpart: its get_exp_val multiplies
  * by the dense matrix (VQE_qulacs_TN_notin_RL.py:86). */
 int vqe_hamiltonian_layout(vqe_t* h, int32_t out[4]);
+/* Where the device COBYLA of the LDS-resident kernels (n <= 13) keeps its arrays for ONE circuit, and which of its
+ * update contexts runs (diagnostic, for tests that must know which code path a circuit took; the answer comes from
+ * the function the kernel itself calls).  It depends on the sizes of the whole resident batch - max_ops (rotations and
+ * noise ops of the longest circuit), max_pair (its RX / RY / RXX / RYY gates), max_params, each as the library rounds
+ * them up to a multiple of 4 -, on the X-mask groups of the Hamiltonian, on whether the launch is the variant for
+ * batches with a circuit of more than 64 parameters (wide), and on the circuit's own parameter count n_params:
+ *   out[0] class: VQE_COBYLA_RESIDENT an LDS region of their own (n <= 9 and the workgroup still fits eight times into
+ *          a CU); _STAGED copied into the idle state region of LDS around every update; _GLOBAL in the global scratch,
+ *          one wavefront, one lane per row; _ROWS the same with row walks through an LDS tile (wide launches at n <= 9,
+ *          more than 32 parameters); _BLOCK in the global scratch, updated by the whole workgroup (wide launches at
+ *          n >= 10, more than 64 parameters)
+ *   out[1] padding of the inner loops (8 or 16), out[2] doubles the arrays take in that layout,
+ *   out[3] dynamic LDS bytes of the launch, out[4] 1 if two lanes share a row (at most 32 parameters, one-wave contexts),
+ *   out[5] bytes of the LDS tile of the one-wave wide launch (0 in every other launch), out[6] bytes of the LDS region of class
+ *   RESIDENT (else 0), out[7] 1 if the launch is accepted (LDS within 160 KiB - the handle variant: within the
+ *   device's figure -, at most 2^n ops from n = 10).
+ * vqe_cobyla_placement is host only (needs no device) and takes the sizes as given (VQE_EINVAL for wide != 0 below
+ * 6 qubits or with max_params <= 64: no launch runs that variant there); vqe_batch_cobyla_placement answers
+ * for circuit `circuit` of the resident batch with the handle's own sizes, for a plain vqe_batch_run_minimize (an
+ * environment step whose new gate is a rotation optimises one variable less).  The reference has no counterpart. */
+enum { VQE_COBYLA_RESIDENT = 0, VQE_COBYLA_STAGED = 1, VQE_COBYLA_GLOBAL = 2, VQE_COBYLA_ROWS = 3, VQE_COBYLA_BLOCK = 4 };
+int vqe_cobyla_placement(int n_qubits, int max_ops, int max_pair, int max_params, int n_groups, int n_params, int wide,
+                         int64_t out[8]);
+int vqe_batch_cobyla_placement(vqe_t* h, int circuit, int64_t out[8]);
 /* LDS bank conflicts of the unit path's ds_read_b128 (model: four groups of 16 lanes per wave): out = {mean, worst}
  * number of a group's lanes that share one 16-byte slot with the plain state layout, then {mean, worst} with the bank
  * swizzle the handle chose (1 = conflict free; the identity where no swizzle applies). */

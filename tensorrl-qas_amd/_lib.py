@@ -45,6 +45,8 @@ SIGNATURES = {
     "vqe_hamiltonian_terms": (C.c_int, [vp, c_i32p, c_i32p]),
     "vqe_hamiltonian_layout": (C.c_int, [vp, c_i32p]),
     "vqe_unit_bank_score": (C.c_int, [vp, c_f64p]),
+    "vqe_cobyla_placement": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_i64p]),
+    "vqe_batch_cobyla_placement": (C.c_int, [vp, C.c_int, c_i64p]),
     "vqe_comm_unique_id": (C.c_int, [vp]),
     "vqe_comm_init": (C.c_int, [vp, C.c_int, C.c_int, vp]),
     "vqe_comm_allreduce_energy": (C.c_int, [vp]),

@@ -114,6 +114,8 @@ CBY_HD int lead_dim_global(int nv) { return (nv + 7) & ~7; }      // (nv is a mu
 // batches of kPad with every load of a batch in flight together; the padding entries are
 // zero and stay zero, dummy vertices n..nv-1 sit between the real ones and the pole (index nv).
 CBY_HD int padded(int n, int pad) { return (n + pad - 1) / pad * pad; }
+// Contexts with kSplit put two lanes on a row when all nv rows fit in half of the nth lanes (CobylaM0::bind)
+CBY_HD bool rows_split(bool ctx_splits, int nv, int nth) { return ctx_splits && 2 * nv <= nth; }
 
 CBY_HD size_t scratch_doubles_ld(int n, int pad, int ld_) {
   // x, sim, simi, datmat, a, vsig, veta, sigbar, dx, w, tdot, state
@@ -172,7 +174,7 @@ struct CobylaM0 {
     w = mem; mem += nv + 2;
     tdot = mem; mem += nv;     // signed simi_j . dx of the trust-region branch, reused by update_simi
     st = mem;
-    split = Ctx::kSplit && 2 * nv <= ctx.nth;
+    split = rows_split(Ctx::kSplit, nv, ctx.nth);
     if (split) {
       const int half = ctx.nth / 2, part = ctx.tid / half;
       const int mid = ((nv / P + 1) / 2) * P;

@@ -246,25 +246,54 @@ int dispatch_n(vqe_t* h, const char* refusal, F f, std::integer_sequence<int, Ns
   return found ? rc : fail(h, VQE_EINVAL, refusal);
 }
 
+// More than 64 parameters in a circuit (the trainable regime): the WIDE variant of the minimiser - on 256-thread
+// workgroups the optimiser update runs on the whole workgroup (BlockCtx), on one-wave workgroups (n <= 9) the lanes
+// walk their rows of the matrices side by side (WaveRowsCtx).  The plain variant keeps neither (registers).
+constexpr int kWideMinN = 6;      // sizes below have no WIDE instantiation
+bool wide_launch(int n, int max_params) {
+  static const bool wide_on = [] { const char* e = std::getenv("VQE_WIDE_UPDATE"); return !(e && e[0] == '0'); }();   // A/B knob
+  return n >= kWideMinN && wide_on && max_params > 64;
+}
+
+// vqe_cobyla_placement / vqe_batch_cobyla_placement: what a minimiser launch with these sizes does with a circuit of
+// nvar variables (cobyla_placement of vqe_device.h - the function StagedCobyla::init calls - and the launcher's own
+// size formulas).
+// Why launch_lds refuses a batch of these sizes (lds: its dynamic LDS bytes), or nullptr
+const char* lds_launch_refusal(int n, size_t lds, int max_ops, size_t lds_per_cu) {
+  if (lds > lds_per_cu) return "circuit too large for the LDS-resident path (gates + parameters)";
+  // register path: the raw ops are staged in the (idle) state region, 2^n records at most
+  if (n >= kRegMinQubits && (size_t)max_ops > ((size_t)1 << n))
+    return "circuit too large for the LDS-resident path (more than 2^n rotations)";
+  return nullptr;
+}
+
+void report_placement(int n, int max_ops, int max_pair, int max_params, int n_groups, int nvar, bool wide, size_t lds_per_cu,
+                      int64_t out[8]) {
+  const bool resident = cobyla_resident_bytes(n, max_ops, max_params, n_groups, max_pair) != 0;
+  const CobPlacement p = cobyla_placement(n, wide, resident, nvar);
+  const size_t lds = lds_bytes(n, max_ops, max_params, n_groups, max_pair, wide);
+  out[0] = p.resident ? VQE_COBYLA_RESIDENT : p.staged ? VQE_COBYLA_STAGED : p.block ? VQE_COBYLA_BLOCK
+           : p.rows ? VQE_COBYLA_ROWS : VQE_COBYLA_GLOBAL;
+  out[1] = p.pad;
+  out[2] = p.words;
+  out[3] = (int64_t)lds;
+  out[4] = p.split;
+  out[5] = (int64_t)cobyla_tile_bytes(n, max_params, wide);
+  out[6] = (int64_t)cobyla_resident_bytes(n, max_ops, max_params, n_groups, max_pair);
+  out[7] = lds_launch_refusal(n, lds, max_ops, lds_per_cu) == nullptr;
+}
+
 template <int N>
 int launch_lds(vqe_t* h, Run mode, BatchArgs A) {
   if (mode == Run::EnvStep) set_env_step(h, A);
   const bool minimize = mode == Run::Minimize || mode == Run::EnvStep;
-  size_t lds = lds_bytes(N, A.max_ops, A.max_params, A.ham.n_groups, A.max_pair);
+  constexpr bool kHasWide = N >= kWideMinN;
+  const bool wide = minimize && wide_launch(N, A.max_params);
+  size_t lds = lds_bytes(N, A.max_ops, A.max_params, A.ham.n_groups, A.max_pair, wide);
   // measurement knob: VQE_LDS_PAD=bytes of unused LDS per workgroup lowers the workgroups per CU
   static const long lds_pad = [] { const char* e = std::getenv("VQE_LDS_PAD"); return e ? std::atol(e) : 0L; }();
   if (lds_pad > 0) lds += (size_t)lds_pad;
-  if (lds > (size_t)h->lds_per_cu)
-    return fail(h, VQE_EINVAL, "circuit too large for the LDS-resident path (gates + parameters)");
-  // register path: the raw ops are staged in the (idle) state region, 2^n records at most
-  if (N >= kRegMinQubits && (size_t)A.max_ops > ((size_t)1 << N))
-    return fail(h, VQE_EINVAL, "circuit too large for the LDS-resident path (more than 2^n rotations)");
-  // More than 64 parameters in a circuit (the trainable regime): the WIDE variant of the kernel - on 256-thread
-  // workgroups the optimiser update runs on the whole workgroup (BlockCtx), on one-wave workgroups (n <= 9) the lanes
-  // walk their rows of the matrices side by side (WaveRowsCtx).  The plain variant keeps neither (registers).
-  constexpr bool kHasWide = N >= 6;
-  static const bool wide_on = [] { const char* e = std::getenv("VQE_WIDE_UPDATE"); return !(e && e[0] == '0'); }();   // A/B knob
-  const bool wide = kHasWide && wide_on && minimize && A.max_params > 64;
+  if (const char* why = lds_launch_refusal(N, lds, A.max_ops, (size_t)h->lds_per_cu)) return fail(h, VQE_EINVAL, why);
   const bool noisy = A.noise.p1 > 0.0 || A.noise.p2 > 0.0;
   constexpr bool kW = false;     // up to 64 parameters per circuit: the instantiation without the workgroup-wide update
   void (*const kernel)(BatchArgs) =
@@ -1405,6 +1434,27 @@ int vqe_hamiltonian_layout(vqe_t* h, int32_t out[4]) {
   if (!h || !out) return VQE_EINVAL;
   if (!h->ham_set) return fail(h, VQE_ESTATE, "no Hamiltonian set");
   out[0] = h->ham.n_groups; out[1] = h->ham.n_units; out[2] = h->ham.n_cls; out[3] = h->ham.has_diag;
+  return VQE_OK;
+}
+
+int vqe_cobyla_placement(int n_qubits, int max_ops, int max_pair, int max_params, int n_groups, int n_params, int wide,
+                         int64_t out[8]) {
+  if (!out || n_qubits < 1 || n_qubits > 13 || max_ops < 1 || max_pair < 0 || max_pair > max_ops || max_params < 1 ||
+      n_groups < 0 || n_params < 1 || n_params > max_params)
+    return VQE_EINVAL;
+  if (wide && !(n_qubits >= kWideMinN && max_params > 64)) return VQE_EINVAL;      // no launch takes the WIDE variant there
+  report_placement(n_qubits, max_ops, max_pair, max_params, n_groups, n_params, wide != 0, (size_t)160 * 1024, out);
+  return VQE_OK;
+}
+
+int vqe_batch_cobyla_placement(vqe_t* h, int circuit, int64_t out[8]) {
+  if (!h || !out) return VQE_EINVAL;
+  if (!h->lds_path) return fail(h, VQE_EINVAL, "n_qubits outside the LDS-resident range");
+  if (!h->ham_set) return fail(h, VQE_ESTATE, "no Hamiltonian set");
+  if (circuit < 0 || circuit >= h->batch) return fail(h, VQE_EINVAL, "circuit index out of range");
+  if (h->h_par_count[circuit] < 1) return fail(h, VQE_EINVAL, "the circuit has no parameters: the optimiser does not run");
+  report_placement(h->n, h->max_ops, h->max_pair, h->max_params, h->ham.n_groups, h->h_par_count[circuit],
+                   wide_launch(h->n, h->max_params), (size_t)h->lds_per_cu, out);
   return VQE_OK;
 }
 

@@ -318,8 +318,9 @@ struct WaveRowsCtx : WaveCtx, TileOps {
   static constexpr bool kTileWalks = true;      // every row walk of tell() goes through the tile
   __device__ __forceinline__ void tile_sync_all() const { tile_sync(); }      // the workgroup is this wavefront
 };
-__host__ __device__ inline size_t cobyla_tile_bytes(int n, int max_params) {
-  return geo_one_wave(n) && max_params > 64 ? kCobTileBytes + (size_t)cby::padded(max_params, 16) * 8 : 0;
+// wide: the launch runs the WIDE variant of k_lds_minimize - no other kernel reads the tile, so no other launch carves it
+__host__ __device__ inline size_t cobyla_tile_bytes(int n, int max_params, bool wide) {
+  return geo_one_wave(n) && wide && max_params > 64 ? kCobTileBytes + (size_t)cby::padded(max_params, 16) * 8 : 0;
 }
 
 // Workgroup-wide context of cobyla_m0.h for LARGE problems (more rows than a wave has lanes,
@@ -461,12 +462,60 @@ __host__ __device__ inline size_t cobyla_resident_bytes(int n, int max_ops, int 
   const size_t need = (cby::scratch_doubles(max_params, 8) * 8 + 15) & ~(size_t)15;
   return lds_bytes_base(n, max_ops, max_params, n_groups, max_pair) + need + 16 <= kResidentLdsBudget ? need : 0;
 }
-__host__ __device__ inline size_t lds_bytes(int n, int max_ops, int max_params, int n_groups, int max_pair) {
+__host__ __device__ inline size_t lds_bytes(int n, int max_ops, int max_params, int n_groups, int max_pair, bool wide) {
   const size_t r = cobyla_resident_bytes(n, max_ops, max_params, n_groups, max_pair);
-  return ((lds_bytes_base(n, max_ops, max_params, n_groups, max_pair) + 15) & ~(size_t)15) + r + cobyla_tile_bytes(n, max_params);
+  return ((lds_bytes_base(n, max_ops, max_params, n_groups, max_pair) + 15) & ~(size_t)15) + r + cobyla_tile_bytes(n, max_params, wide);
 }
 
-__device__ __forceinline__ Lds carve(unsigned char* base, int n, int max_ops, int max_params, int n_groups, int max_pair) {
+// Where the optimiser's arrays of ONE circuit live and which context of cobyla_m0.h updates them: the decision of
+// StagedCobyla::init, which vqe_cobyla_placement reports to the tests from this very function.
+//   n: qubits; wide: the launch runs the WIDE variant of k_lds_minimize; resident: the launch has an LDS region for
+//   the arrays (cobyla_resident_bytes != 0 for the BATCH's sizes); nvar: the variables of this circuit.
+#ifndef VQE_BLOCK_TILE
+#define VQE_BLOCK_TILE 1
+#endif
+// (tiles of the workgroup context: NW x 8.7 KB + the shared vector in the dead state region - 16 << n bytes)
+VQE_HD constexpr bool cobyla_block_tile(int n) {
+  return VQE_BLOCK_TILE && ((size_t)16 << n) >= (size_t)((1 << geo_lt(n)) / 64) * kCobTileBytes + 4096;
+}
+struct CobPlacement {
+  bool resident;   // the arrays live in an LDS region of their own (Lds::cob): nothing is copied
+  bool staged;     // the context works on LDS: resident, or copied into the dead state region around every call
+  bool block;      // more rows than a wave has lanes: workgroup-wide context (BlockCtx) on the global scratch
+  bool rows;       // one wave on the global scratch with the row / column walks of the trainable regime (WaveRowsCtx)
+  bool split;      // lane pairs share a row (WaveCtx, at most 32 rows)
+  int pad;         // kPad of the context that runs
+  int words;       // doubles of the arrays as that context lays them out
+};
+__host__ __device__ __forceinline__ CobPlacement cobyla_placement(int n, bool wide, bool resident, int nvar) {
+  const int nt = 1 << geo_lt(n);
+  const bool k_block = wide && nt >= 256, k_rows = wide && nt == 64;
+  CobPlacement p;
+  p.resident = resident;
+  p.pad = WaveCtx::kPad;
+  p.words = (int)cby::scratch_doubles(nvar, WaveCtx::kPad);
+  p.block = k_block && nvar > 64;
+  p.staged = resident || (!p.block && (size_t)p.words * 8 <= ((size_t)16 << n));
+  if (p.block) {
+    p.pad = cobyla_block_tile(n) ? BlockCtx<256, true>::kPad : BlockCtx<256, false>::kPad;
+    p.words = (int)cby::scratch_doubles(nvar, p.pad);
+  }
+  // ... with the row / column walks of the trainable regime (WaveRowsCtx): problems with more than 32 variables, i.e.
+  // those whose rows are not split over lane pairs
+  p.rows = k_rows && nvar > 32 && !p.staged;
+  // arrays that stay in the global scratch use the 64-byte row layout (cobyla_m0.h: lead_dim_global)
+  // (one-wave context only: with a thread per row - BlockCtx - the aligned stride measured 3.5 % slower at 12 qubits /
+  // 202 variables, 4.6 % faster for the one-wave context at 8 qubits / 129 variables)
+  if (!p.staged && !p.block) {
+    p.pad = p.rows ? WaveRowsCtx::kPad : WaveCtx::kPad;      // (16 with the tile context: rows are whole 128-byte lines)
+    p.words = (int)cby::scratch_doubles_ld(nvar, p.pad, cby::lead_dim_global(cby::padded(nvar, p.pad)));
+  }
+  p.split = !p.block && !p.rows && cby::rows_split(WaveCtx::kSplit, cby::padded(nvar, WaveCtx::kPad), WaveCtx::nth);
+  return p;
+}
+
+__device__ __forceinline__ Lds carve(unsigned char* base, int n, int max_ops, int max_params, int n_groups, int max_pair,
+                                     bool wide = false) {
   const int ng = n_groups > 0 ? n_groups : 1;
   Lds l;
   l.psi = (double2*)base; base += (size_t)16 << n;
@@ -492,7 +541,7 @@ __device__ __forceinline__ Lds carve(unsigned char* base, int n, int max_ops, in
   l.cob = cobyla_resident_bytes(n, max_ops, max_params, n_groups, max_pair)
               ? (double*)((unsigned char*)l.psi + ((lds_bytes_base(n, max_ops, max_params, n_groups, max_pair) + 15) & ~(size_t)15))
               : nullptr;
-  l.tile = cobyla_tile_bytes(n, max_params)
+  l.tile = cobyla_tile_bytes(n, max_params, wide)
                ? (double*)((unsigned char*)l.psi + ((lds_bytes_base(n, max_ops, max_params, n_groups, max_pair) + 15) & ~(size_t)15) +
                            cobyla_resident_bytes(n, max_ops, max_params, n_groups, max_pair))
                : nullptr;
@@ -1461,15 +1510,12 @@ struct StagedCobyla {
   // else: for every other problem the two contexts produce the same bits, so a circuit's result does not depend on
   // which kernel variant its batch selected
   typedef cby::CobylaM0<WaveRowsCtx, false, double> CobR;
-  __device__ __forceinline__ bool rows_ctx() const { return kRowsG && n > 32; }
-#ifndef VQE_BLOCK_TILE
-#define VQE_BLOCK_TILE 1
-#endif
-  // (tiles of the workgroup context: NW x 8.7 KB + the shared vector in the dead state region - 16 << N bytes)
-  static constexpr bool kBlockTile = VQE_BLOCK_TILE && ((size_t)16 << N) >= (Geo<N>::NT / 64) * kCobTileBytes + 4096;
+  __device__ __forceinline__ bool rows_ctx() const { return kRowsG && rows; }
+  static constexpr bool kBlockTile = cobyla_block_tile(N);
   typedef cby::CobylaM0<BlockCtx<Geo<N>::NT, kBlockTile>, false, double> CobB;   // the same, whole workgroup (more rows than a wave has lanes)
   double* red;     // LDS words of the block reductions
   bool block;      // more rows than a wave has lanes: workgroup-wide context on the global scratch
+  bool rows;       // one wave on the global scratch with the row / column walks (cobyla_placement)
   double* gmem;    // per-problem scratch; x[] is its first array
   double* lmem;    // the (dead) state region of LDS
   double* tile;    // LDS transposition tile of the one-wave context on more than 64 variables (kRowsG)
@@ -1498,18 +1544,14 @@ struct StagedCobyla {
     tile = L.tile;
     pub = (int*)(L.red + 8);
     n = n_;
-    words = (int)cby::scratch_doubles(n, WaveCtx::kPad);
     red = L.red;
-    block = kBlock && n > 64;
-    staged = resident || (!block && (size_t)words * 8 <= ((size_t)16 << N));
-    if (block) words = (int)cby::scratch_doubles(n, CobB::P);
-    // arrays that stay in the global scratch use the 64-byte row layout (cobyla_m0.h: lead_dim_global)
-    // (one-wave context only: with a thread per row - BlockCtx - the aligned stride measured 3.5 % slower at 12 qubits /
-    // 202 variables, 4.6 % faster for the one-wave context at 8 qubits / 129 variables)
-    if (!staged && !block) {
-      const int pad = rows_ctx() ? CobR::P : CobG::P;      // (16 with the tile context: rows are whole 128-byte lines)
-      words = (int)cby::scratch_doubles_ld(n, pad, cby::lead_dim_global(cby::padded(n, pad)));
-    }
+    static_assert(CobL::P == WaveCtx::kPad && CobG::P == WaveCtx::kPad && CobR::P == WaveRowsCtx::kPad, "cobyla_placement");
+    static_assert(CobB::P == (kBlockTile ? BlockCtx<256, true>::kPad : BlockCtx<256, false>::kPad), "cobyla_placement");
+    const CobPlacement pl = cobyla_placement(N, WIDE, resident, n);
+    block = pl.block;
+    staged = pl.staged;
+    rows = pl.rows;
+    words = pl.words;
   }
   __device__ __forceinline__ double* x() const { return resident ? lmem : gmem; }
   // the optimiser's scalars as parked in the scratch (valid after start()/tell())
@@ -1765,7 +1807,7 @@ template <int N, bool WIDE = (N >= 10 && Geo<N>::NT >= 256), bool NOISY = false>
 __global__ void __launch_bounds__(Geo<N>::NT, Geo<N>::WPS) k_lds_minimize(BatchArgs A) {
   constexpr int kThreads = Geo<N>::NT;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const Lds L = carve(smem, N, A.max_ops, A.max_params, A.ham.n_groups, A.max_pair);
+  const Lds L = carve(smem, N, A.max_ops, A.max_params, A.ham.n_groups, A.max_pair, WIDE);
   const int b = A.order[blockIdx.x];
   const int P = A.par_count[b];
   const double* theta = A.theta + A.par_begin[b];

@@ -53,6 +53,26 @@ class Circuit:
         return Circuit(z, z, z, z, 0)
 
 
+COBYLA_CLASSES = ("resident", "staged", "global", "rows", "block")      # VQE_COBYLA_* of include/vqe_hip.h
+
+
+def _placement(out):
+    return {"class": COBYLA_CLASSES[out[0]], "pad": int(out[1]), "words": int(out[2]), "lds_bytes": int(out[3]),
+            "split": bool(out[4]), "tile_bytes": int(out[5]), "resident_bytes": int(out[6]), "accepted": bool(out[7])}
+
+
+def cobyla_placement(n_qubits, max_ops, max_pair, max_params, n_groups, n_params, wide):
+    """vqe_cobyla_placement (host only): what a minimiser launch of the LDS-resident kernels with these batch sizes
+    does with the optimiser's arrays of a circuit of ``n_params`` parameters - the kernel's own decision function.
+    -> dict(class, pad, words, lds_bytes, split, tile_bytes, resident_bytes, accepted)"""
+    out = (C.c_int64 * 8)()
+    rc = _lib.load().vqe_cobyla_placement(int(n_qubits), int(max_ops), int(max_pair), int(max_params), int(n_groups),
+                                          int(n_params), int(bool(wide)), out)
+    if rc != 0:
+        raise ValueError("vqe_cobyla_placement: argument out of range")
+    return _placement(out)
+
+
 class VQEEngine:
     """One handle = one (n_qubits, initial state, Hamiltonian) problem on one GPU."""
 
@@ -154,6 +174,13 @@ class VQEEngine:
         out = (C.c_int32 * 4)()
         self._chk(self._lib.vqe_hamiltonian_layout(self._h, out))
         return {"table_groups": out[0], "units": out[1], "class_groups": out[2], "has_diag": bool(out[3])}
+
+    def batch_cobyla_placement(self, circuit: int):
+        """Where the device COBYLA keeps the arrays of circuit ``circuit`` of the resident batch and which of its
+        contexts updates them (n <= 13; see cobyla_placement)."""
+        out = (C.c_int64 * 8)()
+        self._chk(self._lib.vqe_batch_cobyla_placement(self._h, int(circuit), out))
+        return _placement(out)
 
     def unit_bank_score(self):
         """Modelled LDS bank conflicts of the unit path: mean / worst lanes per 16-byte slot of a ds_read_b128 lane group

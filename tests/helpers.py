@@ -64,6 +64,69 @@ def random_hamiltonian(n, T, rng, real=True):
     return np.array(xs, np.uint64), np.array(zs, np.uint64), np.array(cs)
 
 
+def rotations(n, P, rng, p_cnot=0.15):
+    """A circuit with exactly P rotations (and, from two qubits on, CNOTs in between)."""
+    kind, q0, q1, pidx = [], [], [], []
+    for j in range(P):
+        kind.append(1 + int(rng.integers(3))), q0.append(int(rng.integers(n))), q1.append(-1), pidx.append(j)
+        if rng.random() < p_cnot and n > 1:
+            c = int(rng.integers(n))
+            kind.append(0), q0.append(c), q1.append(int((c + 1 + rng.integers(n - 1)) % n)), pidx.append(-1)
+    return tuple(np.array(v, np.int32) for v in (kind, q0, q1, pidx)) + (rng.uniform(-np.pi, np.pi, P),)
+
+
+def tie_free_gates(n, P, rng):
+    """P <= 3 n rotations on DISTINCT (qubit, axis) pairs with CNOTs in between (from two qubits on): no two
+    parameters act alike, so COBYLA meets no exact ties (two equal simplex values / equally placed vertices are
+    decided by the last bit, i.e. by the order of a sum - not by the algorithm)."""
+    pairs = [(q, a) for q in range(n) for a in (1, 2, 3)]
+    rng.shuffle(pairs)
+    kind, q0, q1, pidx = [], [], [], []
+    for j, (q, a) in enumerate(pairs[:P]):
+        kind.append(a), q0.append(q), q1.append(-1), pidx.append(j)
+        if rng.random() < 0.6 and n > 1:
+            c = int(rng.integers(n))
+            kind.append(0), q0.append(c), q1.append(int((c + 1 + rng.integers(n - 1)) % n)), pidx.append(-1)
+    th = rng.uniform(-np.pi, np.pi, P)
+    return tuple(np.array(v, np.int32) for v in (kind, q0, q1, pidx)) + (th,)
+
+
+def with_noise_gates(kind, q0, q1, pidx):
+    """construct_ansatz of the noisy seam: DEPOL2 behind every CNOT, DEPOL1 behind every rotation."""
+    k2, a2, b2, p2 = [], [], [], []
+    for k, a, b, p in zip(kind, q0, q1, pidx):
+        k2 += [int(k), 5 if k == 0 else 4]
+        a2 += [int(a), int(a)]
+        b2 += [int(b), int(b) if k == 0 else -1]
+        p2 += [int(p), -1]
+    return tuple(np.array(v, np.int32) for v in (k2, a2, b2, p2))
+
+
+def oracle_energy(psi0, kind, q0, q1, pidx, th, ham):
+    return vo.energy_pauli(vo.run_circuit(psi0, kind, q0, q1, pidx, th), *ham)
+
+
+def shift_grad(psi0, kind, q0, q1, pidx, th, ham, energy=oracle_energy):
+    """Exact parameter shift, gate by gate: dE/dtheta_j = sum over the gates g with parameter j of
+    (E(theta_g + pi/2) - E(theta_g - pi/2)) / 2, each gate given its own copy of the angle.  ``energy``: the oracle
+    that evaluates E (numpy by default; its C restatement where numpy takes seconds per energy)."""
+    P = th.size
+    grad = np.zeros(P)
+    rot = [g for g in range(kind.size) if kind[g] in (1, 2, 3)]
+    # one private parameter per rotation gate, so that shared parameters are shifted one gate at a time
+    own = np.array([-1] * kind.size, np.int32)
+    for i, g in enumerate(rot):
+        own[g] = i
+    base = np.array([th[pidx[g]] for g in rot])
+    for i, g in enumerate(rot):
+        tp, tm = base.copy(), base.copy()
+        tp[i] += np.pi / 2
+        tm[i] -= np.pi / 2
+        d = 0.5 * (energy(psi0, kind, q0, q1, own, tp, ham) - energy(psi0, kind, q0, q1, own, tm, ham))
+        grad[pidx[g]] += d
+    return grad
+
+
 STEMS = {
     "H2O_8q": "H2O_8q_geom_H_-0.021_-0.002_0.000;_O_0.835_0.452_0.000;_H_1.477_-0.273_0.000_jordan_wigner",
     "CH2_8q": "CH2_8q_geom_C_0.000_0.000_0.000;_H_1.080_0.000_0.000;_H_-0.225_1.056_0.000_jordan_wigner",

@@ -191,14 +191,17 @@ def ham_scale(ham):
 
 # ---- the cases of the GPU trajectory tests (tests/test_lbfgs_gpu.py); tests/test_lbfgs_cpu.py checks on the CPU that
 # none of them has a marginal decision --------------------------------------------------------------------------------
-TRAJ_GATES = {1: 6, 3: 16, 6: 30, 10: 40, 12: 36, 13: 24}
+TRAJ_GATES = {1: 6, 2: 10, 3: 16, 4: 20, 5: 24, 6: 30, 7: 32, 8: 34, 9: 36, 10: 40, 11: 38, 12: 36, 13: 24}
 TRAJ_OPTS = dict(history=3, maxiter=6, maxfun=200)
 # (n, which, su4) -> seed, where the default 500 + n had a marginal decision (n = 1) or trial points that hang on the
 # last digits of the gradient (gradient_sensitivity: the flat landscapes of the fermionic Hamiltonian and of 13
 # qubits, where the first quasi-Newton steps are tens of radians long).  Taken from 500 + n + 100 j: the first seed
 # that passes tests/test_lbfgs_cpu.py with room to spare and still evicts a pair inside the run.
 TRAJ_SEED = {(1, 0, False): 509, (6, 1, False): 1006, (6, 1, True): 706, (10, 1, False): 2510, (12, 1, False): 812,
-             (12, 1, True): 712, (13, 0, False): 1113, (13, 1, False): 1513}
+             (12, 1, True): 712, (13, 0, False): 1113, (13, 1, False): 1513,
+             # the sizes added for tests/test_lds_sizes_gpu.py, by the same procedure (room to spare: a sensitivity of at
+             # most half of X_SENSITIVITY_MAX)
+             (5, 1, False): 905, (8, 1, False): 608, (9, 1, False): 609, (11, 1, False): 1411}
 
 
 def trajectory_cases():

@@ -17,6 +17,7 @@ import pytest
 
 import vqe_oracle as vo
 from helpers import GOLDEN, random_gates, random_hamiltonian, random_state, reference_config, make_data_root
+from helpers import rotations as _rotations, tie_free_gates as _tie_free_gates, with_noise_gates as _with_noise_gates
 
 pytestmark = pytest.mark.gpu
 E_TOL = 1e-10
@@ -34,17 +35,6 @@ def _engine(tq, n, psi0, ham):
     eng.set_init_state(psi0)
     eng.set_hamiltonian(*ham)
     return eng
-
-
-def _with_noise_gates(kind, q0, q1, pidx):
-    """construct_ansatz of the noisy seam: DEPOL2 behind every CNOT, DEPOL1 behind every rotation."""
-    k2, a2, b2, p2 = [], [], [], []
-    for k, a, b, p in zip(kind, q0, q1, pidx):
-        k2 += [int(k), 5 if k == 0 else 4]
-        a2 += [int(a), int(a)]
-        b2 += [int(b), int(b) if k == 0 else -1]
-        p2 += [int(p), -1]
-    return tuple(np.array(v, np.int32) for v in (k2, a2, b2, p2))
 
 
 # ---- ADVICE: register path, raw ops beyond the upper half of the state region ------------------
@@ -342,17 +332,6 @@ def test_trainable_scale_12_qubits(tq):
 
 
 # ---- device COBYLA vs host COBYLA on the device's own energies ------------------------------------
-def _rotations(n, P, rng, p_cnot=0.15):
-    """A circuit with exactly P rotations (and CNOTs in between)."""
-    kind, q0, q1, pidx = [], [], [], []
-    for j in range(P):
-        kind.append(1 + int(rng.integers(3))), q0.append(int(rng.integers(n))), q1.append(-1), pidx.append(j)
-        if rng.random() < p_cnot:
-            c = int(rng.integers(n))
-            kind.append(0), q0.append(c), q1.append(int((c + 1 + rng.integers(n - 1)) % n)), pidx.append(-1)
-    return tuple(np.array(v, np.int32) for v in (kind, q0, q1, pidx)) + (rng.uniform(-np.pi, np.pi, P),)
-
-
 @pytest.mark.parametrize("n", [8, 9])
 def test_result_does_not_depend_on_the_batch_a_circuit_is_in(tq, n):
     """One-wave kernels (n <= 9): a batch with a circuit of more than 64 parameters runs the kernel variant whose
@@ -385,22 +364,6 @@ def test_result_does_not_depend_on_the_batch_a_circuit_is_in(tq, n):
         e = vo.energy_pauli(vo.run_circuit(psi0, *c[:4], x), *ham)
         assert abs(e - f) < 1e-10 and nfev == 90
     eng.close()
-
-
-def _tie_free_gates(n, P, rng):
-    """P rotations on DISTINCT (qubit, axis) pairs with CNOTs in between: no two parameters act
-    alike, so COBYLA meets no exact ties (two equal simplex values / equally placed vertices are
-    decided by the last bit, i.e. by the order of a sum - not by the algorithm)."""
-    pairs = [(q, a) for q in range(n) for a in (1, 2, 3)]
-    rng.shuffle(pairs)
-    kind, q0, q1, pidx = [], [], [], []
-    for j, (q, a) in enumerate(pairs[:P]):
-        kind.append(a), q0.append(q), q1.append(-1), pidx.append(j)
-        if rng.random() < 0.6:
-            c = int(rng.integers(n))
-            kind.append(0), q0.append(c), q1.append(int((c + 1 + rng.integers(n - 1)) % n)), pidx.append(-1)
-    th = rng.uniform(-np.pi, np.pi, P)
-    return tuple(np.array(v, np.int32) for v in (kind, q0, q1, pidx)) + (th,)
 
 
 @pytest.mark.parametrize("n,P,seed", [(4, 5, 0), (5, 7, 1), (6, 9, 2), (8, 11, 3), (8, 12, 4), (12, 10, 5), (10, 24, 6)])

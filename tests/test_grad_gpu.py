@@ -5,6 +5,7 @@ import pytest
 
 import vqe_oracle as vo
 from helpers import fermionic_hamiltonian, random_gates, random_hamiltonian, random_state
+from helpers import oracle_energy as _oracle_energy, shift_grad as _shift_grad
 
 pytestmark = pytest.mark.gpu
 
@@ -21,30 +22,6 @@ def _engine(n, ham, psi0, circ):
 def _circuit(kind, q0, q1, pidx, P):
     import tensorrl_qas_amd as tq
     return tq.Circuit(kind, q0, q1, pidx, P)
-
-
-def _oracle_energy(psi0, kind, q0, q1, pidx, th, ham):
-    return vo.energy_pauli(vo.run_circuit(psi0, kind, q0, q1, pidx, th), *ham)
-
-
-def _shift_grad(psi0, kind, q0, q1, pidx, th, ham):
-    """Exact parameter shift, gate by gate: dE/dtheta_j = sum over the gates g with parameter j of
-    (E(theta_g + pi/2) - E(theta_g - pi/2)) / 2, each gate given its own copy of the angle."""
-    P = th.size
-    grad = np.zeros(P)
-    rot = [g for g in range(kind.size) if kind[g] in (1, 2, 3)]
-    # one private parameter per rotation gate, so that shared parameters are shifted one gate at a time
-    own = np.array([-1] * kind.size, np.int32)
-    for i, g in enumerate(rot):
-        own[g] = i
-    base = np.array([th[pidx[g]] for g in rot])
-    for i, g in enumerate(rot):
-        tp, tm = base.copy(), base.copy()
-        tp[i] += np.pi / 2
-        tm[i] -= np.pi / 2
-        d = 0.5 * (_oracle_energy(psi0, kind, q0, q1, own, tp, ham) - _oracle_energy(psi0, kind, q0, q1, own, tm, ham))
-        grad[pidx[g]] += d
-    return grad
 
 
 def _hamiltonians(n, rng):

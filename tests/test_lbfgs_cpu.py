@@ -163,3 +163,8 @@ def test_gpu_env_step_middle_case_has_no_marginal_decision():
     assert r.marginal == [], r.marginal
     assert 0 < hole < full["theta"].size - 1 and r.nit >= 1
     assert lh.gradient_sensitivity(sub, r, **lh.TRAJ_OPTS) <= lh.X_SENSITIVITY_MAX
+
+
+def test_gpu_trajectory_cases_hold_every_lds_size():
+    """test_trajectory_parity (tests/test_lbfgs_gpu.py) runs k_lds_minimize_lbfgs at every compiled size of the LDS kernels"""
+    assert sorted(lh.TRAJ_GATES) == list(range(1, 14))

@@ -272,7 +272,8 @@ int vqe_batch_fetch(vqe_t* h, double* x /* sum of n_params, may be NULL */,
 int vqe_batch_run_energy_grad(vqe_t* h);
 int vqe_batch_fetch_grad(vqe_t* h, double* grad /* sum of n_params, layout of vqe_batch_fetch's x */);
 /* the optimiser's result before the float32 rounding of vqe_batch_run_env_step
- * (scipy's result.x, stored by the reference as env.opt_ang_save, :288); same layout as x */
+ * (scipy's result.x, stored by the reference as env.opt_ang_save, :288); same layout as x.  After a run that rounds
+ * nothing (vqe_batch_run_minimize, vqe_batch_run_minimize_lbfgs, on every path) it equals vqe_batch_fetch's x. */
 int vqe_batch_fetch_xopt(vqe_t* h, double* x /* sum of n_params */);
 /* ---- device L-BFGS on the adjoint gradient ---------------------------------------------------
  * A batched quasi-Newton optimiser with the shape of the COBYLA launch: one workgroup per circuit, and the whole loop -

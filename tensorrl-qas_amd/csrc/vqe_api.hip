@@ -120,8 +120,12 @@ struct vqe_handle {
   DevBufExact<double2> dmb_rho;
   DevBuf<double> dmb_partial;
   DmPlanSlot dmb_full, dmb_pre;
-  DevBuf<double> d_cob_x0, d_cob_xres, d_cob_f;      // device-resident lock-step COBYLA of the streaming path
-  DevBuf<int32_t> d_cob_nfev, d_cob_active;
+  // the lock-step driver of the device optimisers (lockstep_run): results of the circuits that stopped, the count of
+  // running circuits; COBYLA's start points and per-circuit running flags
+  DevBuf<double> ls_xres, ls_fres;
+  DevBuf<int32_t> ls_nfres, ls_running;
+  DevBuf<double> d_cob_x0;
+  DevBuf<int32_t> d_cob_active;
   void* comm = nullptr;      // RCCL communicator of vqe_comm_init (ncclComm_t)
   int comm_world = 0;
   StreamWork sw;  // streaming-path work buffers
@@ -141,12 +145,9 @@ struct vqe_handle {
   // adjoint gradient of the streaming path (vqe_stream_grad.h): opt-in (vqe_set_stream_grad); its backward sweep undoes
   // the circuit in place, so the states it leaves are not those a reduction-only launch may take
   bool stream_grad = false, stream_states_undone = false;
-  // device L-BFGS of the streaming path (vqe_stream_lbfgs.h): opt-in (vqe_set_stream_lbfgs); per-stream records, the
-  // results of the streams that stopped, the count of running streams
+  // device L-BFGS of the streaming path (vqe_stream_lbfgs.h): opt-in (vqe_set_stream_lbfgs); per-stream records
   bool stream_lbfgs = false;
   DevBufExact<StreamLbfgsRec> lb_rec;
-  DevBufExact<double> lb_xres, lb_fres;
-  DevBufExact<int32_t> lb_nfres, lb_running;
 };
 
 #ifdef VQE_STAMPS
@@ -457,14 +458,8 @@ CobylaPtr make_cobyla(int n, const double* x0, const BatchArgs& A) {
   return CobylaPtr(c);
 }
 
-// COBYLA of all resident streams in lock-step (one batched evaluation per iteration): the streaming path's form of
-// scipy.optimize.minimize(..., method='COBYLA') (environment_qulacs_TN_notin_agent.py:478).  The optimiser state of
-// every stream lives on the device (k_s_cobyla: the host build's arithmetic, one thread per stream); the host only
-// queues launches and looks at the number of running streams every kStreamPoll iterations - no copy of trial points
-// or energies and no synchronisation per evaluation (VQE_STREAM_HOST_COBYLA=1: the round-2 host-driven loop, kept
-// for A/B runs).  x: in x0, out the result (layout pbeg / pcnt); trial points travel through d_x.
-constexpr int kStreamPoll = 8;
-
+// The round-2 host-driven COBYLA of the streaming path (VQE_STREAM_HOST_COBYLA=1, kept for A/B runs): trial points
+// and energies travel per evaluation.  x: in x0, out the result (layout pbeg / pcnt); trial points travel through d_x.
 int stream_cobyla_host(vqe_t* h, BatchArgs& A, const std::vector<int64_t>& pbeg, const std::vector<int32_t>& pcnt,
                        std::vector<double>& x, std::vector<double>& f, std::vector<int32_t>& nfev) {
   const int B = h->batch;
@@ -490,62 +485,90 @@ int stream_cobyla_host(vqe_t* h, BatchArgs& A, const std::vector<int64_t>& pbeg,
   return VQE_OK;
 }
 
-// d_pbeg / d_pcnt: the device copies of pbeg / pcnt (the batch that A describes).
-// eval(A, it, active): queue the it-th batched evaluation (it = 1, 2, ...) of the trial points A.theta into d_f;
-// active[b] != 0 for the streams whose optimiser waits for that value - an evaluation may skip the others (the batched
-// exact channel mode does, the streaming path evaluates all of them).
-template <class Eval>
-int lockstep_cobyla(vqe_t* h, BatchArgs& A, std::vector<double>& x, std::vector<double>& f, std::vector<int32_t>& nfev,
-                    const int64_t* d_pbeg, const int32_t* d_pcnt, Eval eval) {
-  const int B = h->batch;
+// ---- the lock-step driver of the device optimisers ------------------------------------------------------------------
+// The optimisers whose evaluation is a train of launches - COBYLA on the streaming path and in the batched exact channel
+// mode (k_s_cobyla, one thread per circuit), L-BFGS on the streaming path (k_sl_step, one wavefront per circuit) - keep
+// the state of every resident circuit on the device and run all circuits in lock-step: one batched evaluation of the
+// trial points in d_x, the running count zeroed, one step kernel that tells every optimiser its value and leaves the next
+// trial points in d_x.  The host only queues launches and looks at the number of running circuits every kStreamPoll
+// iterations and at maxfun - no copy of trial points or energies and no synchronisation per evaluation.  A circuit that
+// stops writes x, f and nfev to ls_xres / ls_fres / ls_nfres; its trial point stays where it is (the evaluations go on
+// over all circuits).
+constexpr int kStreamPoll = 8;
+
+// The buffers of such a run, and its start points x in d_x, where A.theta points from here on.
+int lockstep_begin(vqe_t* h, BatchArgs& A, const std::vector<double>& x) {
   const size_t PT = x.size();
   HIP_TRY(h, h->d_x.reserve(PT + 1));
-  HIP_TRY(h, h->d_cob_x0.reserve(PT + 1));
-  HIP_TRY(h, h->d_cob_xres.reserve(PT + 1));
-  HIP_TRY(h, h->d_cob_f.reserve(B));
-  HIP_TRY(h, h->d_cob_nfev.reserve(B));
-  HIP_TRY(h, h->d_cob_active.reserve((size_t)B + 1));
-  if (PT) HIP_TRY(h, hipMemcpyAsync(h->d_cob_x0.p, x.data(), PT * 8, hipMemcpyHostToDevice, h->stream));
-  // (trial points of streams that finish early stay where they are: the evaluations go on in lock-step over all streams)
+  HIP_TRY(h, h->ls_xres.reserve(PT + 1));
+  HIP_TRY(h, h->ls_fres.reserve(h->batch));
+  HIP_TRY(h, h->ls_nfres.reserve(h->batch));
+  HIP_TRY(h, h->ls_running.reserve(1));
   if (PT) HIP_TRY(h, hipMemcpyAsync(h->d_x.p, x.data(), PT * 8, hipMemcpyHostToDevice, h->stream));
-  int32_t* n_active = h->d_cob_active.p + B;
-  auto cobyla_step = [&](bool first) {      // start() from x0, or tell() of the evaluation just made
-    HIP_TRY(h, hipMemsetAsync(n_active, 0, 4, h->stream));
-    const auto kernel = first ? k_s_cobyla<true> : k_s_cobyla<false>;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, h->stream, B, d_pbeg, d_pcnt,
-                       (const int64_t*)h->d_scratch_begin.p, h->d_scratch.p, (const double*)h->d_cob_x0.p, h->d_x.p,
-                       (const double*)h->d_f.p, A.rhobeg, A.rhoend, A.maxfun, h->d_cob_active.p, n_active, h->d_cob_xres.p,
-                       h->d_cob_f.p, h->d_cob_nfev.p);
-    return (int)VQE_OK;
-  };
-  VQE_TRY(cobyla_step(true));
   A.theta = h->d_x.p;
+  return VQE_OK;
+}
+
+// The loop, after lockstep_begin.  eval(it): queue the it-th batched evaluation (it = 1, 2, ...); step(it): queue the
+// kernel that takes it (its running count: ls_running).  optimiser: the name in the error message.  Out: x, f, nfev.
+template <class Eval, class Step>
+int lockstep_run(vqe_t* h, const char* optimiser, int maxfun, std::vector<double>& x, std::vector<double>& f,
+                 std::vector<int32_t>& nfev, Eval eval, Step step) {
+  const int B = h->batch;
   uint64_t it = 0;
   int32_t running = 1;
   while (running > 0) {
-    VQE_TRY(eval(A, ++it, (const int32_t*)h->d_cob_active.p));
-    VQE_TRY(cobyla_step(false));
-    if (it % kStreamPoll == 0 || it >= (uint64_t)A.maxfun) {
-      HIP_TRY(h, hipMemcpyAsync(&running, n_active, 4, hipMemcpyDeviceToHost, h->stream));
+    VQE_TRY(eval(++it));
+    HIP_TRY(h, hipMemsetAsync(h->ls_running.p, 0, 4, h->stream));
+    step(it);
+    if (it % kStreamPoll == 0 || it >= (uint64_t)maxfun) {
+      HIP_TRY(h, hipMemcpyAsync(&running, h->ls_running.p, 4, hipMemcpyDeviceToHost, h->stream));
       HIP_TRY(h, hipStreamSynchronize(h->stream));
     }
-    if (it > (uint64_t)A.maxfun + kStreamPoll) return fail(h, VQE_ESTATE, "device COBYLA did not terminate");
+    if (it > (uint64_t)maxfun + kStreamPoll) return fail(h, VQE_ESTATE, std::string("device ") + optimiser + " did not terminate");
   }
   HIP_TRY(h, hipGetLastError());
-  if (PT) HIP_TRY(h, hipMemcpyAsync(x.data(), h->d_cob_xres.p, PT * 8, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(f.data(), h->d_cob_f.p, (size_t)B * 8, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(nfev.data(), h->d_cob_nfev.p, (size_t)B * 4, hipMemcpyDeviceToHost, h->stream));
+  if (!x.empty()) HIP_TRY(h, hipMemcpyAsync(x.data(), h->ls_xres.p, x.size() * 8, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(f.data(), h->ls_fres.p, (size_t)B * 8, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(nfev.data(), h->ls_nfres.p, (size_t)B * 4, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   return VQE_OK;
 }
 
-// the streaming path's lock-step COBYLA: every evaluation is stream_evaluate on all streams
+// COBYLA of all resident circuits in lock-step: the form scipy.optimize.minimize(..., method='COBYLA')
+// (environment_qulacs_TN_notin_agent.py:478) takes where an evaluation is a train of launches.  k_s_cobyla is the host
+// build's arithmetic; its start() runs before the first evaluation, so it is queued here, ahead of the loop.
+// A: the batch to optimise (its par_begin / par_count lay out x); x: in x0, out the result.
+// eval(A, it, active): queue the it-th batched evaluation of the trial points A.theta into d_f; active[b] != 0 for the
+// circuits whose optimiser waits for that value - an evaluation may skip the others (the batched exact channel mode does,
+// the streaming path evaluates all of them).
+template <class Eval>
+int lockstep_cobyla(vqe_t* h, BatchArgs& A, std::vector<double>& x, std::vector<double>& f, std::vector<int32_t>& nfev, Eval eval) {
+  const int B = h->batch;
+  VQE_TRY(lockstep_begin(h, A, x));
+  HIP_TRY(h, h->d_cob_active.reserve(B));
+  VQE_TRY(upload(h, h->d_cob_x0, x));
+  auto cobyla_step = [&](bool first) {      // start() from x0, or tell() of the evaluation just made
+    const auto kernel = first ? k_s_cobyla<true> : k_s_cobyla<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, h->stream, B, (const int64_t*)A.par_begin,
+                       (const int32_t*)A.par_count, (const int64_t*)h->d_scratch_begin.p, h->d_scratch.p,
+                       (const double*)h->d_cob_x0.p, h->d_x.p, (const double*)h->d_f.p, A.rhobeg, A.rhoend, A.maxfun,
+                       h->d_cob_active.p, h->ls_running.p, h->ls_xres.p, h->ls_fres.p, h->ls_nfres.p);
+  };
+  HIP_TRY(h, hipMemsetAsync(h->ls_running.p, 0, 4, h->stream));
+  cobyla_step(true);
+  return lockstep_run(h, "COBYLA", A.maxfun, x, f, nfev,
+                      [&](uint64_t it) { return eval(A, it, (const int32_t*)h->d_cob_active.p); },
+                      [&](uint64_t) { cobyla_step(false); });
+}
+
+// The streaming path's COBYLA: every evaluation is stream_evaluate on all streams (VQE_STREAM_HOST_COBYLA=1: the
+// round-2 host-driven loop, kept for A/B runs).  pbeg / pcnt: the host copies of A.par_begin / A.par_count.
 int stream_cobyla(vqe_t* h, BatchArgs& A, const std::vector<int64_t>& pbeg, const std::vector<int32_t>& pcnt,
-                  std::vector<double>& x, std::vector<double>& f, std::vector<int32_t>& nfev,
-                  const int64_t* d_pbeg, const int32_t* d_pcnt) {
+                  std::vector<double>& x, std::vector<double>& f, std::vector<int32_t>& nfev) {
   static const bool host_loop = [] { const char* e = std::getenv("VQE_STREAM_HOST_COBYLA"); return e && e[0] == '1'; }();
   if (host_loop) return stream_cobyla_host(h, A, pbeg, pcnt, x, f, nfev);
-  return lockstep_cobyla(h, A, x, f, nfev, d_pbeg, d_pcnt, [h](const BatchArgs& a, uint64_t it, const int32_t*) {
+  return lockstep_cobyla(h, A, x, f, nfev, [h](const BatchArgs& a, uint64_t it, const int32_t*) {
     return evaluate(h, a, h->noise.eval_base + it, StreamWant::Both);
   });
 }
@@ -604,6 +627,42 @@ int finish_env_step(vqe_t* h, BatchArgs& A, const PreActionBatch& pre, const std
   return eval(A);
 }
 
+// The result of an optimiser run where vqe_batch_fetch and vqe_batch_fetch_xopt read it: x to d_x, xraw (the point before
+// an environment step's float32 rounding; x itself outside one) to d_xraw, f to d_f, nfev to d_nfev.  Blocking: the
+// host vectors may go out of scope.
+int publish_optimum(vqe_t* h, const std::vector<double>& x, const std::vector<double>& xraw, const std::vector<double>& f,
+                    const std::vector<int32_t>& nfev) {
+  if (h->total_params) {
+    HIP_TRY(h, hipMemcpyAsync(h->d_x.p, x.data(), x.size() * 8, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(h->d_xraw.p, xraw.data(), xraw.size() * 8, hipMemcpyHostToDevice, h->stream));
+  }
+  HIP_TRY(h, hipMemcpyAsync(h->d_f.p, f.data(), (size_t)h->batch * 8, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipMemcpyAsync(h->d_nfev.p, nfev.data(), (size_t)h->batch * 4, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
+  return VQE_OK;
+}
+
+// Run::Minimize / Run::EnvStep of a lock-step optimiser.  Minimize: optimise the resident batch from theta0, publish.
+// EnvStep, one CircuitEnv.step() per circuit (environment_qulacs_TN_notin_agent.py:283-291): optimise the PRE-action
+// circuits (pre_action, vqe_geo.h; built by env_step_host.h), float32 round trip, then the full circuits.
+// optimise(A2, pre, x, f, nfev): the optimiser run on the batch A2 from x (out: the result); pre: the pre-action batch
+// that A2 describes, NULL for the resident batch itself.  full_eval(A): finish_env_step's evaluation.  nfev: out.
+template <class Optimise, class FullEval>
+int minimize_or_env_step(vqe_t* h, bool env_step, BatchArgs& A, std::vector<int32_t>& nfev, Optimise optimise, FullEval full_eval) {
+  std::vector<double> f(h->batch, 0.0);
+  nfev.assign(h->batch, 0);
+  if (!env_step) {
+    std::vector<double> x(h->h_theta);
+    VQE_TRY(optimise(A, (const PreActionBatch*)nullptr, x, f, nfev));
+    return publish_optimum(h, x, x, f, nfev);
+  }
+  PreActionBatch pre;
+  BatchArgs A2 = A;
+  VQE_TRY(load_pre_action_batch(h, pre, A2));
+  VQE_TRY(optimise(A2, (const PreActionBatch*)&pre, pre.x0, f, nfev));
+  return finish_env_step(h, A, pre, nfev, full_eval);
+}
+
 // Streaming path (n >= 14): kernels per op; the COBYLA loop runs all streams in lock-step (one batched
 // evaluation per iteration), its state on the device (stream_cobyla).
 int stream_run(vqe_t* h, Run mode, BatchArgs& A) {
@@ -625,29 +684,13 @@ int stream_run(vqe_t* h, Run mode, BatchArgs& A) {
                          h->sw.states.p, h->sw.masks.p, h->sw.meta.p);
       HIP_TRY(h, hipGetLastError());
     }
-  } else if (mode == Run::Minimize) {
-    const int B = h->batch;
-    std::vector<double> x(h->h_theta), f(B, 0.0);
-    std::vector<int32_t> nfev(B);
-    VQE_TRY(stream_cobyla(h, A, h->h_par_begin, h->h_par_count, x, f, nfev, h->d_par_begin.p, h->d_par_count.p));
-    if (h->total_params)
-      HIP_TRY(h, hipMemcpyAsync(h->d_x.p, x.data(), x.size() * 8, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->d_f.p, f.data(), (size_t)B * 8, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->d_nfev.p, nfev.data(), (size_t)B * 4, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-  } else {
-    // Run::EnvStep: one CircuitEnv.step() per stream on the streaming path
-    // (environment_qulacs_TN_notin_agent.py:283-291): host-driven COBYLA on the PRE-action circuits (pre_action,
-    // vqe_geo.h; built by env_step_host.h), float32 round trip, then the full circuits.
-    PreActionBatch pre;
-    BatchArgs A2 = A;
-    VQE_TRY(load_pre_action_batch(h, pre, A2));
-    std::vector<double> f(h->batch, 0.0);
-    std::vector<int32_t> nfev(h->batch);
-    VQE_TRY(stream_cobyla(h, A2, pre.pbeg, pre.pcnt, pre.x0, f, nfev, h->d_par_begin2.p, h->d_par_count2.p));
-    rc = finish_env_step(h, A, pre, nfev, [h](const BatchArgs& a) {
-      return evaluate(h, a, h->noise.eval_base + (uint64_t)a.maxfun + 1, StreamWant::Both);
-    });
+  } else {      // Run::Minimize, Run::EnvStep
+    std::vector<int32_t> nfev;
+    rc = minimize_or_env_step(h, mode == Run::EnvStep, A, nfev,
+        [h](BatchArgs& a, const PreActionBatch* pre, std::vector<double>& x, std::vector<double>& f, std::vector<int32_t>& nf) {
+          return stream_cobyla(h, a, pre ? pre->pbeg : h->h_par_begin, pre ? pre->pcnt : h->h_par_count, x, f, nf);
+        },
+        [h](const BatchArgs& a) { return evaluate(h, a, h->noise.eval_base + (uint64_t)a.maxfun + 1, StreamWant::Both); });
   }
   if (rc) return rc;
   HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
@@ -802,43 +845,30 @@ int dm_batch_eval(vqe_t* h, const DmPlanSlot& P, const BatchArgs& A, const int32
 // Run::Energy / Minimize / EnvStep of the batched path, in the shape of stream_run's branches: the optimiser of every
 // circuit lives on the device (k_s_cobyla through lockstep_cobyla), an evaluation is dm_batch_eval.
 int dm_run_batched(vqe_t* h, Run mode, BatchArgs A) {
-  const int B = h->batch;
   VQE_TRY(dm_batch_reserve(h));
   HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
   int64_t evals = 1;
   if (mode == Run::Energy) {
     VQE_TRY(dm_batch_plan(h, h->dmb_full, h->h_gates, h->h_gate_begin, h->h_gate_count));
     VQE_TRY(dm_batch_eval(h, h->dmb_full, A, nullptr));
-  } else if (mode == Run::Minimize) {
-    VQE_TRY(dm_batch_plan(h, h->dmb_full, h->h_gates, h->h_gate_begin, h->h_gate_count));
-    std::vector<double> x(h->h_theta), f(B, 0.0);
-    std::vector<int32_t> nfev(B);
-    VQE_TRY(lockstep_cobyla(h, A, x, f, nfev, h->d_par_begin.p, h->d_par_count.p, [h](const BatchArgs& a, uint64_t, const int32_t* active) {
-      return dm_batch_eval(h, h->dmb_full, a, active);
-    }));
-    if (h->total_params) {
-      HIP_TRY(h, hipMemcpyAsync(h->d_x.p, x.data(), x.size() * 8, hipMemcpyHostToDevice, h->stream));
-      HIP_TRY(h, hipMemcpyAsync(h->d_xraw.p, x.data(), x.size() * 8, hipMemcpyHostToDevice, h->stream));
-    }
-    HIP_TRY(h, hipMemcpyAsync(h->d_f.p, f.data(), (size_t)B * 8, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->d_nfev.p, nfev.data(), (size_t)B * 4, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    evals = *std::max_element(nfev.begin(), nfev.end());
   } else {
-    // Run::EnvStep: COBYLA on the pre-action circuits (a second resident batch with a plan of its own), float32 round
-    // trip, one evaluation of the full circuits
-    PreActionBatch pre;
-    BatchArgs A2 = A;
-    VQE_TRY(load_pre_action_batch(h, pre, A2));
-    VQE_TRY(dm_batch_plan(h, h->dmb_pre, pre.gates, pre.gbeg, pre.gcnt));
-    std::vector<double> f(B, 0.0);
-    std::vector<int32_t> nfev(B);
-    VQE_TRY(lockstep_cobyla(h, A2, pre.x0, f, nfev, h->d_par_begin2.p, h->d_par_count2.p, [h](const BatchArgs& a, uint64_t, const int32_t* active) {
-      return dm_batch_eval(h, h->dmb_pre, a, active);
-    }));
-    VQE_TRY(dm_batch_plan(h, h->dmb_full, h->h_gates, h->h_gate_begin, h->h_gate_count));
-    VQE_TRY(finish_env_step(h, A, pre, nfev, [h](const BatchArgs& a) { return dm_batch_eval(h, h->dmb_full, a, nullptr); }));
-    evals = *std::max_element(nfev.begin(), nfev.end()) + 1;
+    // Run::Minimize, Run::EnvStep: the pre-action circuits of an env-step are a second resident batch with a plan of its
+    // own (dmb_pre); the plan of the full circuits is made before their evaluation
+    const auto plan_full = [h] { return dm_batch_plan(h, h->dmb_full, h->h_gates, h->h_gate_begin, h->h_gate_count); };
+    std::vector<int32_t> nfev;
+    VQE_TRY(minimize_or_env_step(h, mode == Run::EnvStep, A, nfev,
+        [&](BatchArgs& a, const PreActionBatch* pre, std::vector<double>& x, std::vector<double>& f, std::vector<int32_t>& nf) {
+          DmPlanSlot& P = pre ? h->dmb_pre : h->dmb_full;
+          VQE_TRY(pre ? dm_batch_plan(h, P, pre->gates, pre->gbeg, pre->gcnt) : plan_full());
+          return lockstep_cobyla(h, a, x, f, nf, [h, &P](const BatchArgs& t, uint64_t, const int32_t* active) {
+            return dm_batch_eval(h, P, t, active);
+          });
+        },
+        [&](const BatchArgs& a) {
+          VQE_TRY(plan_full());
+          return dm_batch_eval(h, h->dmb_full, a, nullptr);
+        }));
+    evals = *std::max_element(nfev.begin(), nfev.end()) + (mode == Run::EnvStep ? 1 : 0);
   }
   HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
   h->dm_info[2] = evals;
@@ -898,13 +928,10 @@ int dm_run(vqe_t* h, Run mode, const BatchArgs& A) {
     f[b] = fo;
     if (env_step) VQE_TRY(dm_energy_one(h, g, G, xb, &f[b]));
   }
-  if (mode != Run::Energy && h->total_params) {
-    HIP_TRY(h, hipMemcpyAsync(h->d_x.p, x.data(), x.size() * 8, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->d_xraw.p, xraw.data(), xraw.size() * 8, hipMemcpyHostToDevice, h->stream));
-  }
-  HIP_TRY(h, hipMemcpyAsync(h->d_f.p, f.data(), (size_t)B * 8, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(h->d_nfev.p, nfev.data(), (size_t)B * 4, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
+  if (mode != Run::Energy) return publish_optimum(h, x, xraw, f, nfev);
+  HIP_TRY(h, hipMemcpyAsync(h->d_f.p, f.data(), (size_t)B * 8, hipMemcpyHostToDevice, h->stream));      // (no optimum: x stays)
+  HIP_TRY(h, hipMemcpyAsync(h->d_nfev.p, nfev.data(), (size_t)B * 4, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   return VQE_OK;
 }
@@ -1066,52 +1093,29 @@ int launch_lbfgs(vqe_t* h, const BatchArgs& A, const LbfgsArgs& O) {
                            });
 }
 
-// The device L-BFGS of all resident streams in lock-step (vqe_stream_lbfgs.h), the shape of stream_cobyla: per
-// evaluation stream_energy_grad on the trial points (E into d_f, the gradient into d_grad), the running count zeroed,
-// k_sl_step - nothing travels between host and device and nothing is waited for, but for the running count every
-// kStreamPoll evaluations and at maxfun.  A: the batch to optimise (its par_begin / par_count lay out x); x: in x0, out
-// the result; nit / status stay on the device (lb_nit / lb_status).  The last launch is a gradient: the states are
-// the undone ones.
+// The device L-BFGS of all resident streams in lock-step (vqe_stream_lbfgs.h) through lockstep_run: an evaluation is
+// stream_energy_grad on the trial points (E into d_f, the gradient into d_grad), the step kernel k_sl_step, whose FIRST
+// form takes the evaluation of x0.  A: the batch to optimise (its par_begin / par_count lay out x); x: in x0, out the
+// result; nit / status stay on the device (lb_nit / lb_status).  The last launch is a gradient: the states are the
+// undone ones.
 int stream_lbfgs(vqe_t* h, BatchArgs& A, const vqe_lbfgs_opts_t& o, std::vector<double>& x, std::vector<double>& f,
                  std::vector<int32_t>& nfev) {
   const int B = h->batch;
-  const size_t PT = x.size();
-  HIP_TRY(h, h->d_x.reserve(PT + 1));
-  HIP_TRY(h, h->d_grad.reserve(PT + 1));
+  HIP_TRY(h, h->d_grad.reserve(x.size() + 1));
   HIP_TRY(h, h->lb_work.reserve((size_t)B * lbfgs_work_doubles(A.max_params, o.history)));
   HIP_TRY(h, h->lb_nit.reserve(B));
   HIP_TRY(h, h->lb_status.reserve(B));
   HIP_TRY(h, h->lb_rec.reserve(B));
-  HIP_TRY(h, h->lb_xres.reserve(PT + 1));
-  HIP_TRY(h, h->lb_fres.reserve(B));
-  HIP_TRY(h, h->lb_nfres.reserve(B));
-  HIP_TRY(h, h->lb_running.reserve(1));
-  // (trial points of streams that finish early stay where they are: the evaluations go on in lock-step over all streams)
-  if (PT) HIP_TRY(h, hipMemcpyAsync(h->d_x.p, x.data(), PT * 8, hipMemcpyHostToDevice, h->stream));
-  A.theta = h->d_x.p;
+  VQE_TRY(lockstep_begin(h, A, x));
   const StreamLbfgsArgs T{A.par_begin, A.par_count, A.max_params, h->lb_rec.p, h->d_x.p, h->d_f.p, h->d_grad.p,
-                          h->lb_running.p, h->lb_xres.p, h->lb_fres.p, h->lb_nfres.p};
+                          h->ls_running.p, h->ls_xres.p, h->ls_fres.p, h->ls_nfres.p};
   const LbfgsArgs O{o.history, o.maxiter, o.maxfun, o.max_ls, o.gtol, o.ftol, o.c1, h->lb_work.p, h->lb_nit.p, h->lb_status.p};
   h->stream_states_undone = true;
-  uint64_t it = 0;
-  int32_t running = 1;
-  while (running > 0) {
-    ++it;
-    VQE_TRY(stream_energy_grad(h->sw, A, h->stream, h->noise.eval_base + it, h->d_grad.p, h->err, h->gen));
-    HIP_TRY(h, hipMemsetAsync(h->lb_running.p, 0, 4, h->stream));
-    hipLaunchKernelGGL(it == 1 ? k_sl_step<true> : k_sl_step<false>, dim3((unsigned)B), dim3(64), 0, h->stream, T, O);
-    if (it % kStreamPoll == 0 || it >= (uint64_t)o.maxfun) {
-      HIP_TRY(h, hipMemcpyAsync(&running, h->lb_running.p, 4, hipMemcpyDeviceToHost, h->stream));
-      HIP_TRY(h, hipStreamSynchronize(h->stream));
-    }
-    if (it > (uint64_t)o.maxfun + kStreamPoll) return fail(h, VQE_ESTATE, "device L-BFGS did not terminate");
-  }
-  HIP_TRY(h, hipGetLastError());
-  if (PT) HIP_TRY(h, hipMemcpyAsync(x.data(), h->lb_xres.p, PT * 8, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(f.data(), h->lb_fres.p, (size_t)B * 8, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipMemcpyAsync(nfev.data(), h->lb_nfres.p, (size_t)B * 4, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(h, hipStreamSynchronize(h->stream));
-  return VQE_OK;
+  return lockstep_run(h, "L-BFGS", o.maxfun, x, f, nfev,
+                      [&](uint64_t it) { return stream_energy_grad(h->sw, A, h->stream, h->noise.eval_base + it, h->d_grad.p, h->err, h->gen); },
+                      [&](uint64_t it) {
+                        hipLaunchKernelGGL(it == 1 ? k_sl_step<true> : k_sl_step<false>, dim3((unsigned)B), dim3(64), 0, h->stream, T, O);
+                      });
 }
 
 // run_lbfgs on the streaming path (n >= 14, vqe_set_stream_lbfgs).  env_step: the rule of the streaming Run::EnvStep with
@@ -1120,33 +1124,19 @@ int stream_lbfgs(vqe_t* h, BatchArgs& A, const vqe_lbfgs_opts_t& o, std::vector<
 int stream_run_lbfgs(vqe_t* h, bool env_step, const vqe_lbfgs_opts_t& o) {
   BatchArgs A = make_args(h);
   A.maxfun = o.maxfun;
-  const int B = h->batch;
   h->last_run_dm = false;
   h->lb_batch = 0;
-  std::vector<double> f(B, 0.0);
-  std::vector<int32_t> nfev(B);
+  std::vector<int32_t> nfev;
   HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
-  if (!env_step) {
-    std::vector<double> x(h->h_theta);
-    VQE_TRY(stream_lbfgs(h, A, o, x, f, nfev));
-    if (h->total_params) {
-      HIP_TRY(h, hipMemcpyAsync(h->d_x.p, x.data(), x.size() * 8, hipMemcpyHostToDevice, h->stream));
-      HIP_TRY(h, hipMemcpyAsync(h->d_xraw.p, x.data(), x.size() * 8, hipMemcpyHostToDevice, h->stream));
-    }
-    HIP_TRY(h, hipMemcpyAsync(h->d_f.p, f.data(), (size_t)B * 8, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(h->d_nfev.p, nfev.data(), (size_t)B * 4, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-  } else {
-    PreActionBatch pre;
-    BatchArgs A2 = A;
-    VQE_TRY(load_pre_action_batch(h, pre, A2));
-    VQE_TRY(stream_lbfgs(h, A2, o, pre.x0, f, nfev));
-    const uint64_t eval_id = h->noise.eval_base + (uint64_t)o.maxfun + 1;
-    VQE_TRY(finish_env_step(h, A, pre, nfev, [h, eval_id](const BatchArgs& a) { return evaluate(h, a, eval_id, StreamWant::Both); }));
-    h->stream_states_undone = false;      // (the last launch was an energy: the states are those of the full circuits)
-  }
+  const uint64_t eval_id = h->noise.eval_base + (uint64_t)o.maxfun + 1;
+  VQE_TRY(minimize_or_env_step(h, env_step, A, nfev,
+      [&](BatchArgs& a, const PreActionBatch*, std::vector<double>& x, std::vector<double>& f, std::vector<int32_t>& nf) {
+        return stream_lbfgs(h, a, o, x, f, nf);
+      },
+      [h, eval_id](const BatchArgs& a) { return evaluate(h, a, eval_id, StreamWant::Both); }));
+  if (env_step) h->stream_states_undone = false;      // (the last launch was an energy: the states are those of the full circuits)
   HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
-  h->lb_batch = B;
+  h->lb_batch = h->batch;
   return VQE_OK;
 }
 

@@ -6,9 +6,9 @@
 // The optimiser's vectors - x, g, the trial point xt, its gradient gt, the direction d and the history S[m][.], Y[m][.] -
 // live in a per-workgroup slice of a global scratch buffer (rows padded to 128 bytes; a few tens of KiB, L2 resident):
 // at n = 12 psi + lambda take 128 of the 160 KiB of LDS.  The per-pair scalars s.y, y.y and the alpha of the two-loop
-// recursion sit in 512 bytes of LDS.  Wave 0 runs the update between two evaluations (lane l owns the elements
-// j = l mod 64 of every vector, so no element is ever touched by two lanes; dot products by wave_sum), the other waves
-// wait at the barrier.
+// recursion sit in 512 bytes of LDS.  Wave 0 runs the update between two evaluations, the other waves wait at the
+// barrier.  The update is lbfgs_tell below: the one device copy of the algorithm, which k_sl_step (vqe_stream_lbfgs.h)
+// runs as well, one wavefront per stream, between two evaluations of the streaming path.
 //
 // The algorithm (tests/lbfgs_helpers.py restates it decision for decision):
 //   (f, g) = eval(x0); nfev = 1; nit = 0
@@ -54,6 +54,124 @@ __device__ __forceinline__ double wave_max(double v) {
   return mx(mx(readlane_f64(v, 0), readlane_f64(v, 16)), mx(readlane_f64(v, 32), readlane_f64(v, 48)));
 }
 
+// What the optimiser carries from one evaluation to the next besides its vectors (in the LDS kernel: registers of wave 0).
+struct LbfgsState {
+  double f, t, dg;                      // value at x, step of the running line search, g.d
+  int32_t ls, cnt, head, nit;           // trials of the line search, pairs held, slot of the next pair, accepted steps
+  int32_t status, nfev;                 // LB_*; evaluations made (counted by the caller)
+};
+__host__ __device__ inline LbfgsState lbfgs_start() { return LbfgsState{0.0, 1.0, 0.0, 0, 0, 0, 0, LB_MAXITER, 0}; }
+
+// The update between two evaluations - the one copy of the algorithm above, run by ONE WAVEFRONT (lane l owns the
+// elements j = l mod 64 of every vector, so no element is ever touched by two lanes and no barrier is needed inside).
+// In: e and gt, the energy and the gradient at the trial point xt; first: that evaluation was the one of x0;
+// state.nfev counts it already.  x, g, d: rows of P doubles; S, Y: m rows of pitch pp; sy, yy, alpha: [kLbfgsMaxHistory] per-slot
+// scalars.  Out: state advanced; xt holds the next trial point unless the optimiser stopped (then x, state.f are the
+// result and state.status says why).  -> stopped
+__device__ __forceinline__ bool lbfgs_tell(LbfgsState& state, const LbfgsArgs& O, int P, int m, size_t pp, double* x, double* g,
+                                           double* d, double* S, double* Y, double* xt, const double* gt, double* sy,
+                                           double* yy, double* alpha, double e, bool first) {
+  const int lane = (int)(threadIdx.x & 63u);
+  LbfgsState st = state;      // (a local, written back at the end: stores through the reference would keep the caller's state out of registers)
+  auto dot = [&](const double* u, const double* v) {
+    double s = 0.0;
+    for (int j = lane; j < P; j += 64) s += u[j] * v[j];
+    return wave_sum(s);
+  };
+  bool stop = false, newpoint = false;
+  if (first) {
+    st.f = e;
+    newpoint = true;
+  } else if (e <= st.f + O.c1 * st.t * st.dg) {
+    double a_sy = 0.0, a_yy = 0.0;
+    for (int j = lane; j < P; j += 64) {
+      const double sv = st.t * d[j], yv = gt[j] - g[j];
+      a_sy += sv * yv;
+      a_yy += yv * yv;
+    }
+    a_sy = wave_sum(a_sy);
+    a_yy = wave_sum(a_yy);
+    if (a_sy > 1e-10 * a_yy) {       // the pair enters slot `head` (the oldest one's when m are held)
+      for (int j = lane; j < P; j += 64) {
+        S[(size_t)st.head * pp + j] = st.t * d[j];
+        Y[(size_t)st.head * pp + j] = gt[j] - g[j];
+      }
+      sy[st.head] = a_sy;
+      yy[st.head] = a_yy;
+      st.head = st.head + 1 == m ? 0 : st.head + 1;
+      st.cnt = st.cnt < m ? st.cnt + 1 : m;
+    }
+    const double conv = O.ftol * fmax(fmax(fabs(st.f), fabs(e)), 1.0);
+    const bool converged = (st.f - e) <= conv;
+    st.f = e;
+    ++st.nit;
+    newpoint = true;
+    if (converged) { stop = true; st.status = LB_FTOL; }
+  } else if (st.nfev == O.maxfun) {
+    stop = true; st.status = LB_MAXFUN;
+  } else if (++st.ls == O.max_ls) {
+    stop = true; st.status = LB_LINESEARCH;
+  } else {
+    st.t *= 0.5;
+  }
+  if (newpoint) {
+    double gmax = 0.0;
+    for (int j = lane; j < P; j += 64) {
+      const double gv = gt[j];
+      x[j] = xt[j];
+      g[j] = gv;
+      const double av = fabs(gv);
+      gmax = (av > gmax || av != av) ? av : gmax;
+    }
+    gmax = wave_max(gmax);
+    if (stop) {
+    } else if (st.nit >= O.maxiter) {
+      stop = true; st.status = LB_MAXITER;
+    } else if (gmax <= O.gtol) {
+      stop = true; st.status = LB_GTOL;
+    } else if (st.nfev >= O.maxfun) {
+      stop = true; st.status = LB_MAXFUN;
+    } else {
+      bool steepest = st.cnt == 0;
+      if (!steepest) {
+        for (int j = lane; j < P; j += 64) d[j] = g[j];
+        for (int i = 0, s = st.head; i < st.cnt; ++i) {     // newest first
+          s = s == 0 ? m - 1 : s - 1;
+          const double a = dot(S + (size_t)s * pp, d) / sy[s];
+          alpha[s] = a;
+          for (int j = lane; j < P; j += 64) d[j] -= a * Y[(size_t)s * pp + j];
+        }
+        const int newest = st.head == 0 ? m - 1 : st.head - 1;
+        const double gamma = sy[newest] / yy[newest];
+        for (int j = lane; j < P; j += 64) d[j] *= gamma;
+        int s = st.head - st.cnt;
+        if (s < 0) s += m;
+        for (int i = 0; i < st.cnt; ++i) {                   // oldest first
+          const double beta = dot(Y + (size_t)s * pp, d) / sy[s];
+          const double c = alpha[s] - beta;
+          for (int j = lane; j < P; j += 64) d[j] += c * S[(size_t)s * pp + j];
+          s = s + 1 == m ? 0 : s + 1;
+        }
+        for (int j = lane; j < P; j += 64) d[j] = -d[j];
+        st.dg = dot(g, d);
+        if (st.dg >= 0.0) { st.cnt = 0; st.head = 0; steepest = true; }
+      }
+      if (steepest) {
+        const double gn = sqrt(dot(g, g));
+        const double den = gn > 1.0 ? gn : 1.0;
+        for (int j = lane; j < P; j += 64) d[j] = -g[j] / den;
+        st.dg = dot(g, d);
+      }
+      st.t = 1.0;
+      st.ls = 0;
+    }
+  }
+  if (!stop)
+    for (int j = lane; j < P; j += 64) xt[j] = x[j] + st.t * d[j];
+  state = st;
+  return stop;
+}
+
 template <int N, bool LAM_GLOBAL>
 __global__ void __launch_bounds__(Geo<N>::NT) k_lds_minimize_lbfgs(BatchArgs A, GradHam GH, LbfgsArgs O, double2* lam_scratch) {
   constexpr int NT = Geo<N>::NT;
@@ -62,7 +180,6 @@ __global__ void __launch_bounds__(Geo<N>::NT) k_lds_minimize_lbfgs(BatchArgs A, 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const uint32_t tid = threadIdx.x;
   const int wave = (int)(tid >> 6);
-  const int lane = (int)(tid & 63u);
   unsigned char* base = smem;
   Lds L{};
   L.psi = (double2*)base; base += (size_t)16 << N;
@@ -105,117 +222,21 @@ __global__ void __launch_bounds__(Geo<N>::NT) k_lds_minimize_lbfgs(BatchArgs A, 
     compile_ops(A, b, 0, L, pa.skip, false, pa.skip_end);
     for (int j = (int)tid; j < P; j += NT) xt[j] = theta0[j];
     __syncthreads();
-    auto dot = [&](const double* u, const double* v) {
-      double s = 0.0;
-      for (int j = lane; j < P; j += 64) s += u[j] * v[j];
-      return wave_sum(s);
-    };
-    int nfev = 0;
-    // wave 0 only (the other waves never read them)
-    double f = 0.0, t = 1.0, dg = 0.0;
-    int ls = 0, cnt = 0, head = 0, nit = 0, status = LB_MAXITER;
+    // wave 0 only (the other waves count the evaluations and never read the rest)
+    LbfgsState st = lbfgs_start();
     for (;;) {
       const double e = adjoint_eval<N, LAM_GLOBAL, true>(A, GH, L, lam, gacc, xt, P, gt);
-      ++nfev;
+      ++st.nfev;
       if (pa.hole >= 0 && (int)tid == pa.hole % NT) gt[pa.hole] = 0.0;    // (the thread that stored it in adjoint_eval)
-      if (A.trace && nfev <= A.maxfun) {   // diagnostic: the trial point (optimised parameters only) and its value
-        double* tr = A.trace + ((size_t)b * A.maxfun + (size_t)(nfev - 1)) * (size_t)(1 + A.max_params);
+      if (A.trace && st.nfev <= A.maxfun) {   // diagnostic: the trial point (optimised parameters only) and its value
+        double* tr = A.trace + ((size_t)b * A.maxfun + (size_t)(st.nfev - 1)) * (size_t)(1 + A.max_params);
         if (tid == 0) tr[0] = e;
         for (int j = (int)tid; j < P; j += NT)
           if (j != pa.hole) tr[1 + j - (pa.hole >= 0 && j > pa.hole)] = xt[j];
       }
       __syncthreads();                     // gt is complete
       if (wave == 0) {
-        bool stop = false, newpoint = false;
-        if (nfev == 1) {
-          f = e;
-          newpoint = true;
-        } else if (e <= f + O.c1 * t * dg) {
-          double a_sy = 0.0, a_yy = 0.0;
-          for (int j = lane; j < P; j += 64) {
-            const double sv = t * d[j], yv = gt[j] - g[j];
-            a_sy += sv * yv;
-            a_yy += yv * yv;
-          }
-          a_sy = wave_sum(a_sy);
-          a_yy = wave_sum(a_yy);
-          if (a_sy > 1e-10 * a_yy) {       // the pair enters slot `head` (the oldest one's when m are held)
-            for (int j = lane; j < P; j += 64) {
-              S[(size_t)head * pp + j] = t * d[j];
-              Y[(size_t)head * pp + j] = gt[j] - g[j];
-            }
-            sy[head] = a_sy;
-            yy[head] = a_yy;
-            head = head + 1 == m ? 0 : head + 1;
-            cnt = cnt < m ? cnt + 1 : m;
-          }
-          const double conv = O.ftol * fmax(fmax(fabs(f), fabs(e)), 1.0);
-          const bool converged = (f - e) <= conv;
-          f = e;
-          ++nit;
-          newpoint = true;
-          if (converged) { stop = true; status = LB_FTOL; }
-        } else if (nfev == O.maxfun) {
-          stop = true; status = LB_MAXFUN;
-        } else if (++ls == O.max_ls) {
-          stop = true; status = LB_LINESEARCH;
-        } else {
-          t *= 0.5;
-        }
-        if (newpoint) {
-          double gmax = 0.0;
-          for (int j = lane; j < P; j += 64) {
-            const double gv = gt[j];
-            x[j] = xt[j];
-            g[j] = gv;
-            const double av = fabs(gv);
-            gmax = (av > gmax || av != av) ? av : gmax;
-          }
-          gmax = wave_max(gmax);
-          if (stop) {
-          } else if (nit >= O.maxiter) {
-            stop = true; status = LB_MAXITER;
-          } else if (gmax <= O.gtol) {
-            stop = true; status = LB_GTOL;
-          } else if (nfev >= O.maxfun) {
-            stop = true; status = LB_MAXFUN;
-          } else {
-            bool steepest = cnt == 0;
-            if (!steepest) {
-              for (int j = lane; j < P; j += 64) d[j] = g[j];
-              for (int i = 0, s = head; i < cnt; ++i) {           // newest first
-                s = s == 0 ? m - 1 : s - 1;
-                const double a = dot(S + (size_t)s * pp, d) / sy[s];
-                alpha[s] = a;
-                for (int j = lane; j < P; j += 64) d[j] -= a * Y[(size_t)s * pp + j];
-              }
-              const int newest = head == 0 ? m - 1 : head - 1;
-              const double gamma = sy[newest] / yy[newest];
-              for (int j = lane; j < P; j += 64) d[j] *= gamma;
-              int s = head - cnt;
-              if (s < 0) s += m;
-              for (int i = 0; i < cnt; ++i) {                      // oldest first
-                const double beta = dot(Y + (size_t)s * pp, d) / sy[s];
-                const double c = alpha[s] - beta;
-                for (int j = lane; j < P; j += 64) d[j] += c * S[(size_t)s * pp + j];
-                s = s + 1 == m ? 0 : s + 1;
-              }
-              for (int j = lane; j < P; j += 64) d[j] = -d[j];
-              dg = dot(g, d);
-              if (dg >= 0.0) { cnt = 0; head = 0; steepest = true; }
-            }
-            if (steepest) {
-              const double gn = sqrt(dot(g, g));
-              const double den = gn > 1.0 ? gn : 1.0;
-              for (int j = lane; j < P; j += 64) d[j] = -g[j] / den;
-              dg = dot(g, d);
-            }
-            t = 1.0;
-            ls = 0;
-          }
-        }
-        if (!stop)
-          for (int j = lane; j < P; j += 64) xt[j] = x[j] + t * d[j];
+        const bool stop = lbfgs_tell(st, O, P, m, pp, x, g, d, S, Y, xt, gt, sy, yy, alpha, e, st.nfev == 1);
         ctl[0] = stop ? 1 : 0;             // (every lane stores the same word)
       }
       __syncthreads();                     // xt, x and the stop flag are complete
@@ -226,18 +247,18 @@ __global__ void __launch_bounds__(Geo<N>::NT) k_lds_minimize_lbfgs(BatchArgs A, 
       A.xraw[p0 + j] = v;
       A.xout[p0 + j] = A.env_step ? (double)(float)v : v;
     }
-    double fret = f;
+    double fret = st.f;
     if (A.env_step) {
       // CircuitEnv.step: float32 round trip, then the energy of the FULL circuit (no gradient wanted)
       __syncthreads();                     // xout complete
       compile_ops(A, b, 0, L);
       fret = adjoint_eval<N, LAM_GLOBAL, false>(A, GH, L, lam, gacc, A.xout + p0, P, gt);
     }
-    if (tid == 0) {                        // (a thread of wave 0: f, nit, status are its own)
+    if (tid == 0) {                        // (a thread of wave 0: st is its own)
       A.fout[b] = fret;
-      A.nfev[b] = nfev;
-      O.nit[b] = nit;
-      O.status[b] = status;
+      A.nfev[b] = st.nfev;
+      O.nit[b] = st.nit;
+      O.status[b] = st.status;
     }
     __syncthreads();                       // the LDS and the scratch slice are reused by the next circuit of a persistent grid
   }

@@ -523,6 +523,38 @@ def test_noise_trajectories_on_the_streaming_path(tq):
         eng.close()
 
 
+def test_streaming_minimize_publishes_xopt(tq):
+    """vqe_batch_run_minimize at n = 14 (device COBYLA in lock-step): outside an environment step nothing is rounded, so
+    vqe_batch_fetch_xopt returns the optimum, vqe_batch_fetch's x, as after every other optimiser run.  Three circuits of
+    4, 6 and 8 gates (2, 1 and 5 parameters) and maxfun = 20: with rhoend = 0.05 the streams stop at different
+    evaluations, between the host's looks at the running count (every 8 evaluations and at maxfun); every stream is what
+    its circuit gives alone (vqe_minimize_cobyla), bit for bit."""
+    n, maxfun, rhoend = 14, 20, 0.05
+    rng = np.random.default_rng(1421)
+    psi0 = random_state(n, rng)
+    ham = random_hamiltonian(n, 20, rng)
+    raws = [random_gates(n, G, rng) for G in (4, 6, 8)]
+    assert len({g[4].size for g in raws}) == 3
+    circs = [tq.Circuit(*g[:4], g[4].size) for g in raws]
+    eng = _engine(tq, n, psi0, ham)
+    eng.batch_load(circs, [g[4] for g in raws])
+    eng.batch_run_minimize(1.0, rhoend, maxfun)
+    x, f, nfev = eng.batch_fetch()
+    xopt = eng.batch_fetch_xopt()
+    print(f"nfev {nfev.tolist()}  |x - xopt| {np.abs(x - xopt).max():.3e}")
+    assert np.array_equal(x, xopt)
+    assert len(set(nfev.tolist())) > 1 and nfev.max() <= maxfun, nfev
+    off = 0
+    for b, (c, g) in enumerate(zip(circs, raws)):
+        eng.set_circuit(c)
+        x1, f1, nfev1 = eng.minimize_cobyla(g[4], 1.0, rhoend, maxfun)
+        assert np.array_equal(x[off:off + g[4].size], x1) and f[b] == f1 and nfev[b] == nfev1, b
+        assert abs(vo.energy_pauli(vo.run_circuit(psi0, *g[:4], x1), *ham) - f1) < E_TOL
+        off += g[4].size
+    assert off == x.size
+    eng.close()
+
+
 @pytest.mark.parametrize("n,G,seed", [(9, 40, 0), (10, 60, 1), (11, 90, 2), (13, 70, 3), (10, 170, 4), (12, 150, 5)])
 def test_register_path_sizes(tq, n, G, seed):
     """n = 10..13 run with the amplitudes in registers (coset layouts), n = 9 is the largest

@@ -194,6 +194,29 @@ def test_run_state_does_not_leak():
     assert all(np.array_equal(a, b) for a, b in zip(after, fresh))
 
 
+def test_one_driver_serves_both_optimisers_on_one_handle():
+    """L-BFGS, COBYLA, L-BFGS on one handle: the two optimisers share the host's lock-step loop, its result buffers and
+    its count of running streams, and nothing of a run shows in the next one."""
+    case, circs, thetas = _batch()
+    eng = _engine(case["n"], case["ham"], case["psi0"])
+
+    def lbfgs_run():
+        eng.batch_load(circs, thetas)
+        eng.batch_run_minimize_lbfgs(**sh.BATCH_OPTS)
+        return (*eng.batch_fetch(), *eng.batch_fetch_lbfgs_info())
+
+    def cobyla_run(e):
+        e.batch_load(circs, thetas)
+        e.batch_run_minimize(maxfun=12)
+        return (*e.batch_fetch(), e.batch_fetch_xopt())
+
+    first, between, again = lbfgs_run(), cobyla_run(eng), lbfgs_run()
+    assert all(np.array_equal(a, b) for a, b in zip(first, again))          # x, f, nfev, nit, status
+    fresh = cobyla_run(_engine(case["n"], case["ham"], case["psi0"], stream_lbfgs=False))
+    assert all(np.array_equal(a, b) for a, b in zip(between, fresh))
+    assert np.array_equal(between[0], between[3])
+
+
 def test_switch_and_refusals():
     import tensorrl_qas_amd as tq
     n = 14

@@ -159,7 +159,19 @@ int vqe_comm_destroy(vqe_t* h);
 int vqe_term_owner(int n_qubits, int n_terms, const uint64_t* xmask, int world, int32_t* owner);
 /* Stochastic Pauli noise (qulacs DepolarizingNoise / TwoQubitDepolarizingNoise
  * semantics: each non-identity Pauli with probability p/3 resp. p/15, one trajectory per
- * evaluation).  The draw for (stream, evaluation, gate) is a pure function of `seed`. */
+ * evaluation).  The draw for (stream, evaluation, gate) is a pure function of `seed`; stream = position of the
+ * circuit in the resident batch, evaluation = the handle's evaluation counter:
+ *   - vqe_create and every vqe_set_noise set the counter to 0 (nothing else does: not vqe_set_shot_noise, not a new
+ *     Hamiltonian, circuit, batch or initial state);
+ *   - an energy run (vqe_energy*, vqe_batch_run_energy) or a state (vqe_get_state*) draws at the counter, then adds 1;
+ *   - a gradient-free optimiser run (vqe_minimize_cobyla, vqe_batch_run_minimize, vqe_batch_run_env_step) with `maxfun`
+ *     draws its k-th evaluation at counter + k (k = 1 .. nfev), an env-step's final evaluation of the full circuit at
+ *     counter + maxfun + 1, then adds maxfun + 1 - whatever nfev was;
+ *   - exact-channel runs (the energies and optimiser runs of vqe_set_noise_mode 1), gradient and device L-BFGS runs,
+ *     vqe_batch_run_reduction and every refused call leave it unchanged.  vqe_get_state* has no exact-channel form: in
+ *     mode 1 too it is a trajectory at the counter and adds 1.  The counter counts with noise off as well.
+ * One seed per handle: vqe_set_noise and vqe_set_shot_noise both set it, for the Pauli draws and the shot draws alike,
+ * and the later call wins.  VQE_EINVAL (handle unchanged) for a probability outside [0, 1]. */
 int vqe_set_noise(vqe_t* h, double p1, double p2, uint64_t seed);
 /* How the noise gates of a circuit are evaluated.  0 (default): one Pauli trajectory per evaluation, as qulacs does
  * inside update_quantum_state (VQE_qulacs_TN_notin_RL_noise.py:94-101).  1: the exact channel those draws sample
@@ -199,7 +211,11 @@ int vqe_noise_mode_info(vqe_t* h, int32_t out[2]);
  * (environments/VQAs/VQE_qulacs_TN_notin_RL_noise_restricted.py:47-48,84-96): every evaluation
  * returns E + weights . N(0, sigma^2 I), sigma = n_shots^-1/2, i.e. E + sigma_total * N(0,1)
  * with sigma_total = sigma * |weights|_2 (the same distribution, one draw per evaluation from
- * the seeded counter-based generator).  0 switches it off. */
+ * the seeded counter-based generator).  0 switches it off.  The draw of (stream, evaluation) is numbered by the same
+ * evaluation counter as the Pauli draws (see vqe_set_noise); this call does NOT restart it.  `seed` replaces the
+ * handle's one seed - also for the Pauli draws of a vqe_set_noise made earlier, and also when sigma_total is 0 -, and
+ * a later vqe_set_noise replaces it in turn: callers that want both noises pass the same seed to both (CircuitEnv
+ * does), or call vqe_set_noise first and know that the second seed is the one in force. */
 int vqe_set_shot_noise(vqe_t* h, double sigma_total, uint64_t seed);
 
 /* ---- one circuit ---------------------------------------------------------------------
@@ -238,7 +254,14 @@ int vqe_minimize_cobyla(vqe_t* h, const double* x0, double rhobeg, double rhoend
  * vqe_batch_load copies the description (and x0 / theta) into device memory; the
  * *_run calls only launch device work on resident data and never modify it (a run can be
  * repeated); vqe_batch_fetch copies results back.  replaces: B independent CircuitEnv.scipy_optim / get_energy calls
- * (environment_qulacs_TN_notin_agent.py:442-482). */
+ * (environment_qulacs_TN_notin_agent.py:442-482).
+ * A handle holds ONE resident batch.  vqe_batch_load replaces it and clears the new gates of vqe_batch_set_new_gate
+ * (an env-step after a load without a new vqe_batch_set_new_gate optimises the full circuits); a refused load
+ * (VQE_EINVAL) leaves the previous batch, its new gates and its fetchable results as they were.  The one-circuit calls
+ * (vqe_energy*, vqe_energy_grad_batch, vqe_get_state*, vqe_minimize_cobyla, vqe_minimize_lbfgs) load the circuit of
+ * vqe_set_circuit as a batch of their own: after one of them the resident batch is THAT circuit (`batch` copies of it for
+ * the *_batch calls), and vqe_batch_run_* / vqe_batch_fetch* serve it, not the batch loaded before - load again to go
+ * back.  Results on the device (x, xopt, f, nfev, gradients, traces) belong to the last run: another run overwrites them. */
 int vqe_batch_load(vqe_t* h, int batch, const int64_t* gate_off, const int32_t* kind,
                    const int32_t* q0, const int32_t* q1, const int32_t* param_idx,
                    const int64_t* par_off, const double* theta0);

@@ -169,15 +169,21 @@ int upload(vqe_t* h, DevBuf<T>& b, const T* src, size_t n) {
 template <class T>
 int upload(vqe_t* h, DevBuf<T>& b, const std::vector<T>& src) { return upload(h, b, src.data(), src.size()); }
 
-// Build (or rebuild after re-sharding) the device Hamiltonian: plan the layout on the host (ham_layout.h), upload it.
-int build_hamiltonian(vqe_t* h) {
-  ++h->gen;
-  ++h->ham_ver;
+// Build (or rebuild after re-sharding) the device Hamiltonian: plan the layout of shard (rank, world) of H - a new
+// operator, or NULL for the one the handle holds - on the host (ham_layout.h), upload it.  A plan that fails leaves the
+// handle as it was: host copy, shard numbers and generation counters change only once the plan stands, together.
+int build_hamiltonian(vqe_t* h, HamHost* H, int rank, int world) {
   static const bool units_on = [] { const char* e = std::getenv("VQE_UNITS"); return !(e && e[0] == '0'); }();   // A/B knob
   HamLayout L;
   std::string err;
-  if (!plan_hamiltonian(h->ham_host, h->n, h->lds_path, h->shard_rank, h->shard_world, units_on, L, err))
+  if (!plan_hamiltonian(H ? *H : h->ham_host, h->n, h->lds_path, rank, world, units_on, L, err))
     return fail(h, VQE_EINVAL, err);
+  if (H) h->ham_host = std::move(*H);
+  h->shard_rank = rank;
+  h->shard_world = world;
+  h->ham_set = true;
+  ++h->gen;
+  ++h->ham_ver;
   VQE_TRY(upload(h, h->d_gx, L.gx));
   VQE_TRY(upload(h, h->d_tab_r, L.tab_r));
   VQE_TRY(upload(h, h->d_tab_i, L.tab_i));
@@ -880,7 +886,8 @@ int dm_run_batched(vqe_t* h, Run mode, BatchArgs A) {
 // The resident batch in exact channel mode: Run::Energy, or COBYLA (host-driven on exact energies; Run::EnvStep: on the
 // pre-action circuit, then float32 round trip and the energy of the full circuit, as the fused kernel does).  After
 // vqe_set_dm_batched: dm_run_batched, behind the same refusals.
-int dm_run(vqe_t* h, Run mode, const BatchArgs& A) {
+// What the exact channel mode cannot serve (checked by run(), before anything of the handle changes)
+int dm_refusal(vqe_t* h) {
   if (h->n < 2 || h->n > 13) return fail(h, VQE_EINVAL, "the exact channel mode (density matrix) serves 2 <= n_qubits <= 13");
   // the superoperator blocks (dm_host.h) are built from CNOT, RX, RY, RZ and the two channels only: refused before anything is launched
   for (int b = 0; b < h->batch; ++b)
@@ -888,6 +895,10 @@ int dm_run(vqe_t* h, Run mode, const BatchArgs& A) {
       if (gate_is_rot2(h->h_gates[i].kind))
         return fail(h, VQE_EINVAL, "the exact channel mode does not take RXX / RYY / RZZ gates (use Pauli-trajectory noise, vqe_set_noise_mode 0)");
   if (h->amp_world > 1) return fail(h, VQE_ESTATE, "the exact channel mode has no amplitude sharding");
+  return VQE_OK;
+}
+
+int dm_run(vqe_t* h, Run mode, const BatchArgs& A) {
   VQE_TRY(dm_prepare_ham(h));
   std::fill(h->dm_info, h->dm_info + 4, (int64_t)0);
   if (h->dm_batched != 0) return dm_run_batched(h, mode, A);
@@ -956,10 +967,23 @@ int run(vqe_t* h, Run mode, double rhobeg, double rhoend, int maxfun) {
                                "vqe_cobyla_ask/tell and sum the partial energies of all ranks");
   if (mode == Run::Reduce && h->lds_path)
     return fail(h, VQE_ESTATE, "the reduction-only launch exists on the streaming path (n >= 14) only");
+  // Everything else a run can be refused for, before the trace, the L-BFGS info and the timing of the previous run are
+  // given up: a refused run leaves the handle and what can be fetched from it as they were.
+  const bool exact = h->noise_mode == 1 && (mode == Run::Energy || optimise);
+  if (exact) {
+    VQE_TRY(dm_refusal(h));
+  } else if (h->lds_path) {
+    const size_t lds = lds_bytes(h->n, A.max_ops, A.max_params, A.ham.n_groups, A.max_pair, optimise && wide_launch(h->n, A.max_params));
+    if (const char* why = lds_launch_refusal(h->n, lds, A.max_ops, (size_t)h->lds_per_cu)) return fail(h, VQE_EINVAL, why);
+  } else if (mode == Run::Reduce) {
+    if (h->stream_states_undone)
+      return fail(h, VQE_ESTATE, "the states of the last run were undone by its gradient sweep: run the energy first");
+    if (h->sw.states.cap < ((size_t)h->batch << h->n)) return fail(h, VQE_ESTATE, "no states: run the energy first");
+  }
   if (h->trace_on && optimise && h->lds_path) VQE_TRY(arm_trace(h, A, maxfun));
   h->last_run_dm = false;
   h->lb_batch = 0;             // fout / nfev are about to be another run's: the L-BFGS info of an earlier one is stale
-  if (h->noise_mode == 1 && (mode == Run::Energy || optimise)) return dm_run(h, mode, A);
+  if (exact) return dm_run(h, mode, A);
   VQE_TRY(h->lds_path ? dispatch_lds(h, mode, A) : stream_run(h, mode, A));
   // every evaluation of a stochastic run consumes fresh trajectory numbers
   if (mode != Run::Reduce) h->noise.eval_base += (optimise ? (uint64_t)maxfun + 1 : 1);
@@ -1283,10 +1307,10 @@ int vqe_set_hamiltonian_pauli(vqe_t* h, int n_terms, const uint64_t* xmask, cons
   if (n_terms < 0 || (n_terms > 0 && (!xmask || !zmask || !coeff)))
     return fail(h, VQE_EINVAL, "bad Hamiltonian arguments");
   HIP_TRY(h, hipSetDevice(h->dev));
-  if (!ham_from_paulis(h->n, n_terms, xmask, zmask, coeff, h->ham_host))
+  HamHost H;      // grouped apart from the handle: ham_from_paulis stops at the first bad mask, with H half written
+  if (!ham_from_paulis(h->n, n_terms, xmask, zmask, coeff, H))
     return fail(h, VQE_EINVAL, "Pauli mask uses a qubit >= n_qubits");
-  h->ham_set = true;
-  return build_hamiltonian(h);
+  return build_hamiltonian(h, &H, h->shard_rank, h->shard_world);
 }
 
 int vqe_set_hamiltonian_dense(vqe_t* h, const double* op_re_im, double tol) {
@@ -1458,9 +1482,9 @@ int vqe_unit_bank_score(vqe_t* h, double out[4]) {
 int vqe_set_term_shard(vqe_t* h, int rank, int world) {
   if (!h) return VQE_EINVAL;
   if (world < 1 || rank < 0 || rank >= world) return fail(h, VQE_EINVAL, "bad shard rank/world");
+  if (h->ham_set) { HIP_TRY(h, hipSetDevice(h->dev)); return build_hamiltonian(h, nullptr, rank, world); }
   h->shard_rank = rank;
   h->shard_world = world;
-  if (h->ham_set) { HIP_TRY(h, hipSetDevice(h->dev)); return build_hamiltonian(h); }
   return VQE_OK;
 }
 

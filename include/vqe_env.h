@@ -86,7 +86,8 @@ int vqe_vecenv_opt_ang(vqe_vecenv_t* v, int32_t env, double* out, int32_t* n);
  * (vqe_batch_run_env_step_lbfgs with `opts`, which must not be NULL: VQE_EINVAL; start from vqe_lbfgs_default_opts and
  * set maxfun to the config's maxfun to keep nfev comparable with COBYLA's budget).
  * The reference has no counterpart: its optimiser is the config's optim_alg, one environment at a time.  Refused
- * (VQE_ESTATE) between step_begin and step_end, and for VQE_ENV_OPT_LBFGS on a noisy batch. */
+ * (VQE_ESTATE) between step_begin and step_end, and for VQE_ENV_OPT_LBFGS on a noisy batch unless the engine is in the
+ * exact channel mode (vqe_set_noise_mode 1; its steps then need vqe_set_dm_batched and vqe_set_dm_grad). */
 enum { VQE_ENV_OPT_COBYLA = 0, VQE_ENV_OPT_LBFGS = 1 };
 int vqe_vecenv_set_optimizer(vqe_vecenv_t* v, int kind, const vqe_lbfgs_opts_t* opts);
 /* kernel time of the last launch (HIP events) */

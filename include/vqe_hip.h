@@ -199,6 +199,16 @@ int vqe_set_dm_batched(vqe_t* h, int max_resident);
  * largest nfev of a minimisation, one more for an env-step), [3] block levels (sweeps per chunk and evaluation: the
  * largest block count of a resident circuit).  All 0 after a serial run. */
 int vqe_dm_batch_info(vqe_t* h, int64_t out[4]);
+/* Exact channel mode on the batched path only: serve vqe_energy_grad_batch, vqe_batch_run_energy_grad /
+ * vqe_batch_fetch_grad and the device L-BFGS (vqe_minimize_lbfgs, vqe_batch_run_minimize_lbfgs / _env_step_lbfgs) by the
+ * adjoint gradient of tr(rho H): forward sweeps with rho_0 .. rho_L kept, Lambda = conj(H) swept back with the adjoint
+ * blocks, one 16 x 16 matrix per block contracted with the block's derivative.  0 (default): those calls are refused in
+ * mode 1 as before.  Accepted on any handle; it takes effect in mode 1 with vqe_set_dm_batched != 0 (with the serial
+ * path those calls stay refused, VQE_ESTATE).  A resident circuit costs levels + 2 density matrices, so out of the same
+ * budget (max_resident density matrices, or a quarter of the free memory) fewer circuits are resident than in an
+ * energy run - vqe_dm_batch_info reports the count - and VQE_ENOMEM when not even one fits.  The gradient of a circuit
+ * has the same bits whatever the batch around it, its position and max_resident.  Noise counter: unchanged. */
+int vqe_set_dm_grad(vqe_t* h, int enable);
 /* host only (needs no device): the superoperator blocks the exact channel mode would sweep for this circuit - windows[2k],
  * windows[2k+1] = the two qubits (a, b) of block k, S[k][2][16][16] = real and imaginary part of its 16 x 16 matrix, entry
  * index = ket_a + 2 ket_b + 4 bra_a + 8 bra_b.  windows == NULL or S == NULL: only the count.  For tests of the fusion. */
@@ -236,8 +246,10 @@ int vqe_energy_batch(vqe_t* h, int batch, const double* theta /* batch x n_param
  * vqe_set_stream_grad(h, 1) was called; then the streaming path computes it (forward sweeps, lambda = H psi in a second
  * state-sized buffer, backward sweeps over both).  Such a call undoes the circuit on the resident states: a
  * vqe_batch_run_reduction right after it is refused with VQE_ESTATE.  Refused with
- * VQE_ESTATE while Pauli noise (p1 or p2 > 0), the exact channel noise mode, shot noise or an amplitude shard is set
- * on the handle.  On a term-sharded handle energy and gradient are the shard's partial sums. */
+ * VQE_ESTATE while Pauli noise (p1 or p2 > 0), shot noise or an amplitude shard is set on the handle, and in the
+ * exact channel noise mode unless vqe_set_dm_grad(h, 1) and vqe_set_dm_batched(h, != 0) were called: then the batched
+ * path computes the gradient of tr(rho H) for the channel of vqe_set_noise, whatever p1 / p2.  On a term-sharded
+ * handle energy and gradient are the shard's partial sums. */
 int vqe_energy_grad_batch(vqe_t* h, int batch, const double* theta /* batch x P */,
                           double* energy /* batch */, double* grad /* batch x P */);
 /* replaces: circuit.update_quantum_state(state); state.get_vector()  (:84-85) */
@@ -315,8 +327,11 @@ int vqe_batch_fetch_xopt(vqe_t* h, double* x /* sum of n_params */);
  * algorithm runs on the streaming path, all resident streams in lock-step: per evaluation the streaming adjoint gradient
  * and one small update kernel (csrc/vqe_stream_lbfgs.h), nothing copied to the host in between.  A
  * vqe_batch_run_reduction right after such a minimise run is refused with VQE_ESTATE (its last launch was a gradient);
- * after an env-step it is accepted.  Refused with VQE_ESTATE, before anything is launched, while Pauli noise, the
- * exact channel mode, shot noise, an amplitude shard or a term shard (the line search needs the full energy) is set;
+ * after an env-step it is accepted.  Exact channel mode after vqe_set_dm_grad(h, 1) and vqe_set_dm_batched(h, != 0):
+ * the same lock-step form on the batched density-matrix path (csrc/vqe_dm_grad.h), an env-step on the
+ * pre-action circuits.  Refused with VQE_ESTATE, before anything is launched, while Pauli noise, the exact channel
+ * mode without those two switches, shot noise, an amplitude shard or a term shard (the line search needs the full
+ * energy) is set;
  * VQE_EINVAL for history outside 1..16, maxiter < 0, maxfun < 1, max_ls < 1, a negative tolerance or c1 outside (0, 1).
  * opts == NULL: the defaults. */
 typedef struct { int32_t history; int32_t maxiter; int32_t maxfun; int32_t max_ls;

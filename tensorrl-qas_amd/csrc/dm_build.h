@@ -1,6 +1,7 @@
 // dm_build.h - the per-block builder of the batched exact channel mode: the 16 x 16 superoperator of one block from its
 // member list (dm_host.h: DmBatchTables) and the circuit's angles.  One function, compiled for the device by k_dm_build
-// (vqe_dm_batch.h) and for the host by tests/cpp/dm_plan_check.cpp, which holds it against dm_fill_blocks.
+// (vqe_dm_batch.h) and for the host by tests/cpp/dm_plan_check.cpp, which holds it against dm_fill_blocks.  Below it the
+// derivative chain of the adjoint gradient (vqe_dm_grad.h): the same product with a rotation's generator behind it.
 //
 // Fixed order: S = identity; for the members in list order S <- G S, every entry of the product summed over the inner
 // index ascending.  The unit of work is ONE ENTRY (r, c) of one product, which is what a thread of k_dm_build owns; the
@@ -61,6 +62,65 @@ VQE_HD inline void dm_build_entry(int kind, int pos, double cs, double sn, const
   }
   outr = vr;
   outi = vi;
+}
+
+// ---- the derivative chain (vqe_dm_grad.h) -------------------------------------------------------------
+// A rotation member is rho -> U rho U^+ with U = exp(+i theta/2 P), so d/dtheta of it is D G with the fixed generator
+// D rho = (i/2) (P rho - rho P):  D[(i, j), (i', j')] = (i/2) (P[i][i'] [j == j'] - [i == i'] P[j'][j]), P acting on
+// window position pos.  dS/dtheta of a block is its member list with D inserted behind the member.
+VQE_HD inline void dm_generator_entry(int kind, int pos, int r, int k, double& gr, double& gi) {
+  const int i = r & 3, j = r >> 2, ip = k & 3, jp = k >> 2, other = pos ^ 1;
+  gr = 0.0;
+  gi = 0.0;
+  for (int side = 0; side < 2; ++side) {      // 0: (i/2) P on the ket index, 1: -(i/2) P^T on the bra index
+    const int x = side ? jp : i, y = side ? j : ip;      // the entry P[x][y] that is wanted
+    if ((side ? i != ip : j != jp) || ((x >> other) & 1) != ((y >> other) & 1)) continue;
+    const int a = (x >> pos) & 1, b = (y >> pos) & 1;
+    double pr = 0.0, pi = 0.0;
+    if (kind == G_RX) pr = a != b ? 1.0 : 0.0;
+    else if (kind == G_RY) pi = a == b ? 0.0 : (a == 0 ? -1.0 : 1.0);
+    else pr = a != b ? 0.0 : (a == 0 ? 1.0 : -1.0);
+    const double s = side ? -0.5 : 0.5;      // (+-i/2) (pr + i pi)
+    gr += -s * pi;
+    gi += s * pr;
+  }
+}
+
+// entry (r, c) of D S: dm_build_entry with the generator in the member's place
+VQE_HD inline void dm_generator_apply_entry(int kind, int pos, const double* sr, const double* si, int r, int c, double& outr, double& outi) {
+  double vr = 0.0, vi = 0.0;
+  for (int k = 0; k < 16; ++k) {
+    double gr, gi;
+    dm_generator_entry(kind, pos, r, k, gr, gi);
+    const double xr = sr[k * 16 + c], xi = si[k * 16 + c];
+    vr += gr * xr - gi * xi;
+    vi += gr * xi + gi * xr;
+  }
+  outr = vr;
+  outi = vi;
+}
+
+// dS/dtheta of one block for its rotation member `which` (index into the block's member list), into (outr, outi)
+// [16][16] row-major: the chain of k_dm_build with D behind that member.  mem: the block's members (3 ints each),
+// cs / sn: cos / sin of half the angle of every member (1, 0 where it is no rotation).  tr / ti: 2 x 256 doubles of
+// work space.  The serial form of what a workgroup of k_dmg_contract runs entry by entry; tests/cpp/dm_grad_check.cpp
+// holds it against the exact shift of dm_fill_blocks.
+VQE_HD inline void dm_block_derivative(const int32_t* mem, int n_mem, int which, const double* cs, const double* sn, const double* dep,
+                                       double* outr, double* outi, double* tr, double* ti) {
+  double* cr = outr; double* ci = outi; double* nr = tr; double* ni = ti;
+  for (int t = 0; t < 256; ++t) { cr[t] = (t >> 4) == (t & 15) ? 1.0 : 0.0; ci[t] = 0.0; }
+  for (int m = 0; m < n_mem; ++m) {
+    const int kind = mem[3 * m], pos = mem[3 * m + 1];
+    for (int pass = 0; pass < (m == which ? 2 : 1); ++pass) {
+      for (int t = 0; t < 256; ++t) {
+        if (pass == 0) dm_build_entry(kind, pos, cs[m], sn[m], dep, cr, ci, t >> 4, t & 15, nr[t], ni[t]);
+        else dm_generator_apply_entry(kind, pos, cr, ci, t >> 4, t & 15, nr[t], ni[t]);
+      }
+      double* s = cr; cr = nr; nr = s;
+      s = ci; ci = ni; ni = s;
+    }
+  }
+  if (cr != outr) for (int t = 0; t < 256; ++t) { outr[t] = cr[t]; outi[t] = ci[t]; }
 }
 
 }  // namespace vqe

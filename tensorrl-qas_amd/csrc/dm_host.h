@@ -210,4 +210,18 @@ inline void dm_flatten_plans(int n, int batch, const GateRec* gates, const int64
   dm_depol_tables(p1, p2, T.dep);
 }
 
+// ---- the adjoint gradient of the batched path (vqe_dm_grad.h) ------------------------------------------------------
+// A gradient evaluation keeps rho_0 .. rho_L and Lambda of every resident circuit: levels + 2 density matrices.  The
+// circuits resident at a time for a budget of `budget_bytes` (max_resident density matrices, or a quarter of the free
+// memory - the budget of an energy run): 0 when not even one fits, never more than the batch or the y extent of a grid.
+inline int dm_grad_resident(size_t budget_bytes, int n, int levels, int batch) {
+  const size_t per_circuit = ((size_t)levels + 2) * (sizeof(double) * 2 << (2 * n));
+  return (int)std::min<size_t>(std::min<size_t>(budget_bytes / per_circuit, (size_t)std::max(batch, 0)), 65535);
+}
+// The groups of 16 window entries of a level are summed into M in tiles of 16 groups; a partial sum covers
+// dm_grad_tiles_per_partial(n) consecutive tiles, a function of n alone: at most 256 partials, 4 tiles or more each.
+inline uint32_t dm_grad_tiles(int n) { return (uint32_t)(((((size_t)1 << (2 * n)) / 16) + 15) / 16); }
+inline uint32_t dm_grad_tiles_per_partial(int n) { return std::max<uint32_t>(4u, (dm_grad_tiles(n) + 255u) / 256u); }
+inline uint32_t dm_grad_partials(int n) { return (dm_grad_tiles(n) + dm_grad_tiles_per_partial(n) - 1u) / dm_grad_tiles_per_partial(n); }
+
 }  // namespace vqe

@@ -449,7 +449,11 @@ int vqe_vecenv_set_optimizer(vqe_vecenv_t* v, int kind, const vqe_lbfgs_opts_t* 
   if (kind != VQE_ENV_OPT_COBYLA && kind != VQE_ENV_OPT_LBFGS) return fail(v, VQE_EINVAL, "unknown optimiser kind");
   if (v->pending) return fail(v, VQE_ESTATE, "set_optimizer between step_begin and step_end");
   if (kind == VQE_ENV_OPT_LBFGS) {
-    if (v->cfg.noisy) return fail(v, VQE_ESTATE, "the device L-BFGS takes no noisy batch");
+    // a noisy batch has gradients in the engine's exact channel mode only (there the engine checks its own switches,
+    // vqe_set_dm_batched and vqe_set_dm_grad, at every step)
+    int32_t mode[2] = {0, 0};
+    if (v->cfg.noisy && (vqe_noise_mode_info(v->eng, mode) != VQE_OK || mode[0] != 1))
+      return fail(v, VQE_ESTATE, "the device L-BFGS takes no noisy batch on Pauli trajectories (exact channel mode: vqe_set_noise_mode 1)");
     if (!opts) return fail(v, VQE_EINVAL, "VQE_ENV_OPT_LBFGS needs its options");
     v->lbfgs = *opts;
   }

@@ -6,6 +6,7 @@
 #include "vqe_stream.h"
 #include "vqe_dm.h"
 #include "vqe_dm_batch.h"
+#include "vqe_dm_grad.h"
 #include "vqe_grad.h"
 #include "vqe_lbfgs.h"
 #include "vqe_stream_lbfgs.h"
@@ -40,9 +41,15 @@ struct DmPlanSlot {
   uint64_t gen = ~0ull;
   DevBuf<int32_t> blk_begin, blk_circ, blk_win, mem_begin, mem;
   DevBuf<double> dep, S;
-  std::vector<int32_t> h_blk_begin;
+  std::vector<int32_t> h_blk_begin, h_mem_begin;
   int n_blocks = 0, max_blocks = 0;
   DmBatchDev dev{};
+  // the adjoint gradient (vqe_dm_grad.h), made on the first gradient evaluation of the plan: the block of every member,
+  // S^+ of every block, M of every block, the value of every member
+  uint64_t grad_gen = ~0ull;
+  DevBuf<int32_t> mem_blk;
+  DevBuf<double> Sdag, M, val;
+  int n_members = 0;
 };
 
 struct vqe_handle {
@@ -120,6 +127,10 @@ struct vqe_handle {
   DevBufExact<double2> dmb_rho;
   DevBuf<double> dmb_partial;
   DmPlanSlot dmb_full, dmb_pre;
+  // adjoint gradient of that path (vqe_set_dm_grad, vqe_dm_grad.h): opt-in; the partial sums of M of a chunk's level
+  bool dm_grad = false;
+  DevBuf<double> dmg_part;
+  DevBuf<int32_t> dmg_active;
   // the lock-step driver of the device optimisers (lockstep_run): results of the circuits that stopped, the count of
   // running circuits; COBYLA's start points and per-circuit running flags
   DevBuf<double> ls_xres, ls_fres;
@@ -793,7 +804,8 @@ int dm_batch_plan(vqe_t* h, DmPlanSlot& P, const std::vector<GateRec>& gates, co
   HIP_TRY(h, P.S.reserve((size_t)std::max(1, P.n_blocks) * 512));
   HIP_TRY(h, hipStreamSynchronize(h->stream));      // the tables go out of scope
   P.h_blk_begin = std::move(T.blk_begin);
-  P.dev = DmBatchDev{P.blk_begin.p, P.blk_circ.p, P.blk_win.p, P.mem_begin.p, P.mem.p, P.dep.p, P.S.p};
+  P.h_mem_begin = std::move(T.mem_begin);
+  P.dev =DmBatchDev{P.blk_begin.p, P.blk_circ.p, P.blk_win.p, P.mem_begin.p, P.mem.p, P.dep.p, P.S.p};
   P.gen = h->gen;
   return VQE_OK;
 }
@@ -947,6 +959,207 @@ int dm_run(vqe_t* h, Run mode, const BatchArgs& A) {
   return VQE_OK;
 }
 
+// ---- adjoint gradient and device L-BFGS of the batched form (vqe_set_dm_grad; kernels: vqe_dm_grad.h) ----
+
+// The handle serves gradients in the exact channel mode: the mode, the switch and the batched path
+bool dm_grad_path(const vqe_t* h) { return h->noise_mode == 1 && h->dm_grad && h->dm_batched != 0; }
+
+// dm_refusal's gate test on the single circuit of vqe_set_circuit, for the calls that would load it as the batch:
+// refused before the resident batch changes
+int dm_circuit_refusal(vqe_t* h) {
+  if (!dm_grad_path(h)) return VQE_OK;
+  for (const GateRec& g : h->circ)
+    if (gate_is_rot2(g.kind))
+      return fail(h, VQE_EINVAL, "the exact channel mode does not take RXX / RYY / RZZ gates (use Pauli-trajectory noise, vqe_set_noise_mode 0)");
+  return VQE_OK;
+}
+
+// The gradient tables of plan P and the resident circuits R of a gradient run on it (dm_grad_resident: levels + 2
+// density matrices per circuit out of the budget of an energy run), with their buffers; info[0], [1], [3].
+int dm_grad_reserve(vqe_t* h, DmPlanSlot& P) {
+  const int n = h->n;
+  const size_t total = (size_t)1 << (2 * n);
+  if (P.grad_gen != P.gen) {
+    P.n_members = P.h_mem_begin.back();
+    std::vector<int32_t> mem_blk((size_t)P.n_members);
+    for (int k = 0; k < P.n_blocks; ++k)
+      for (int m = P.h_mem_begin[k]; m < P.h_mem_begin[k + 1]; ++m) mem_blk[m] = k;
+    VQE_TRY(upload(h, P.mem_blk, mem_blk));
+    HIP_TRY(h, P.Sdag.reserve((size_t)std::max(1, P.n_blocks) * 512));
+    HIP_TRY(h, P.M.reserve((size_t)std::max(1, P.n_blocks) * 512));
+    HIP_TRY(h, P.val.reserve((size_t)std::max(1, P.n_members)));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));      // mem_blk goes out of scope
+    P.grad_gen = P.gen;
+  }
+  if (h->dm_batched < 0 && !h->dm_auto_cap) {
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(h, hipMemGetInfo(&free_b, &total_b));
+    h->dm_auto_cap = std::max<size_t>(1, (free_b / 4) / (total * sizeof(double2)));
+  }
+  const size_t cap = h->dm_batched > 0 ? (size_t)h->dm_batched : h->dm_auto_cap;
+  const int R = dm_grad_resident(cap * total * sizeof(double2), n, P.max_blocks, h->batch);
+  if (R < 1)
+    return fail(h, VQE_ENOMEM, "a gradient in the exact channel mode keeps levels + 2 = " + std::to_string(P.max_blocks + 2) +
+                               " density matrices per resident circuit; the budget (vqe_set_dm_batched) holds " + std::to_string(cap));
+  const size_t eb = (((size_t)1 << n) + 255) / 256;
+  HIP_TRY(h, h->dmb_rho.reserve((size_t)R * ((size_t)P.max_blocks + 2) * total));
+  HIP_TRY(h, h->dmb_partial.reserve((size_t)R * eb));
+  HIP_TRY(h, h->dmg_part.reserve((size_t)R * dm_grad_partials(n) * 512));
+  h->dm_info[0] = R;
+  h->dm_info[1] = (h->batch + R - 1) / R;
+  h->dm_info[3] = P.max_blocks;
+  return VQE_OK;
+}
+
+// One lock-step gradient evaluation after dm_grad_reserve(h, P): the circuits of plan P (the batch A describes) at
+// A.theta, tr(rho H) into A.fout[b] and dE/dtheta into d_grad (layout A.par_begin / A.par_count) for every active
+// circuit.  Queued on the handle's stream; nothing is copied back.
+int dm_grad_eval(vqe_t* h, const DmPlanSlot& P, const BatchArgs& A, const int32_t* active) {
+  const int n = h->n, B = h->batch, R = (int)h->dm_info[0];
+  const size_t total = (size_t)1 << (2 * n);
+  const uint32_t n_groups = (uint32_t)(total / 16);
+  const size_t tiles = ((size_t)n_groups + 15) / 16;
+  const unsigned eb = (unsigned)((((size_t)1 << n) + 255) / 256);
+  const uint32_t tpp = dm_grad_tiles_per_partial(n), n_part = dm_grad_partials(n);
+  DmBatchDev Td = P.dev;      // the sweep of Lambda: the same blocks and windows, S^+ for S
+  Td.S = P.Sdag.p;
+  double2* const lam = h->dmb_rho.p;
+  const auto state = [&](int level) { return h->dmb_rho.p + ((size_t)level + 1) * (size_t)R * total; };
+  if (P.n_blocks) {
+    hipLaunchKernelGGL(k_dm_build, dim3((unsigned)P.n_blocks), dim3(256), 0, h->stream, P.dev, (const double*)A.theta,
+                       (const int64_t*)A.par_begin, active);
+    hipLaunchKernelGGL(k_dmg_adjoint, dim3((unsigned)P.n_blocks), dim3(256), 0, h->stream, P.dev, P.Sdag.p, active);
+  }
+  for (int c0 = 0; c0 < B; c0 += R) {
+    const int cnt = std::min(R, B - c0);
+    int levels = 0;
+    for (int b = c0; b < c0 + cnt; ++b) levels = std::max(levels, P.h_blk_begin[b + 1] - P.h_blk_begin[b]);
+    const size_t share = (size_t)h->cu_count * 16 / (size_t)cnt;      // the grids of dm_batch_eval
+    const unsigned gi = (unsigned)std::max<size_t>(1, std::min<size_t>((total + 255) / 256, std::max<size_t>(8, share)));
+    const unsigned gb = (unsigned)std::max<size_t>(1, std::min<size_t>((tiles + 3) / 4, std::max<size_t>(8, share / 2)));
+    hipLaunchKernelGGL(k_dm_init_b, dim3(gi, (unsigned)cnt), dim3(256), 0, h->stream, state(0), (const double2*)h->init.p, n, c0, active);
+    for (int l = 0; l < levels; ++l)
+      hipLaunchKernelGGL(k_dmg_forward, dim3(gb, (unsigned)cnt), dim3(256), 0, h->stream, (const double2*)state(l), state(l + 1), P.dev, n,
+                         n_groups, l, c0, active);
+    hipLaunchKernelGGL(k_dm_energy_b, dim3(eb, (unsigned)cnt), dim3(256), 0, h->stream, (const double2*)state(levels), n, h->dm_groups,
+                       (const uint32_t*)h->dm_gx.p, (const int32_t*)h->dm_toff.p, (const uint32_t*)h->dm_tz.p,
+                       (const double*)h->dm_cr.p, (const double*)h->dm_ci.p, h->dmb_partial.p, c0, active);
+    hipLaunchKernelGGL(k_dm_sum_b, dim3((unsigned)((cnt + 63) / 64)), dim3(64), 0, h->stream, (const double*)h->dmb_partial.p, (int)eb,
+                       cnt, c0, active, A.fout);
+    hipLaunchKernelGGL(k_dmg_lambda_zero, dim3(gi, (unsigned)cnt), dim3(256), 0, h->stream, lam, n, c0, active);
+    hipLaunchKernelGGL(k_dmg_lambda_set, dim3(eb, (unsigned)cnt), dim3(256), 0, h->stream, lam, n, h->dm_groups,
+                       (const uint32_t*)h->dm_gx.p, (const int32_t*)h->dm_toff.p, (const uint32_t*)h->dm_tz.p,
+                       (const double*)h->dm_cr.p, (const double*)h->dm_ci.p, c0, active);
+    for (int l = levels - 1; l >= 0; --l) {      // block index l = level l + 1 of the mathematics: rho_l beside Lambda_{l+1}
+      hipLaunchKernelGGL(k_dmg_macc, dim3((n_part + 3) / 4, (unsigned)cnt), dim3(256), 0, h->stream, (const double2*)state(l),
+                         (const double2*)lam, P.dev, n, n_groups, tpp, n_part, l, c0, active, h->dmg_part.p);
+      hipLaunchKernelGGL(k_dmg_msum, dim3((unsigned)cnt), dim3(512), 0, h->stream, (const double*)h->dmg_part.p, P.dev, n_part, l, c0,
+                         active, P.M.p);
+      hipLaunchKernelGGL(k_dm_block_b, dim3(gb, (unsigned)cnt), dim3(256), 0, h->stream, lam, Td, n, n_groups, l, c0, active);
+    }
+  }
+  if (P.n_members)
+    hipLaunchKernelGGL(k_dmg_contract, dim3((unsigned)P.n_members), dim3(256), 0, h->stream, P.dev, (const int32_t*)P.mem_blk.p,
+                       (const double*)A.theta, (const int64_t*)A.par_begin, active, (const double*)P.M.p, P.val.p);
+  hipLaunchKernelGGL(k_dmg_scatter, dim3((unsigned)B), dim3(64), 0, h->stream, P.dev, (const int64_t*)A.par_begin,
+                     (const int32_t*)A.par_count, active, (const double*)P.val.p, h->d_grad.p);
+  HIP_TRY(h, hipGetLastError());
+  return VQE_OK;
+}
+
+// run_grad in the exact channel mode: E into d_f, the gradient into d_grad.
+int dm_run_grad(vqe_t* h) {
+  VQE_TRY(dm_refusal(h));
+  HIP_TRY(h, hipSetDevice(h->dev));
+  VQE_TRY(dm_prepare_ham(h));
+  VQE_TRY(dm_batch_plan(h, h->dmb_full, h->h_gates, h->h_gate_begin, h->h_gate_count));
+  int64_t info[4];
+  std::copy(h->dm_info, h->dm_info + 4, info);
+  if (const int rc = dm_grad_reserve(h, h->dmb_full)) {      // refused: the handle as it was
+    std::copy(info, info + 4, h->dm_info);
+    return rc;
+  }
+  HIP_TRY(h, h->d_grad.reserve((size_t)h->total_params + 1));
+  const BatchArgs A = make_args(h);
+  h->last_run_dm = false;
+  HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
+  VQE_TRY(dm_grad_eval(h, h->dmb_full, A, nullptr));
+  HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
+  h->dm_info[2] = 1;
+  h->dm_blocks_last = h->dmb_full.max_blocks;
+  return VQE_OK;
+}
+
+// The device L-BFGS of the resident circuits in lock-step, stream_lbfgs with dm_grad_eval as the evaluation: k_sl_step
+// keeps its running flags in its records, k_dmg_active hands them to the evaluation kernels as their `active` array, so
+// a circuit that has stopped costs an early exit per workgroup.
+int dm_lbfgs(vqe_t* h, const DmPlanSlot& P, BatchArgs& A, const vqe_lbfgs_opts_t& o, std::vector<double>& x, std::vector<double>& f,
+             std::vector<int32_t>& nfev) {
+  const int B = h->batch;
+  HIP_TRY(h, h->d_grad.reserve(x.size() + 1));
+  HIP_TRY(h, h->lb_work.reserve((size_t)B * lbfgs_work_doubles(A.max_params, o.history)));
+  HIP_TRY(h, h->lb_nit.reserve(B));
+  HIP_TRY(h, h->lb_status.reserve(B));
+  HIP_TRY(h, h->lb_rec.reserve(B));
+  HIP_TRY(h, h->dmg_active.reserve(B));
+  VQE_TRY(lockstep_begin(h, A, x));
+  const StreamLbfgsArgs T{A.par_begin, A.par_count, A.max_params, h->lb_rec.p, h->d_x.p, h->d_f.p, h->d_grad.p,
+                          h->ls_running.p, h->ls_xres.p, h->ls_fres.p, h->ls_nfres.p};
+  const LbfgsArgs O{o.history, o.maxiter, o.maxfun, o.max_ls, o.gtol, o.ftol, o.c1, h->lb_work.p, h->lb_nit.p, h->lb_status.p};
+  return lockstep_run(h, "L-BFGS", o.maxfun, x, f, nfev,
+                      [&](uint64_t it) {
+                        if (it == 1) return dm_grad_eval(h, P, A, nullptr);
+                        hipLaunchKernelGGL(k_dmg_active, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, h->stream,
+                                           (const int32_t*)&h->lb_rec.p->active, (int)(sizeof(StreamLbfgsRec) / 4), B, h->dmg_active.p);
+                        return dm_grad_eval(h, P, A, (const int32_t*)h->dmg_active.p);
+                      },
+                      [&](uint64_t it) {
+                        hipLaunchKernelGGL(it == 1 ? k_sl_step<true> : k_sl_step<false>, dim3((unsigned)B), dim3(64), 0, h->stream, T, O);
+                      });
+}
+
+// run_lbfgs in the exact channel mode, in the shape of stream_run_lbfgs: an env-step optimises the pre-action circuits
+// under a plan of their own (dmb_pre), then the float32 round trip and one energy evaluation of the full circuits.
+int dm_run_lbfgs(vqe_t* h, bool env_step, const vqe_lbfgs_opts_t& o) {
+  VQE_TRY(dm_refusal(h));
+  VQE_TRY(dm_prepare_ham(h));
+  BatchArgs A = make_args(h);
+  A.maxfun = o.maxfun;
+  std::vector<int32_t> nfev;
+  int64_t before[4], grad_info[4] = {0, 0, 0, 0};
+  std::copy(h->dm_info, h->dm_info + 4, before);
+  bool started = false;
+  const int rc = minimize_or_env_step(h, env_step, A, nfev,
+      [&](BatchArgs& a, const PreActionBatch* pre, std::vector<double>& x, std::vector<double>& f, std::vector<int32_t>& nf) {
+        DmPlanSlot& P = pre ? h->dmb_pre : h->dmb_full;
+        VQE_TRY(pre ? dm_batch_plan(h, P, pre->gates, pre->gbeg, pre->gcnt)
+                    : dm_batch_plan(h, P, h->h_gates, h->h_gate_begin, h->h_gate_count));
+        VQE_TRY(dm_grad_reserve(h, P));
+        std::copy(h->dm_info, h->dm_info + 4, grad_info);
+        started = true;
+        h->last_run_dm = false;
+        h->lb_batch = 0;
+        HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
+        return dm_lbfgs(h, P, a, o, x, f, nf);
+      },
+      [&](const BatchArgs& a) {
+        VQE_TRY(dm_batch_plan(h, h->dmb_full, h->h_gates, h->h_gate_begin, h->h_gate_count));
+        VQE_TRY(dm_batch_reserve(h));
+        return dm_batch_eval(h, h->dmb_full, a, nullptr);
+      });
+  if (rc) {
+    if (!started) std::copy(before, before + 4, h->dm_info);
+    return rc;
+  }
+  HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
+  std::copy(grad_info, grad_info + 4, h->dm_info);      // the resident count and the chunks of the gradient evaluations
+  h->dm_info[2] = *std::max_element(nfev.begin(), nfev.end()) + (env_step ? 1 : 0);
+  h->dm_info[3] = h->dmb_full.max_blocks;
+  h->dm_blocks_last = h->dmb_full.max_blocks;
+  h->lb_batch = h->batch;
+  return VQE_OK;
+}
+
 // The evaluation trace of an optimiser run (vqe_batch_set_trace): [batch][maxfun][1 + max_params] doubles, zeroed
 int arm_trace(vqe_t* h, BatchArgs& A, int maxfun) {
   const size_t stride = (size_t)1 + (size_t)h->max_params, words = (size_t)h->batch * (size_t)maxfun * stride;
@@ -1012,6 +1225,15 @@ int build_grad_tables(vqe_t* h) {
 // Checked before anything is loaded, so a refused call leaves the handle as it was.
 // (grad_state_refusal: everything but the path test - the device L-BFGS has a switch of its own for n >= 14)
 int grad_state_refusal(vqe_t* h) {
+  if (h->noise_mode == 1 && h->dm_grad) {
+    // the exact channel mode after vqe_set_dm_grad: deterministic energies whatever p1 / p2, no shot noise in this mode;
+    // the gates and the size are dm_refusal's, checked once the batch is known
+    if (h->dm_batched == 0)
+      return fail(h, VQE_ESTATE, "energy gradients in the exact channel noise mode are computed on the batched path: "
+                                 "vqe_set_dm_grad needs vqe_set_dm_batched != 0 beside it");
+    if (h->amp_world > 1) return fail(h, VQE_ESTATE, "the exact channel mode has no amplitude sharding");
+    return VQE_OK;
+  }
   if (h->noise.p1 > 0.0 || h->noise.p2 > 0.0)
     return fail(h, VQE_ESTATE, "energy gradients of Pauli-noise trajectories are refused (set p1 = p2 = 0)");
   if (h->noise_mode == 1) return fail(h, VQE_ESTATE, "energy gradients are not available in the exact channel noise mode");
@@ -1020,6 +1242,7 @@ int grad_state_refusal(vqe_t* h) {
   return VQE_OK;
 }
 int grad_refusal(vqe_t* h) {
+  if (h->noise_mode == 1 && h->dm_grad) return grad_state_refusal(h);
   if (!h->lds_path && !h->stream_grad)
     return fail(h, VQE_EINVAL, "energy gradients are computed for n_qubits <= 13 (LDS-resident path) only");
   return grad_state_refusal(h);
@@ -1076,6 +1299,7 @@ int stream_grad(vqe_t* h, const BatchArgs& A) {
 
 int run_grad(vqe_t* h) {
   VQE_TRY(grad_refusal(h));
+  if (dm_grad_path(h)) return dm_run_grad(h);
   HIP_TRY(h, hipSetDevice(h->dev));
   if (h->lds_path) VQE_TRY(build_grad_tables(h));
   HIP_TRY(h, h->d_grad.reserve((size_t)h->total_params + 1));
@@ -1167,6 +1391,7 @@ int stream_run_lbfgs(vqe_t* h, bool env_step, const vqe_lbfgs_opts_t& o) {
 // o: options that passed lbfgs_check
 int run_lbfgs(vqe_t* h, bool env_step, const vqe_lbfgs_opts_t& o) {
   HIP_TRY(h, hipSetDevice(h->dev));
+  if (dm_grad_path(h)) return dm_run_lbfgs(h, env_step, o);
   if (!h->lds_path) return stream_run_lbfgs(h, env_step, o);
   VQE_TRY(build_grad_tables(h));
   BatchArgs A = make_args(h);
@@ -1537,6 +1762,12 @@ int vqe_set_dm_batched(vqe_t* h, int max_resident) {
   return VQE_OK;
 }
 
+int vqe_set_dm_grad(vqe_t* h, int enable) {
+  if (!h) return VQE_EINVAL;
+  h->dm_grad = enable != 0;      // (takes effect in noise mode 1 with vqe_set_dm_batched != 0; elsewhere nothing to switch)
+  return VQE_OK;
+}
+
 int vqe_dm_batch_info(vqe_t* h, int64_t out[4]) {
   if (!h || !out) return VQE_EINVAL;
   std::copy(h->dm_info, h->dm_info + 4, out);
@@ -1673,6 +1904,7 @@ int vqe_energy_grad_batch(vqe_t* h, int batch, const double* theta, double* ener
   if (batch < 1 || !energy || (h->circ_params > 0 && (!theta || !grad))) return fail(h, VQE_EINVAL, "bad arguments");
   int rc;
   if ((rc = grad_refusal(h))) return rc;
+  if ((rc = dm_circuit_refusal(h))) return rc;
   HIP_TRY(h, hipSetDevice(h->dev));
   if ((rc = load_single(h, batch, theta))) return rc;
   if ((rc = ready(h))) return rc;
@@ -1749,6 +1981,7 @@ int vqe_minimize_lbfgs(vqe_t* h, const double* x0, const vqe_lbfgs_opts_t* opts,
   int rc;
   if ((rc = lbfgs_check(h, opts, &o))) return rc;
   if (!f || (h->circ_params > 0 && (!x0 || !x))) return fail(h, VQE_EINVAL, "x0 / x / f is NULL");
+  if ((rc = dm_circuit_refusal(h))) return rc;
   HIP_TRY(h, hipSetDevice(h->dev));
   if ((rc = load_single(h, 1, x0))) return rc;
   if ((rc = ready(h))) return rc;

@@ -246,6 +246,13 @@ class VQEEngine:
         device memory, R >= 1 at most R (a batch larger than that is evaluated in chunks)."""
         self._chk(self._lib.vqe_set_dm_batched(self._h, int(max_resident)))
 
+    def set_dm_grad(self, enable: bool = True):
+        """Exact channel mode on the batched path (set_noise_mode(1) + set_dm_batched): let energy_grad /
+        energy_grad_batch / batch_run_energy_grad and minimize_lbfgs / batch_run_minimize_lbfgs /
+        batch_run_env_step_lbfgs run there, on the adjoint gradient of tr(rho H).  Off by default: those calls raise in
+        mode 1.  A resident circuit then costs levels + 2 density matrices (dm_batch_info reports the resident count)."""
+        self._chk(self._lib.vqe_set_dm_grad(self._h, 1 if enable else 0))
+
     def dm_batch_info(self):
         """The last batched exact-channel run (all 0 after a serial one)."""
         out = (C.c_int64 * 4)()

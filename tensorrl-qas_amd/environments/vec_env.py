@@ -77,7 +77,8 @@ class _EnvView:
 class VecCircuitEnv:
     """``device_optimizer``: the optimiser of every step's fused launch, a property of the batch and not of the
     reference's config file - "cobyla" (default: batch_run_env_step, the config's optim_alg = COBYLA) or "lbfgs"
-    (batch_run_env_step_lbfgs: the device L-BFGS on adjoint gradients, noiseless configurations only; NOT scipy's
+    (batch_run_env_step_lbfgs: the device L-BFGS on adjoint gradients, noiseless configurations and the noisy classes
+    with noise_channel = "exact" - set_dm_grad on top of the two switches below; NOT scipy's
     L-BFGS-B; at 14 qubits and more the engine's set_stream_lbfgs is switched on for it).  ``lbfgs_opts``: options of VQEEngine.lbfgs_opts; ``maxfun`` defaults to the config's global_iters so
     that nfev stays comparable with COBYLA's budget.
     ``noise_channel``: how the noisy environment classes evaluate their depolarising channels - "trajectory" (default:
@@ -104,15 +105,18 @@ class VecCircuitEnv:
         self.device_optimizer = device_optimizer
         self._lbfgs_opts = None
         if device_optimizer == "lbfgs":
-            if first.NOISY or first.phys_noise or first.n_shots:
+            if noise_channel != "exact" and (first.NOISY or first.phys_noise or first.n_shots):
                 raise NotImplementedError("device_optimizer = 'lbfgs' needs an exact, deterministic energy: noisy and "
-                                          "finite-shot configurations are served by the device COBYLA")
+                                          "finite-shot configurations are served by the device COBYLA, or by "
+                                          "noise_channel = 'exact' (the channel itself, a density matrix)")
             self._lbfgs_opts = {"maxfun": int(first.global_iters), **(lbfgs_opts or {})}
         self.engine = first.engine
         self.noise_channel = noise_channel
         if noise_channel == "exact":
             self.engine.set_noise_mode(1)
             self.engine.set_dm_batched(-1)
+            if device_optimizer == "lbfgs":
+                self.engine.set_dm_grad(True)            # the adjoint gradient of tr(rho H) on the batched path
         if device_optimizer == "lbfgs" and first.num_qubits >= 14:
             self.engine.set_stream_lbfgs(True)           # the streaming path runs the device L-BFGS on request only
         self._proto = first

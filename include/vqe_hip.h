@@ -353,6 +353,39 @@ int vqe_batch_run_minimize_lbfgs(vqe_t* h, const vqe_lbfgs_opts_t* opts);
 int vqe_batch_run_env_step_lbfgs(vqe_t* h, const vqe_lbfgs_opts_t* opts);
 /* replaces: result.nit / result.status of those scipy calls (status numbered as above); either pointer may be NULL */
 int vqe_batch_fetch_lbfgs_info(vqe_t* h, int32_t* nit /* batch */, int32_t* status /* batch */);
+/* ---- device Lanczos: the extreme eigenpair of the Hamiltonian ------------------------------------
+ * The lowest (which = 0) or highest (which = 1) eigenvalue of the handle's Hamiltonian and its eigenvector, by Lanczos
+ * on the device: a stored basis of at most max_basis vectors (complex128[2^n] each, in global memory; fewer when 2^n
+ * or a quarter of the free device memory holds fewer beside three work vectors - VQE_ENOMEM below 2), full
+ * reorthogonalisation, explicit restart from the current Ritz vector when the basis is full.  Every step is queued on
+ * the handle's stream; the host reads the recurrence coefficients every check_every steps and stops when the residual
+ * estimate is <= tol * max(1, |theta|).  The same path for every n the handle accepts (csrc/vqe_lanczos.h).
+ * replaces: numpy.linalg.eigvalsh of the dense operator - the `eigvals` of the reference's Hamiltonian files, whose
+ * minimum is the environments' min_eig (environment_qulacs_TN_notin_agent.py:126-131,166-167) - and the DMRG run whose
+ * state the init circuit is fitted to; the reference ships neither for its 12- and 20-qubit problems.
+ * THE KRYLOV LIMIT: the result is the extreme eigenpair of H restricted to the Krylov space of the start vector.  The
+ * default start (uniform draws from `seed`) overlaps every eigenvector; with start_from_init the start is the handle's
+ * initial state, and a start without a component along the wanted eigenvector never finds it - from an exact
+ * eigenvector the answer is that eigenvector after one application, whatever its place in the spectrum.
+ * *eigenvalue is the Rayleigh quotient of the returned vector (never below the true minimum), amps the normalised
+ * vector (NULL: not copied; the _dev variant takes device memory, complex128[2^n], and returns the same bits).
+ * info = {true residual |H y - theta y|, H applications of the recurrence, restarts, status}; status 0 converged,
+ * 1 breakdown (the Krylov space is an exact invariant subspace: the pair is exact in it), 2 max_matvec applications
+ * used up - NOT an error: VQE_OK with the best Ritz pair so far and its true residual.  Two calls with equal options
+ * return equal bits.
+ * Refused before anything is launched, handle unchanged: VQE_ESTATE without a Hamiltonian, on a term shard with
+ * world > 1 (a shard's spectrum is not H's) or an amplitude shard; VQE_EINVAL for which outside {0, 1}, max_basis < 2,
+ * max_matvec < 1, check_every < 1, tol <= 0 or not finite.  Noise settings and the circuit play no part; the call
+ * changes neither the initial state, the resident batch and its results, the noise counter nor any later result of
+ * the handle.  vqe_last_kernel_ms reports the run. */
+typedef struct { int32_t which;          /* 0 lowest, 1 highest */
+                 int32_t max_basis, max_matvec, check_every, start_from_init;
+                 double tol; uint64_t seed; } vqe_lanczos_opts_t;
+int vqe_lanczos_default_opts(vqe_lanczos_opts_t* o);   /* 0, 128, 2000, 8, 0, 1e-10, 1 */
+int vqe_lanczos(vqe_t* h, const vqe_lanczos_opts_t* opts /* NULL: defaults */, double* eigenvalue,
+                double* amps_re_im /* 2 * 2^n or NULL */, double info[4]);
+int vqe_lanczos_dev(vqe_t* h, const vqe_lanczos_opts_t* opts, double* eigenvalue,
+                    void* dev_amps_re_im /* or NULL */, double info[4]);
 /* device pointer to the batch's f / energy array (float64[batch]) for on-device
  * reductions by the caller (e.g. torch.distributed all_reduce over RCCL) */
 int vqe_batch_energy_devptr(vqe_t* h, void** dev_ptr);

@@ -10,6 +10,7 @@
 #include "vqe_grad.h"
 #include "vqe_lbfgs.h"
 #include "vqe_stream_lbfgs.h"
+#include "vqe_lanczos.h"
 #include "ham_layout.h"
 #include "dm_host.h"
 #include "env_step_host.h"
@@ -159,6 +160,8 @@ struct vqe_handle {
   // device L-BFGS of the streaming path (vqe_stream_lbfgs.h): opt-in (vqe_set_stream_lbfgs); per-stream records
   bool stream_lbfgs = false;
   DevBufExact<StreamLbfgsRec> lb_rec;
+  // device Lanczos (vqe_lanczos.h): the solver's own copy of the full operator (logical frame) and its vectors
+  LzWork lz;
 };
 
 #ifdef VQE_STAMPS
@@ -2039,6 +2042,65 @@ int vqe_batch_fetch_xopt(vqe_t* h, double* x) {
     HIP_TRY(h, hipMemcpyAsync(x, h->d_xraw.p, (size_t)h->total_params * 8, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   return VQE_OK;
+}
+
+// ---- device Lanczos (vqe_lanczos.h) ---------------------------------------------------------------------------------
+extern "C++" {
+namespace {
+// Everything a vqe_lanczos call can be refused for, before anything is launched or given up.
+int lanczos_check(vqe_t* h, const vqe_lanczos_opts_t* opts, LzOptions* o) {
+  vqe_lanczos_opts_t d;
+  vqe_lanczos_default_opts(&d);
+  if (opts) d = *opts;
+  if (!h->ham_set) return fail(h, VQE_ESTATE, "no Hamiltonian set");
+  if (h->shard_world > 1)
+    return fail(h, VQE_ESTATE, "vqe_lanczos on a term-sharded handle: a shard's spectrum is not the Hamiltonian's");
+  if (h->amp_world > 1) return fail(h, VQE_ESTATE, "vqe_lanczos on an amplitude-sharded handle: it holds a slice of the register");
+  if (d.which != 0 && d.which != 1) return fail(h, VQE_EINVAL, "vqe_lanczos: which must be 0 (lowest) or 1 (highest)");
+  if (d.max_basis < 2) return fail(h, VQE_EINVAL, "vqe_lanczos: max_basis must be at least 2");
+  if (d.max_matvec < 1) return fail(h, VQE_EINVAL, "vqe_lanczos: max_matvec must be at least 1");
+  if (d.check_every < 1) return fail(h, VQE_EINVAL, "vqe_lanczos: check_every must be at least 1");
+  if (!(d.tol > 0.0) || !std::isfinite(d.tol)) return fail(h, VQE_EINVAL, "vqe_lanczos: tol must be positive and finite");
+  *o = LzOptions{d.which, d.max_basis, d.max_matvec, d.check_every, d.start_from_init != 0, d.tol, d.seed};
+  return VQE_OK;
+}
+
+int lanczos(vqe_t* h, const vqe_lanczos_opts_t* opts, double* eigenvalue, void* amps, bool amps_on_device, double info[4]) {
+  if (!h) return VQE_EINVAL;
+  if (!eigenvalue || !info) return fail(h, VQE_EINVAL, "bad arguments");
+  LzOptions o;
+  VQE_TRY(lanczos_check(h, opts, &o));
+  HIP_TRY(h, hipSetDevice(h->dev));
+  VQE_TRY(lz_upload_ham(h->lz, h->ham_host, h->ham_ver, h->stream, h->err));
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(h, hipMemGetInfo(&free_b, &total_b));
+  h->last_run_dm = false;
+  HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
+  const int rc = lz_run(h->lz, h->n, h->stream, (const double2*)h->init.p, o, free_b, eigenvalue, info, h->err);
+  HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
+  VQE_TRY(rc);
+  if (amps) {
+    HIP_TRY(h, hipMemcpyAsync(amps, lz_vector(h->lz, h->n), ((size_t)16) << h->n,
+                              amps_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
+    if (!amps_on_device) HIP_TRY(h, hipStreamSynchronize(h->stream));
+  }
+  return VQE_OK;
+}
+}  // namespace
+}
+
+int vqe_lanczos_default_opts(vqe_lanczos_opts_t* o) {
+  if (!o) return VQE_EINVAL;
+  *o = vqe_lanczos_opts_t{0, 128, 2000, 8, 0, 1e-10, 1ull};
+  return VQE_OK;
+}
+
+int vqe_lanczos(vqe_t* h, const vqe_lanczos_opts_t* opts, double* eigenvalue, double* amps_re_im, double info[4]) {
+  return lanczos(h, opts, eigenvalue, amps_re_im, false, info);
+}
+
+int vqe_lanczos_dev(vqe_t* h, const vqe_lanczos_opts_t* opts, double* eigenvalue, void* dev_amps_re_im, double info[4]) {
+  return lanczos(h, opts, eigenvalue, dev_amps_re_im, true, info);
 }
 
 int vqe_batch_energy_devptr(vqe_t* h, void** p) {

@@ -346,6 +346,57 @@ class VQEEngine:
                                                C.byref(nfev), C.byref(nit), C.byref(st)))
         return x, f.value, nfev.value, nit.value, st.value
 
+    # -- device Lanczos: extreme eigenpair of the Hamiltonian (no circuit involved) ----------------------
+    LANCZOS_STATUS = {0: "converged", 1: "breakdown", 2: "budget"}
+
+    def lanczos_opts(self, which="min", **opts):
+        """vqe_lanczos_opts_t with the library's defaults (max_basis 128, max_matvec 2000, check_every 8,
+        start_from_init 0, tol 1e-10, seed 1) and the given fields replaced; ``which``: "min" / "max" (or 0 / 1)."""
+        o = _lib.LanczosOpts()
+        self._chk(self._lib.vqe_lanczos_default_opts(C.byref(o)))
+        ends = {"min": 0, "max": 1, 0: 0, 1: 1}
+        if which not in ends:
+            raise ValueError("which must be 'min' or 'max'")
+        o.which = ends[which]
+        names = {f[0] for f in _lib.LanczosOpts._fields_} - {"which"}
+        for k, v in opts.items():
+            if k not in names:
+                raise TypeError(f"unknown Lanczos option {k!r} (known: {sorted(names)})")
+            setattr(o, k, float(v) if k == "tol" else int(v))
+        return o
+
+    def _lanczos_info(self, info):
+        return {"residual": info[0], "matvecs": int(info[1]), "restarts": int(info[2]), "status": int(info[3]),
+                "status_name": self.LANCZOS_STATUS[int(info[3])]}
+
+    def lanczos(self, which="min", want_vector=True, **opts):
+        """The lowest ("min") or highest ("max") eigenvalue of the Hamiltonian and its eigenvector by Lanczos on the
+        GPU (vqe_lanczos).  The value is the Rayleigh quotient of the returned vector; it is the extreme pair of the
+        Krylov space of the start vector (random by default, the initial state with ``start_from_init=1``).  Returns
+        (value, complex128[2^n] or None, info) with info = dict(residual, matvecs, restarts, status, status_name);
+        status "budget" is no error - the best pair so far with its true residual."""
+        o = self.lanczos_opts(which, **opts)
+        ev = C.c_double()
+        info = (C.c_double * 4)()
+        vec = np.empty(2 << self.n_qubits, np.float64) if want_vector else None
+        self._chk(self._lib.vqe_lanczos(self._h, C.byref(o), C.byref(ev), _p(vec, c_f64p) if want_vector else C.cast(None, c_f64p),
+                                        info))
+        return ev.value, (vec.view(np.complex128) if want_vector else None), self._lanczos_info(info)
+
+    def lanczos_dev(self, dev_ptr: int, which="min", **opts):
+        """lanczos with the vector written to device memory (complex128[2^n], asynchronous on the handle's stream; 0: no
+        vector).  Returns (value, info)."""
+        o = self.lanczos_opts(which, **opts)
+        ev = C.c_double()
+        info = (C.c_double * 4)()
+        self._chk(self._lib.vqe_lanczos_dev(self._h, C.byref(o), C.byref(ev), C.c_void_p(int(dev_ptr) or None), info))
+        return ev.value, self._lanczos_info(info)
+
+    def ground_state(self, **opts):
+        """(lowest eigenvalue, its eigenvector) of the Hamiltonian by the device Lanczos."""
+        value, vec, _ = self.lanczos("min", True, **opts)
+        return value, vec
+
     # -- batches of circuits --------------------------------------------------------------
     def batch_load(self, circuits, thetas):
         """``circuits``: list of Circuit; ``thetas``: list of arrays (x0 / theta per circuit)."""

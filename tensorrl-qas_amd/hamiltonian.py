@@ -182,6 +182,34 @@ def extreme_eigenvalues(ham, tol=1e-10):
     return _lanczos(ham, tol, want_vector=False)
 
 
+def _device_engine(ham, device_id):
+    from .engine import VQEEngine
+    eng = VQEEngine(ham.n, device_id)
+    eng.set_hamiltonian(ham.xmask, ham.zmask, ham.coeff)
+    return eng
+
+
+def ground_state_device(ham, device_id=0, **opts):
+    """``ground_state`` on the GPU: (min eigenvalue, its eigenvector as complex128[2^n]) by the library's device Lanczos
+    (VQEEngine.lanczos; ``opts``: max_basis, max_matvec, check_every, tol, seed).  Raises VQEError without a GPU."""
+    eng = _device_engine(ham, device_id)
+    try:
+        return eng.ground_state(**opts)
+    finally:
+        eng.close()
+
+
+def extreme_eigenvalues_device(ham, device_id=0, **opts):
+    """``extreme_eigenvalues`` on the GPU: (min, max) eigenvalue by two runs of the device Lanczos on one engine."""
+    eng = _device_engine(ham, device_id)
+    try:
+        lo, _, _ = eng.lanczos("min", False, **opts)
+        hi, _, _ = eng.lanczos("max", False, **opts)
+        return lo, hi
+    finally:
+        eng.close()
+
+
 def _lanczos(ham, tol, want_vector):
     """(min, max) eigenvalue of a PauliHamiltonian by matrix-free Lanczos (scipy ``eigsh`` on a
     LinearOperator that applies the Pauli sum): replaces the reference's dense ``eigvals`` - the

@@ -9,6 +9,8 @@ instead of DMRG + quimb, the HBM-streaming Stiefel-Adam fit on the GPU (csrc/mps
     heisenberg_20q_meta.json             E0 (Lanczos), E(init circuit), infidelity of the fit, timings, seeds
 
 Run on a GPU box:  python3 tools/make_heis20_init.py [out_dir]      (gpurun_out/heis20 by default)"""
+# --device-lanczos (anywhere on the command line): the ground state by the library's device Lanczos
+# (hamiltonian.ground_state_device) instead of the host path; off by default.
 import json
 import os
 import sys
@@ -23,11 +25,13 @@ from tensorrl_qas_amd import dmrg_to_qc as dq  # noqa: E402
 from tensorrl_qas_amd.dmrg_to_qc.mps2qc import fit_state_to_init_circuit  # noqa: E402
 
 n = int(os.environ.get("HEIS_N", "20"))
+device_lanczos = "--device-lanczos" in sys.argv[1:]
+sys.argv = [a for a in sys.argv if a != "--device-lanczos"]
 out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "gpurun_out", f"heis{n}")
 os.makedirs(out, exist_ok=True)
 ham, _ = tq.hamiltonian.heisenberg(n)
 t0 = time.time()
-e0, psi = tq.hamiltonian.ground_state(ham)
+e0, psi = tq.hamiltonian.ground_state_device(ham) if device_lanczos else tq.hamiltonian.ground_state(ham)
 t_lanczos = time.time() - t0
 print(f"Lanczos: E0 = {e0:.12f} ({t_lanczos:.1f} s)", flush=True)
 t0 = time.time()
@@ -49,6 +53,6 @@ open(os.path.join(out, stem), "w").write(text)
 meta = {"n_qubits": n, "model": "heisenberg open chain, sum (XX+YY+ZZ) + sum Z, weights 1 (reference heisenberg_model.py:22-72)",
         "e0_lanczos": e0, "e_init_circuit": e_init, "fit_infidelity_1_minus_abs_overlap": infid, "fidelity_abs_overlap_squared": fid,
         "layers": 1, "su4_blocks": int(len(sites)), "gates_in_file": int(len(circ)), "rng_seed": 20,
-        "lanczos_s": t_lanczos, "fit_s": t_fit, "script": "tools/make_heis20_init.py"}
+        "lanczos_s": t_lanczos, "lanczos": "device" if device_lanczos else "host", "fit_s": t_fit, "script": "tools/make_heis20_init.py"}
 json.dump(meta, open(os.path.join(out, f"heisenberg_{n}q_meta.json"), "w"), indent=1)
 print(json.dumps(meta))

@@ -11,7 +11,9 @@
  *   dmrg-to-qc/tnqc_ansatze.py:46-98  brickwork_ansatz(): gate order
  * The reference does this with jax autodiff over a quimb tensor network, one fit at a time; here
  * a whole batch of fits (random restarts and / or different targets) runs in ONE launch, one
- * workgroup per fit, the complete optimisation loop on the device.
+ * workgroup per fit, the complete optimisation loop on the device.  Beyond MPS2QC_MAX_QUBITS the states stream through
+ * HBM, one kernel per gate sweep: mps2qc_fit_brickwork_stream keeps the optimiser update on the host,
+ * mps2qc_fit_brickwork_resident runs it on the device and also takes its target from device memory.
  *
  * Conventions (quimb): MPS site 0 is the most significant bit of the dense index; a gate on
  * sites (i, i+1) is a row-major 4x4 complex matrix indexed by 2*s_i + s_{i+1}.  Complex
@@ -94,4 +96,8 @@ const char* mps2qc_last_error(void);
 #ifdef __cplusplus
 }
 #endif
+
+/* mps2qc_fit_brickwork_resident, the streaming fit with the optimiser on the device (same library) */
+#include "mps2qc_resident_hip.h"
+
 #endif

@@ -141,6 +141,12 @@ SIGNATURES.update({
     "vqe_vecenv_set_optimizer": (C.c_int, [vp, C.c_int, C.POINTER(LbfgsOpts)]),
 })
 
+class ResidentOpts(C.Structure):
+    """mps2qc_resident_opts_t of include/mps2qc_hip.h"""
+    _fields_ = [("target_on_device", C.c_int32), ("target_little_endian", C.c_int32), ("check_every", C.c_int32),
+                ("use_graph", C.c_int32)]
+
+
 # include/mps2qc_hip.h (libmps2qc_hip.so: the offline MPS -> PQC fit)
 MPS2QC_LIB_PATH = os.environ.get("MPS2QC_HIP_LIB") or os.path.join(_HERE, "libmps2qc_hip.so")
 MPS2QC_SIGNATURES = {
@@ -156,6 +162,15 @@ MPS2QC_SIGNATURES = {
                                               c_f64p, c_f64p, c_f64p, c_f64p, c_i32p, c_f64p, c_f64p,
                                               C.POINTER(C.c_float)]),
     "mps2qc_last_error": (C.c_char_p, []),
+}
+# include/mps2qc_resident_hip.h (same library: the streaming fit with the optimiser on the device)
+MPS2QC_RESIDENT_SIGNATURES = {
+    "mps2qc_resident_default_opts": (C.c_int, [C.POINTER(ResidentOpts)]),
+    "mps2qc_fit_brickwork_resident": (C.c_int, [C.c_int, C.c_int, C.c_int, c_i32p, C.c_int, vp, C.c_int, c_f64p,
+                                                C.c_double, C.c_double, C.c_double, C.c_double, C.c_int,
+                                                C.c_int, C.c_double, C.c_double, C.POINTER(ResidentOpts),
+                                                c_f64p, c_f64p, c_f64p, c_f64p, c_i32p, c_f64p, c_f64p,
+                                                C.POINTER(C.c_float), c_i32p]),
 }
 
 _lib = None
@@ -190,7 +205,7 @@ def load_mps2qc():
         if not os.path.exists(MPS2QC_LIB_PATH):
             raise VQEError(f"{MPS2QC_LIB_PATH} not found: build it with __graft_entry__.build(); no CPU fallback.")
         lib = C.CDLL(MPS2QC_LIB_PATH)
-        for name, (res, args) in MPS2QC_SIGNATURES.items():
+        for name, (res, args) in {**MPS2QC_SIGNATURES, **MPS2QC_RESIDENT_SIGNATURES}.items():
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

@@ -1303,3 +1303,6 @@ extern "C" int mps2qc_fit_brickwork_stream(int device_id, int n, int G, const in
   if (last_overlap) memcpy(last_overlap, S.h_ov, (size_t)batch * 16);
   return 0;
 }
+
+// ---- the same fit with the update on the device: mps2qc_fit_brickwork_resident -----------------------------------
+#include "mps2qc_resident_kernels.h"

@@ -189,12 +189,20 @@ def _device_engine(ham, device_id):
     return eng
 
 
-def ground_state_device(ham, device_id=0, **opts):
+def ground_state_device(ham, device_id=0, return_tensor=False, **opts):
     """``ground_state`` on the GPU: (min eigenvalue, its eigenvector as complex128[2^n]) by the library's device Lanczos
-    (VQEEngine.lanczos; ``opts``: max_basis, max_matvec, check_every, tol, seed).  Raises VQEError without a GPU."""
+    (VQEEngine.lanczos; ``opts``: max_basis, max_matvec, check_every, tol, seed).  Raises VQEError without a GPU.
+    ``return_tensor=True``: the vector stays on the device, as a complex128 torch tensor on ``cuda:device_id`` in the
+    engine's little-endian order - what ``dmrg_to_qc.fit_state_to_init_circuit`` fits without a host copy."""
     eng = _device_engine(ham, device_id)
     try:
-        return eng.ground_state(**opts)
+        if not return_tensor:
+            return eng.ground_state(**opts)
+        import torch
+        vec = torch.empty(1 << ham.n, dtype=torch.complex128, device=f"cuda:{device_id}")
+        value, _ = eng.lanczos_dev(vec.data_ptr(), "min", **opts)
+        eng.sync()      # the vector was written on the engine's stream: nothing else may read it before
+        return value, vec
     finally:
         eng.close()
 

@@ -11,6 +11,8 @@ instead of DMRG + quimb, the HBM-streaming Stiefel-Adam fit on the GPU (csrc/mps
 Run on a GPU box:  python3 tools/make_heis20_init.py [out_dir]      (gpurun_out/heis20 by default)"""
 # --device-lanczos (anywhere on the command line): the ground state by the library's device Lanczos
 # (hamiltonian.ground_state_device) instead of the host path; off by default.
+# HEIS_RESIDENT=1 (environment, off by default): Lanczos -> fit with the state never leaving the device - the ground state
+# stays a device tensor (ground_state_device(return_tensor=True)) and the resident streaming fit reads it there.
 import json
 import os
 import sys
@@ -31,7 +33,12 @@ out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "gpurun_out", f"h
 os.makedirs(out, exist_ok=True)
 ham, _ = tq.hamiltonian.heisenberg(n)
 t0 = time.time()
-e0, psi = tq.hamiltonian.ground_state_device(ham) if device_lanczos else tq.hamiltonian.ground_state(ham)
+resident = os.environ.get("HEIS_RESIDENT", "0") not in ("", "0")
+if resident:
+    e0, psi_dev = tq.hamiltonian.ground_state_device(ham, return_tensor=True)
+    psi = psi_dev
+else:
+    e0, psi = tq.hamiltonian.ground_state_device(ham) if device_lanczos else tq.hamiltonian.ground_state(ham)
 t_lanczos = time.time() - t0
 print(f"Lanczos: E0 = {e0:.12f} ({t_lanczos:.1f} s)", flush=True)
 t0 = time.time()
@@ -47,12 +54,12 @@ eng.set_hamiltonian(ham.xmask, ham.zmask, ham.coeff)
 eng.set_circuit(circ)
 e_init = eng.energy(ang)
 state = eng.get_state(ang)
-fid = float(abs(np.vdot(psi, state)) ** 2)
+fid = float(abs(np.vdot(psi_dev.cpu().numpy() if resident else psi, state)) ** 2)
 stem = f"init_heisenberg_{n}q_TNbond2.qasm"
 open(os.path.join(out, stem), "w").write(text)
 meta = {"n_qubits": n, "model": "heisenberg open chain, sum (XX+YY+ZZ) + sum Z, weights 1 (reference heisenberg_model.py:22-72)",
         "e0_lanczos": e0, "e_init_circuit": e_init, "fit_infidelity_1_minus_abs_overlap": infid, "fidelity_abs_overlap_squared": fid,
         "layers": 1, "su4_blocks": int(len(sites)), "gates_in_file": int(len(circ)), "rng_seed": 20,
-        "lanczos_s": t_lanczos, "lanczos": "device" if device_lanczos else "host", "fit_s": t_fit, "script": "tools/make_heis20_init.py"}
+        "lanczos_s": t_lanczos, "lanczos": "device" if device_lanczos or resident else "host", "fit_update": "device" if resident else "host", "fit_s": t_fit, "script": "tools/make_heis20_init.py"}
 json.dump(meta, open(os.path.join(out, f"heisenberg_{n}q_meta.json"), "w"), indent=1)
 print(json.dumps(meta))

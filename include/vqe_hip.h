@@ -386,6 +386,40 @@ int vqe_lanczos(vqe_t* h, const vqe_lanczos_opts_t* opts /* NULL: defaults */, d
                 double* amps_re_im /* 2 * 2^n or NULL */, double info[4]);
 int vqe_lanczos_dev(vqe_t* h, const vqe_lanczos_opts_t* opts, double* eigenvalue,
                     void* dev_amps_re_im /* or NULL */, double info[4]);
+/* ---- device Lanczos: several eigenpairs, with multiplicities ------------------------------------------
+ * The n_eig lowest (which = 0) or highest (which = 1) eigenpairs of the handle's Hamiltonian, copies of a degenerate
+ * eigenvalue included: thick-restart Lanczos with locking by deflation, one stage per pair.  Stage e draws
+ * a fresh random start vector (from seed and e; stage 0 has the start vector of vqe_lanczos) orthogonal to the e vectors
+ * found so far, which stay in the basis storage, so the full reorthogonalisation of every step keeps the recurrence in
+ * their complement.  A full active basis keeps `keep` Ritz vectors and the residual vector and goes on (keep = 0: the
+ * library's rule, half the active basis; with fewer than 3 active vectors: the explicit restart of vqe_lanczos).  A stage
+ * ends by the stop rule of vqe_lanczos.  Storage: max_basis + n_eig - 1 vectors beside the three work vectors, fewer when
+ * 2^n or a quarter of the free device memory holds fewer - stage e then has min(max_basis, slots - e, 2^n - e, 1024)
+ * active vectors; VQE_ENOMEM, before anything is launched, if the last stage would have fewer than 2 (1 where a single
+ * dimension is left).
+ * replaces: the low (high) end of numpy.linalg.eigvalsh of the dense operator - the `eigvals` array of the reference's
+ * Hamiltonian files - where the dense matrix cannot exist, with the gap and the degeneracy of the ground level.
+ * eigenvalues[i] ascend for which = 0 and descend for which = 1, each the Rayleigh quotient of vector i; amps holds the
+ * normalised vectors one after the other (n_eig x 2 * 2^n doubles; NULL: not copied; the _dev variant takes device
+ * memory and returns the same bits); residuals[i] = |H y_i - theta_i y_i|.  max_matvec counts the H applications of all
+ * stages together.  info = {largest true residual, H applications of the recurrences, restarts, status, pairs returned}:
+ * status 0 all pairs converged, 1 some stage ended at a breakdown (its pair is exact in its space), 2 max_matvec spent -
+ * NOT an error: VQE_OK with the pairs found so far (info[4] of them; the other entries of eigenvalues and residuals are
+ * NaN, their vectors are not written).  Two calls with equal options return equal bits.
+ * THE KRYLOV LIMIT, as for vqe_lanczos: pair e is extreme in the Krylov space of a random vector orthogonal to the
+ * locked vectors, for H restricted to their complement; the locked vectors are eigenvectors only up to their reported
+ * residuals, which bounds what the later pairs can inherit from them.
+ * Refused before anything is launched, handle unchanged: as vqe_lanczos (no Hamiltonian, term shard, amplitude shard,
+ * which, max_basis < 2, max_matvec < 1, check_every < 1, tol), and VQE_EINVAL for n_eig outside 1 .. min(2^n, 64),
+ * keep < 0 or keep >= max_basis - 1.  The call changes neither the initial state, the resident batch and its results,
+ * the noise counter nor any later result of the handle.  vqe_last_kernel_ms reports the run. */
+typedef struct { int32_t which, n_eig, max_basis, max_matvec, check_every, keep;  /* keep 0: the library's rule */
+                 double tol; uint64_t seed; } vqe_lanczos_multi_opts_t;
+int vqe_lanczos_multi_default_opts(vqe_lanczos_multi_opts_t* o);   /* 0, 1, 128, 2000, 8, 0, 1e-10, 1 */
+int vqe_lanczos_multi(vqe_t* h, const vqe_lanczos_multi_opts_t* opts /* NULL: defaults */, double* eigenvalues /* n_eig */,
+                      double* amps_re_im /* n_eig x 2 * 2^n or NULL */, double* residuals /* n_eig */, double info[5]);
+int vqe_lanczos_multi_dev(vqe_t* h, const vqe_lanczos_multi_opts_t* opts, double* eigenvalues,
+                          void* dev_amps_re_im /* or NULL */, double* residuals, double info[5]);
 /* device pointer to the batch's f / energy array (float64[batch]) for on-device
  * reductions by the caller (e.g. torch.distributed all_reduce over RCCL) */
 int vqe_batch_energy_devptr(vqe_t* h, void** dev_ptr);

@@ -36,6 +36,12 @@ class LanczosOpts(C.Structure):
                 ("start_from_init", C.c_int32), ("tol", C.c_double), ("seed", C.c_uint64)]
 
 
+class LanczosMultiOpts(C.Structure):
+    """vqe_lanczos_multi_opts_t of include/vqe_hip.h"""
+    _fields_ = [("which", C.c_int32), ("n_eig", C.c_int32), ("max_basis", C.c_int32), ("max_matvec", C.c_int32),
+                ("check_every", C.c_int32), ("keep", C.c_int32), ("tol", C.c_double), ("seed", C.c_uint64)]
+
+
 # name -> (restype, argtypes); mirrors include/vqe_hip.h one to one
 SIGNATURES = {
     "vqe_create": (C.c_int, [C.c_int, C.c_int, C.POINTER(vp)]),
@@ -97,6 +103,9 @@ SIGNATURES = {
     "vqe_lanczos_default_opts": (C.c_int, [C.POINTER(LanczosOpts)]),
     "vqe_lanczos": (C.c_int, [vp, C.POINTER(LanczosOpts), c_f64p, c_f64p, c_f64p]),
     "vqe_lanczos_dev": (C.c_int, [vp, C.POINTER(LanczosOpts), c_f64p, vp, c_f64p]),
+    "vqe_lanczos_multi_default_opts": (C.c_int, [C.POINTER(LanczosMultiOpts)]),
+    "vqe_lanczos_multi": (C.c_int, [vp, C.POINTER(LanczosMultiOpts), c_f64p, c_f64p, c_f64p, c_f64p]),
+    "vqe_lanczos_multi_dev": (C.c_int, [vp, C.POINTER(LanczosMultiOpts), c_f64p, vp, c_f64p, c_f64p]),
     "vqe_batch_energy_devptr": (C.c_int, [vp, C.POINTER(vp)]),
     "vqe_batch_copy_energy": (C.c_int, [vp, vp]),
     "vqe_batch_set_trace": (C.c_int, [vp, C.c_int]),

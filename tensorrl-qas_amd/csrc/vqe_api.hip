@@ -2086,7 +2086,72 @@ int lanczos(vqe_t* h, const vqe_lanczos_opts_t* opts, double* eigenvalue, void* 
   }
   return VQE_OK;
 }
+
+// Everything a vqe_lanczos_multi call can be refused for, before anything is launched or given up.
+int lanczos_multi_check(vqe_t* h, const vqe_lanczos_multi_opts_t* opts, LzMultiOptions* o) {
+  vqe_lanczos_multi_opts_t d;
+  vqe_lanczos_multi_default_opts(&d);
+  if (opts) d = *opts;
+  if (!h->ham_set) return fail(h, VQE_ESTATE, "no Hamiltonian set");
+  if (h->shard_world > 1)
+    return fail(h, VQE_ESTATE, "vqe_lanczos_multi on a term-sharded handle: a shard's spectrum is not the Hamiltonian's");
+  if (h->amp_world > 1)
+    return fail(h, VQE_ESTATE, "vqe_lanczos_multi on an amplitude-sharded handle: it holds a slice of the register");
+  if (d.which != 0 && d.which != 1) return fail(h, VQE_EINVAL, "vqe_lanczos_multi: which must be 0 (lowest) or 1 (highest)");
+  const int64_t most = std::min<int64_t>((int64_t)1 << h->n, kLzMaxEig);
+  if (d.n_eig < 1 || d.n_eig > most) return fail(h, VQE_EINVAL, "vqe_lanczos_multi: n_eig must be in 1 .. min(2^n, 64)");
+  if (d.max_basis < 2) return fail(h, VQE_EINVAL, "vqe_lanczos_multi: max_basis must be at least 2");
+  if (d.max_matvec < 1) return fail(h, VQE_EINVAL, "vqe_lanczos_multi: max_matvec must be at least 1");
+  if (d.check_every < 1) return fail(h, VQE_EINVAL, "vqe_lanczos_multi: check_every must be at least 1");
+  if (d.keep < 0 || d.keep >= d.max_basis - 1)
+    return fail(h, VQE_EINVAL, "vqe_lanczos_multi: keep must be 0 (the library's rule) or in 1 .. max_basis - 2");
+  if (!(d.tol > 0.0) || !std::isfinite(d.tol)) return fail(h, VQE_EINVAL, "vqe_lanczos_multi: tol must be positive and finite");
+  *o = LzMultiOptions{d.which, d.n_eig, d.max_basis, d.max_matvec, d.check_every, d.keep, d.tol, d.seed};
+  return VQE_OK;
+}
+
+int lanczos_multi(vqe_t* h, const vqe_lanczos_multi_opts_t* opts, double* eigenvalues, void* amps, bool amps_on_device,
+                  double* residuals, double info[5]) {
+  if (!h) return VQE_EINVAL;
+  if (!eigenvalues || !residuals || !info) return fail(h, VQE_EINVAL, "bad arguments");
+  LzMultiOptions o;
+  VQE_TRY(lanczos_multi_check(h, opts, &o));
+  HIP_TRY(h, hipSetDevice(h->dev));
+  VQE_TRY(lz_upload_ham(h->lz, h->ham_host, h->ham_ver, h->stream, h->err));
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(h, hipMemGetInfo(&free_b, &total_b));
+  h->last_run_dm = false;
+  int order[kLzMaxEig];
+  HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
+  const int rc = lz_run_multi(h->lz, h->n, h->stream, o, free_b, eigenvalues, residuals, order, info, h->err);
+  HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
+  VQE_TRY(rc);
+  if (amps) {
+    const size_t bytes = ((size_t)16) << h->n;
+    for (int i = 0; i < (int)info[4]; ++i)
+      HIP_TRY(h, hipMemcpyAsync((char*)amps + (size_t)i * bytes, lz_multi_vector(h->lz, h->n, order[i]), bytes,
+                                amps_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
+    if (!amps_on_device) HIP_TRY(h, hipStreamSynchronize(h->stream));
+  }
+  return VQE_OK;
+}
 }  // namespace
+}
+
+int vqe_lanczos_multi_default_opts(vqe_lanczos_multi_opts_t* o) {
+  if (!o) return VQE_EINVAL;
+  *o = vqe_lanczos_multi_opts_t{0, 1, 128, 2000, 8, 0, 1e-10, 1ull};
+  return VQE_OK;
+}
+
+int vqe_lanczos_multi(vqe_t* h, const vqe_lanczos_multi_opts_t* opts, double* eigenvalues, double* amps_re_im, double* residuals,
+                      double info[5]) {
+  return lanczos_multi(h, opts, eigenvalues, amps_re_im, false, residuals, info);
+}
+
+int vqe_lanczos_multi_dev(vqe_t* h, const vqe_lanczos_multi_opts_t* opts, double* eigenvalues, void* dev_amps_re_im,
+                          double* residuals, double info[5]) {
+  return lanczos_multi(h, opts, eigenvalues, dev_amps_re_im, true, residuals, info);
 }
 
 int vqe_lanczos_default_opts(vqe_lanczos_opts_t* o) {

@@ -18,6 +18,9 @@
 // the same value.  A negligible beta_j is a breakdown (an exact invariant subspace): k_lz_norm does
 // not divide and sets a device flag on which every kernel queued behind it exits at once.  The host reads alpha, beta
 // and the flag every check_every steps (lanczos_host.h: lz_decide) and never anything state-sized.
+//
+// Several eigenpairs with their multiplicities (vqe_lanczos_multi) are at the end of the file: the same
+// step kernels driven by the LzMulti state machine, one stage per pair, and k_lz_rotate for the thick restart.
 #pragma once
 #include "vqe_device.h"
 #include "vqe_devbuf.h"
@@ -428,6 +431,7 @@ struct LzWork {
   DevBufExact<double2> basis, work;     // the stored vectors; w, y, H y
   DevBuf<double> ab, pa, pn, s, out;    // alpha[m] beta[m] brk[2]; partials; Ritz coefficients; {theta, r}
   DevBuf<double2> pp, coef;
+  DevBuf<double> rot;                   // vqe_lanczos_multi: the rotation S of a thick restart
   size_t vector_bytes() const { return (basis.cap + work.cap) * sizeof(double2); }
 };
 
@@ -568,6 +572,188 @@ inline int lz_run(LzWork& W, int n, hipStream_t st, const double2* init, const L
   info[1] = (double)c.matvecs;
   info[2] = (double)restarts;
   info[3] = decision == LZ_CONVERGED ? 0.0 : (decision == LZ_BREAKDOWN ? 1.0 : 2.0);
+  return VQE_OK;
+}
+
+// ---- several eigenpairs: thick restart, locking by deflation (vqe_lanczos_multi) -------------------------------
+// Locked eigenvectors sit in basis slots 0 .. e-1, the active basis of stage e behind them; k_lz_proj / k_lz_coef /
+// k_lz_sub run over (V, e + j + 1), so the full reorthogonalisation deflates the locked vectors as it goes.  The stage /
+// look / restart / lock logic is LzMulti (lanczos_host.h); lz_run_multi executes its commands with the kernels above and
+// the one below.
+
+constexpr size_t kLzRotLds = 32768;        // bytes of LDS a block of k_lz_rotate stages: 4 blocks on a CU's 160 KiB
+constexpr int kLzRotQ = 4;                 // outputs a thread accumulates from one LDS read
+constexpr int kLzRotMaxBlocks = 4096;
+static_assert((size_t)kLzMaxActive * sizeof(double2) <= kLzRotLds, "a block of k_lz_rotate stages at least one amplitude of every vector");
+
+// The thick restart, in place over the m active vectors A[i] = A + i 2^n:  A[q] <- sum_i S[i][q] A[i] for q < r (S real,
+// S[i][q] = S[i * ld + q], rows padded with zeros to ld = a multiple of kLzRotQ), and A[r] <- resid where resid != NULL.
+// A block stages a chunk of C = 2^lc amplitudes of all m vectors in LDS (m C 16 bytes <= kLzRotLds; [i][c], so a wave
+// reads consecutive 16-byte words), then writes the r outputs of that chunk: every input of an amplitude is read before
+// any of its outputs is written, and no other block touches the chunk.  Thread t owns amplitude t mod C and the output
+// groups q0 = kLzRotQ (t / C), + kLzRotQ 256 / C, ..; sums over i ascending, no atomics.
+__global__ void __launch_bounds__(kLzThreads) k_lz_rotate(int n, double2* A, int m, int r, int ld, const double* __restrict__ S,
+                                                          const double2* __restrict__ resid, int lc) {
+  extern __shared__ double2 lz_rot[];
+  const uint32_t dim = 1u << n;
+  const uint32_t C = 1u << lc;
+  const uint32_t c = threadIdx.x & (C - 1u);
+  const int grp = (int)(threadIdx.x >> lc), ngrp = kLzThreads >> lc;
+  const int total = m << lc;
+  for (uint32_t base = blockIdx.x * C; base < dim; base += gridDim.x * C) {
+    __syncthreads();      // the readers of the previous chunk are done with the stage
+    for (int t = threadIdx.x; t < total; t += kLzThreads) {
+      const uint32_t p = base + ((uint32_t)t & (C - 1u));
+      lz_rot[t] = p < dim ? A[((size_t)(t >> lc) << n) + p] : make_double2(0.0, 0.0);
+    }
+    __syncthreads();
+    const uint32_t p = base + c;
+    if (p < dim) {
+      for (int q0 = grp * kLzRotQ; q0 < r; q0 += ngrp * kLzRotQ) {
+        double2 acc[kLzRotQ];
+#pragma unroll
+        for (int k = 0; k < kLzRotQ; ++k) acc[k] = make_double2(0.0, 0.0);
+        const double* row = S + q0;
+        for (int i = 0; i < m; ++i, row += ld) {
+          const double2 a = lz_rot[((uint32_t)i << lc) + c];
+#pragma unroll
+          for (int k = 0; k < kLzRotQ; ++k) {
+            acc[k].x += row[k] * a.x;
+            acc[k].y += row[k] * a.y;
+          }
+        }
+#pragma unroll
+        for (int k = 0; k < kLzRotQ; ++k)
+          if (q0 + k < r) A[((size_t)(q0 + k) << n) + p] = acc[k];
+      }
+      if (resid && grp == 0) A[((size_t)r << n) + p] = resid[p];
+    }
+  }
+}
+
+// log2 of the chunk of k_lz_rotate for m active vectors: the largest power of two with m C 16 <= kLzRotLds, C <= 256
+inline int lz_rotate_chunk_log2(int m) {
+  int lc = 0;
+  while (lc < 8 && ((size_t)m << (lc + 1)) * sizeof(double2) <= kLzRotLds) ++lc;
+  return lc;
+}
+
+// The whole run on stream st, after lz_upload_ham.  The eigenvectors are left in the basis slots; pair i of the answer
+// (eigenvalues ascending for which = 0, descending for which = 1) is lz_multi_vector(W, n, order[i]).
+// info = {largest true residual, H applications of the recurrences, restarts, status, pairs returned}.
+inline const double2* lz_multi_vector(const LzWork& W, int n, int slot) { return W.basis.p + ((size_t)slot << n); }
+
+inline int lz_run_multi(LzWork& W, int n, hipStream_t st, const LzMultiOptions& o, size_t free_bytes, double* eigenvalues,
+                        double* residuals, int* order, double info[5], std::string& err) {
+  const size_t dim = (size_t)1 << n;
+  const int M = lz_multi_slots(((uint64_t)free_bytes + W.vector_bytes()) / 4, n, o.max_basis, o.n_eig);
+  if (!lz_multi_fits(M, n, o.max_basis, o.n_eig))
+    return fail(err, VQE_ENOMEM, "vqe_lanczos_multi keeps n_eig - 1 locked vectors and at least 2 active basis vectors beside 3 work "
+                                 "vectors of 2^n complex128: a quarter of the free device memory does not hold them");
+  const int capmax = lz_stage_capacity(M, n, o.max_basis, 0);
+  const int nblk = (int)std::min<size_t>((dim + kLzChunk - 1) / kLzChunk, (size_t)kLzMaxBlocks);
+  HIP_TRY(err, W.basis.reserve((size_t)M * dim));
+  HIP_TRY(err, W.work.reserve((size_t)kLzWorkVectors * dim));
+  HIP_TRY(err, W.ab.reserve((size_t)2 * capmax + 2));
+  HIP_TRY(err, W.pa.reserve(nblk));
+  HIP_TRY(err, W.pn.reserve(nblk));
+  HIP_TRY(err, W.s.reserve(capmax));
+  HIP_TRY(err, W.rot.reserve((size_t)capmax * (capmax + kLzRotQ)));
+  HIP_TRY(err, W.out.reserve(2));
+  HIP_TRY(err, W.pp.reserve((size_t)M * nblk));
+  HIP_TRY(err, W.coef.reserve(M));
+  double2* const V = W.basis.p;
+  double2* const w = W.work.p;
+  double2* const y = W.work.p + dim;
+  double2* const hy = W.work.p + 2 * dim;
+  double* const alpha = W.ab.p;
+  double* const beta = W.ab.p + capmax;
+  double* const brk = W.ab.p + 2 * capmax;
+  const double thresh = 1e-13 * W.hnorm;
+  const dim3 grid((unsigned)nblk), block(kLzThreads);
+  const auto vec = [&](int k) { return V + (size_t)k * dim; };
+  const auto orthogonalise = [&](int cnt) {      // two passes of classical Gram-Schmidt of w against slots 0 .. cnt-1
+    for (int pass = 0; pass < 2; ++pass) {
+      hipLaunchKernelGGL(k_lz_proj, grid, block, 0, st, n, (const double2*)V, cnt, (const double2*)w, W.pp.p, (const double*)brk);
+      hipLaunchKernelGGL(k_lz_coef, dim3((unsigned)cnt), block, 0, st, (const double2*)W.pp.p, nblk, W.coef.p, (const double*)brk);
+      hipLaunchKernelGGL(k_lz_sub, grid, block, 0, st, n, (const double2*)V, cnt, (const double2*)W.coef.p, w, W.pn.p, (const double*)brk);
+    }
+  };
+
+  std::vector<double> ab((size_t)2 * capmax + 2);
+  LzMulti mach(o, n, M);
+  for (;;) {
+    const LzMultiCmd c = mach.cmd();
+    if (c.op == LZM_DONE) break;
+    const int e = c.stage;
+    if (c.op == LZM_START) {
+      HIP_TRY(err, hipMemsetAsync(W.ab.p, 0, ((size_t)2 * capmax + 2) * sizeof(double), st));
+      hipLaunchKernelGGL(k_lz_start, grid, block, 0, st, n, c.seed, w, W.pn.p);
+      if (e > 0) orthogonalise(e);
+      hipLaunchKernelGGL(k_lz_norm, grid, block, 0, st, n, (const double2*)w, vec(e), (const double*)W.pn.p, (const double*)W.pa.p, nblk,
+                         alpha, beta, brk, -1, 0.0);
+      mach.started();
+    } else if (c.op == LZM_STEPS) {
+      for (int j = c.j0; j < c.j1; ++j) {
+        const bool prev = !(j == c.j0 && c.no_prev);
+        hipLaunchKernelGGL(k_lz_apply, grid, block, 0, st, W.ham, n, (const double2*)vec(e + j),
+                           prev ? (const double2*)vec(e + j - 1) : nullptr, (const double*)(prev ? beta + j - 1 : nullptr), w, W.pa.p,
+                           (const double*)brk);
+        hipLaunchKernelGGL(k_lz_axpy, grid, block, 0, st, n, (const double2*)vec(e + j), w, (const double*)W.pa.p, nblk, (const double*)brk);
+        orthogonalise(e + j + 1);
+        hipLaunchKernelGGL(k_lz_norm, grid, block, 0, st, n, (const double2*)w, j + 1 < c.capacity ? vec(e + j + 1) : w,
+                           (const double*)W.pn.p, (const double*)W.pa.p, nblk, alpha, beta, brk, j, thresh);
+      }
+      HIP_TRY(err, hipGetLastError());
+      HIP_TRY(err, hipMemcpyAsync(ab.data(), W.ab.p, ab.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+      HIP_TRY(err, hipStreamSynchronize(st));
+      int broke = -1;
+      if (ab[(size_t)2 * capmax] != 0.0) {
+        broke = (int)ab[(size_t)2 * capmax + 1];
+        if (broke < 0) return fail(err, VQE_EINVAL, "vqe_lanczos_multi: the start vector of a stage is zero");
+      }
+      mach.steps_done(ab.data(), ab.data() + capmax, broke);
+    } else if (c.op == LZM_RESTART) {
+      const int lc = lz_rotate_chunk_log2(c.m);
+      const size_t chunks = (dim + ((size_t)1 << lc) - 1) >> lc;
+      HIP_TRY(err, hipMemcpyAsync(W.rot.p, c.s, (size_t)c.m * c.ld * sizeof(double), hipMemcpyHostToDevice, st));
+      hipLaunchKernelGGL(k_lz_rotate, dim3((unsigned)std::min<size_t>(chunks, (size_t)kLzRotMaxBlocks)), block,
+                         ((size_t)c.m << lc) * sizeof(double2), st, n, vec(e), c.m, c.r, c.ld, (const double*)W.rot.p,
+                         c.with_resid ? (const double2*)w : nullptr, lc);
+      HIP_TRY(err, hipGetLastError());
+      HIP_TRY(err, hipStreamSynchronize(st));      // S is rebuilt at the next restart
+      mach.restarted();
+    } else {      // LZM_LOCK: the Ritz vector into slot e, its Rayleigh quotient and true residual by one more application
+      HIP_TRY(err, hipMemsetAsync(brk, 0, 2 * sizeof(double), st));
+      HIP_TRY(err, hipMemcpyAsync(W.s.p, c.s, (size_t)c.m * sizeof(double), hipMemcpyHostToDevice, st));
+      hipLaunchKernelGGL(k_lz_ritz, grid, block, 0, st, n, (const double2*)vec(e), c.m, (const double*)W.s.p, y, W.pn.p);
+      hipLaunchKernelGGL(k_lz_norm, grid, block, 0, st, n, (const double2*)y, vec(e), (const double*)W.pn.p, (const double*)W.pa.p, nblk,
+                         alpha, beta, brk, -1, 0.0);
+      hipLaunchKernelGGL(k_lz_apply, grid, block, 0, st, W.ham, n, (const double2*)vec(e), (const double2*)nullptr, (const double*)nullptr,
+                         hy, W.pa.p, (const double*)brk);
+      hipLaunchKernelGGL(k_lz_resid, grid, block, 0, st, n, (const double2*)vec(e), (const double2*)hy, (const double*)W.pa.p, nblk, W.pn.p);
+      hipLaunchKernelGGL(k_lz_final, dim3(1), block, 0, st, (const double*)W.pa.p, (const double*)W.pn.p, nblk, W.out.p);
+      HIP_TRY(err, hipGetLastError());
+      double out[2] = {0.0, 0.0};
+      HIP_TRY(err, hipMemcpyAsync(out, W.out.p, sizeof(out), hipMemcpyDeviceToHost, st));
+      HIP_TRY(err, hipStreamSynchronize(st));
+      mach.locked(out[0], out[1]);
+    }
+  }
+  const int pairs = mach.pairs();
+  for (int i = 0; i < pairs; ++i) order[i] = i;
+  std::stable_sort(order, order + pairs, [&](int a, int b) { return o.which ? mach.theta(a) > mach.theta(b) : mach.theta(a) < mach.theta(b); });
+  double worst = 0.0;
+  for (int i = 0; i < o.n_eig; ++i) {
+    eigenvalues[i] = i < pairs ? mach.theta(order[i]) : std::numeric_limits<double>::quiet_NaN();
+    residuals[i] = i < pairs ? mach.residual(order[i]) : std::numeric_limits<double>::quiet_NaN();
+    if (i < pairs) worst = std::max(worst, residuals[i]);
+  }
+  info[0] = worst;
+  info[1] = (double)mach.matvecs();
+  info[2] = (double)mach.restarts();
+  info[3] = (double)mach.status();
+  info[4] = (double)pairs;
   return VQE_OK;
 }
 

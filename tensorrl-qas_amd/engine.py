@@ -397,6 +397,56 @@ class VQEEngine:
         value, vec, _ = self.lanczos("min", True, **opts)
         return value, vec
 
+    def lanczos_multi_opts(self, k, which="min", **opts):
+        """vqe_lanczos_multi_opts_t with the library's defaults (max_basis 128, max_matvec 2000, check_every 8, keep 0 =
+        the library's rule, tol 1e-10, seed 1), ``n_eig = k`` and the given fields replaced."""
+        o = _lib.LanczosMultiOpts()
+        self._chk(self._lib.vqe_lanczos_multi_default_opts(C.byref(o)))
+        ends = {"min": 0, "max": 1, 0: 0, 1: 1}
+        if which not in ends:
+            raise ValueError("which must be 'min' or 'max'")
+        o.which = ends[which]
+        o.n_eig = int(k)
+        names = {f[0] for f in _lib.LanczosMultiOpts._fields_} - {"which", "n_eig"}
+        for key, v in opts.items():
+            if key not in names:
+                raise TypeError(f"unknown Lanczos option {key!r} (known: {sorted(names)})")
+            setattr(o, key, float(v) if key == "tol" else int(v))
+        return o
+
+    def _lanczos_multi_info(self, info, res):
+        pairs = int(info[4])
+        return {"residual": info[0], "matvecs": int(info[1]), "restarts": int(info[2]), "status": int(info[3]),
+                "status_name": self.LANCZOS_STATUS[int(info[3])], "pairs": pairs, "residuals": res[:pairs].copy()}
+
+    def lanczos_multi(self, k, which="min", want_vectors=True, **opts):
+        """The ``k`` lowest ("min", ascending) or highest ("max", descending) eigenpairs of the Hamiltonian, copies of a
+        degenerate eigenvalue included, by thick-restart Lanczos with locking on the GPU (vqe_lanczos_multi).  Returns
+        (values[pairs], complex128[pairs, 2^n] or None, info) with info = dict(residual - the largest -, residuals[pairs],
+        matvecs, restarts, status, status_name, pairs); pairs = k unless the status is "budget" (no error: the pairs found
+        before ``max_matvec`` applications were spent).  ``hamiltonian.level_structure`` groups the values into levels."""
+        o = self.lanczos_multi_opts(k, which, **opts)
+        k = max(int(k), 1)
+        ev, res = np.empty(k, np.float64), np.empty(k, np.float64)
+        info = (C.c_double * 5)()
+        vec = np.empty((k, 2 << self.n_qubits), np.float64) if want_vectors else None
+        self._chk(self._lib.vqe_lanczos_multi(self._h, C.byref(o), _p(ev, c_f64p),
+                                              _p(vec, c_f64p) if want_vectors else C.cast(None, c_f64p), _p(res, c_f64p), info))
+        d = self._lanczos_multi_info(info, res)
+        return ev[:d["pairs"]].copy(), (vec[:d["pairs"]].view(np.complex128) if want_vectors else None), d
+
+    def lanczos_multi_dev(self, dev_ptr: int, k, which="min", **opts):
+        """lanczos_multi with the vectors written to device memory (complex128[k, 2^n], asynchronous on the handle's
+        stream; 0: no vectors).  Returns (values[pairs], info)."""
+        o = self.lanczos_multi_opts(k, which, **opts)
+        k = max(int(k), 1)
+        ev, res = np.empty(k, np.float64), np.empty(k, np.float64)
+        info = (C.c_double * 5)()
+        self._chk(self._lib.vqe_lanczos_multi_dev(self._h, C.byref(o), _p(ev, c_f64p), C.c_void_p(int(dev_ptr) or None),
+                                                  _p(res, c_f64p), info))
+        d = self._lanczos_multi_info(info, res)
+        return ev[:d["pairs"]].copy(), d
+
     # -- batches of circuits --------------------------------------------------------------
     def batch_load(self, circuits, thetas):
         """``circuits``: list of Circuit; ``thetas``: list of arrays (x0 / theta per circuit)."""

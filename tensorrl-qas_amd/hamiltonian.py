@@ -218,6 +218,41 @@ def extreme_eigenvalues_device(ham, device_id=0, **opts):
         eng.close()
 
 
+def lowest_eigenpairs_device(ham, k, device_id=0, return_tensor=False, **opts):
+    """The ``k`` lowest eigenpairs on the GPU, copies of a degenerate eigenvalue included: (values[k] ascending,
+    vectors complex128[k, 2^n], info) by the library's thick-restart Lanczos (VQEEngine.lanczos_multi; ``opts``:
+    max_basis, max_matvec, check_every, keep, tol, seed).  ``return_tensor=True``: the vectors stay on the device, as a
+    complex128 torch tensor [k, 2^n] on ``cuda:device_id``.  Fewer than k rows come back only with info["status_name"]
+    == "budget".  ``level_structure(values, atol)`` turns the values into (level, multiplicity)."""
+    eng = _device_engine(ham, device_id)
+    try:
+        if not return_tensor:
+            return eng.lanczos_multi(k, "min", True, **opts)
+        import torch
+        vec = torch.empty((int(k), 1 << ham.n), dtype=torch.complex128, device=f"cuda:{device_id}")
+        values, info = eng.lanczos_multi_dev(vec.data_ptr(), k, "min", **opts)
+        eng.sync()      # the vectors were written on the engine's stream: nothing else may read them before
+        return values, vec[:info["pairs"]], info
+    finally:
+        eng.close()
+
+
+def level_structure(values, atol=1e-8):
+    """[(level, multiplicity), ...] of eigenvalues in the order given (ascending or descending): neighbours closer than
+    ``atol`` to the FIRST value of a level belong to it; the level is the mean of its members.  CH2-8q's lowest values give
+    (-37.086298, 3) first.  The last level of a list of k values may be cut by k."""
+    out = []
+    group = []
+    for v in (float(x) for x in values):
+        if group and abs(v - group[0]) > atol:
+            out.append((sum(group) / len(group), len(group)))
+            group = []
+        group.append(v)
+    if group:
+        out.append((sum(group) / len(group), len(group)))
+    return out
+
+
 def _lanczos(ham, tol, want_vector):
     """(min, max) eigenvalue of a PauliHamiltonian by matrix-free Lanczos (scipy ``eigsh`` on a
     LinearOperator that applies the Pauli sum): replaces the reference's dense ``eigvals`` - the
@@ -261,7 +296,10 @@ def write_npz(path, ham, eigvals=None, dense_limit=12):
     ``hamiltonian`` (big-endian np.kron order, as the reference stores it) is written up to
     ``dense_limit`` qubits - beyond it cannot exist and the loaders of this package do not need it;
     ``eigvals`` defaults to the full spectrum when the dense matrix is built, else to the Lanczos
-    (min, max).  ``ham`` must be in the FIXED-path convention (string character k = simulator qubit k)."""
+    (min, max).  The low end of the spectrum with its multiplicities, where the dense matrix cannot exist, comes from
+    the device: ``eigvals=lowest_eigenpairs_device(ham, k)[0]`` (ascending, as the reference stores them; its minimum
+    is the environments' ``min_eig``); this default does not change.
+    ``ham`` must be in the FIXED-path convention (string character k = simulator qubit k)."""
     strings = pauli_strings(ham)
     out = {"weights": np.asarray(ham.coeff, np.float64), "paulis": np.array(strings), "energy_shift": 0}
     if ham.n <= dense_limit:

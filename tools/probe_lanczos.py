@@ -6,7 +6,13 @@ applications, the wall time of the host path and the difference of the two eigen
 
     python3 tools/probe_lanczos.py [out.json]        (profiles/lanczos.json by default; needs a GPU)
 
-The table it prints is in DESIGN 4.14."""
+    python3 tools/probe_lanczos.py --multi [out.json]   (profiles/lanczos_multi.json by default)
+
+--multi: several eigenpairs (VQEEngine.lanczos_multi: thick restart, locking) beside vqe_lanczos of the same build in the
+same session, on the same problems: device ms (median of 3 after 1 warm-up) and H applications for k = 1 and k = 4 at the
+library's defaults, and the k = 1 figures of both entry points at max_basis 4, 8 and 128 (max_matvec 5000).
+
+The tables it prints are in DESIGN 4.14."""
 import json
 import os
 import statistics
@@ -17,10 +23,46 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import tensorrl_qas_amd as tq  # noqa: E402
 
-out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "lanczos.json")
+multi = "--multi" in sys.argv[1:]
+args = [a for a in sys.argv[1:] if a != "--multi"]
+out = args[0] if args else os.path.join(ROOT, "profiles", "lanczos_multi.json" if multi else "lanczos.json")
 os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
 problems = [(f"heisenberg_{n}q", tq.hamiltonian.heisenberg(n)[0]) for n in (12, 16, 20)]
 problems.append(("synthetic_LiH12", tq.hamiltonian.synthetic_lih12()))
+
+
+def timed(eng, call, reps=4):
+    ms = []
+    for _ in range(reps):
+        res = call()
+        ms.append(eng.last_kernel_ms())
+    return res, statistics.median(ms[1:])
+
+
+if multi:
+    rows = []
+    for name, ham in problems:
+        eng = tq.VQEEngine(ham.n)
+        eng.set_hamiltonian(ham.xmask, ham.zmask, ham.coeff)
+        for basis in (128, 8, 4):
+            (val, _, info), ms = timed(eng, lambda: eng.lanczos("min", want_vector=False, max_basis=basis, max_matvec=5000))
+            rows.append({"problem": name, "entry": "vqe_lanczos", "k": 1, "max_basis": basis, "device_ms": ms, "matvecs": info["matvecs"],
+                         "restarts": info["restarts"], "status": info["status_name"], "residual": info["residual"], "values": [val]})
+            print(json.dumps(rows[-1]), flush=True)
+            for k in ((1, 4) if basis == 128 else (1,)):
+                (vals, _, info), ms = timed(eng, lambda: eng.lanczos_multi(k, "min", want_vectors=False, max_basis=basis, max_matvec=5000))
+                rows.append({"problem": name, "entry": "vqe_lanczos_multi", "k": k, "max_basis": basis, "device_ms": ms,
+                             "matvecs": info["matvecs"], "restarts": info["restarts"], "status": info["status_name"],
+                             "residual": info["residual"], "pairs": info["pairs"], "values": [float(v) for v in vals]})
+                print(json.dumps(rows[-1]), flush=True)
+        eng.close()
+    json.dump({"script": "tools/probe_lanczos.py --multi", "options": "tol 1e-10, check_every 8, seed 1, keep 0, max_matvec 5000",
+               "rows": rows}, open(out, "w"), indent=1)
+    print("| problem | entry | k | max_basis | H applications | restarts | device ms | status |\n|---|---|---|---|---|---|---|---|")
+    for r in rows:
+        print(f"| {r['problem']} | {r['entry']} | {r['k']} | {r['max_basis']} | {r['matvecs']} | {r['restarts']} | {r['device_ms']:.2f} | {r['status']} |")
+    sys.exit(0)
+
 rows = []
 for name, ham in problems:
     eng = tq.VQEEngine(ham.n)

@@ -50,8 +50,8 @@ enum {
   VQE_GATE_DEPOL1 = 4, /* DepolarizingNoise(q0, p1)                       */
   VQE_GATE_DEPOL2 = 5, /* TwoQubitDepolarizingNoise(q0, q1, p2)           */
   VQE_GATE_RXX = 6,    /* exp(+i*theta/2 * X_q0 X_q1), q0 != q1, param_idx */
-  VQE_GATE_RYY = 7,    /* exp(+i*theta/2 * Y_q0 Y_q1)   (symmetric in q0, q1; refused by the */
-  VQE_GATE_RZZ = 8     /* exp(+i*theta/2 * Z_q0 Z_q1)    exact channel mode)                 */
+  VQE_GATE_RYY = 7,    /* exp(+i*theta/2 * Y_q0 Y_q1)   (symmetric in q0, q1; the exact channel   */
+  VQE_GATE_RZZ = 8     /* exp(+i*theta/2 * Z_q0 Z_q1)    mode takes them after vqe_set_dm_rot2)   */
 };
 
 /* ---- lifetime ------------------------------------------------------------------------
@@ -209,6 +209,25 @@ int vqe_dm_batch_info(vqe_t* h, int64_t out[4]);
  * energy run - vqe_dm_batch_info reports the count - and VQE_ENOMEM when not even one fits.  The gradient of a circuit
  * has the same bits whatever the batch around it, its position and max_resident.  Noise counter: unchanged. */
 int vqe_set_dm_grad(vqe_t* h, int enable);
+/* Exact channel mode only: Kraus sets in the two noise slots (csrc/dm_host.h).  The channel applied at
+ * VQE_GATE_DEPOL1 gates becomes rho -> sum_k K1_k rho K1_k^+ (K1: n1 x 2 x 2 complex, re / im interleaved, row-major), the
+ * one at VQE_GATE_DEPOL2 gates sum_k K2_k rho K2_k^+ (K2: n2 x 4 x 4, basis index = bit(q0) + 2 bit(q1) of the GATE's two
+ * qubits in the gate's order - a channel need not be symmetric in them).  n1 == 0 leaves that slot on the depolarising
+ * channel of vqe_set_noise (p1), n2 == 0 likewise (p2); both 0 removes the override.  0 <= n1 <= 16, 0 <= n2 <= 64.
+ * VQE_EINVAL with the handle unchanged for a count out of range, a NULL array with a positive count, or a set that is
+ * not trace preserving (max |sum K^+ K - I| > 1e-12).  The call touches neither the seed, the noise counter, p1 / p2 nor
+ * the results of the resident batch; a later vqe_set_noise does not remove the override.
+ * While an override is installed the mode 1 runs use it - energies, COBYLA and env-steps on the serial and the batched
+ * path, gradient and L-BFGS under vqe_set_dm_grad - and what has no form for a general channel is refused with
+ * VQE_ESTATE before anything is loaded or launched, noise counter unchanged: every energy, gradient, state, reduction
+ * and optimiser run of mode 0, and vqe_get_state* in any mode.  Without an override nothing changes. */
+int vqe_set_noise_kraus(vqe_t* h, int n1, const double* K1, int n2, const double* K2);
+/* out[0], out[1]: Kraus operators installed in the one- / two-qubit slot, 0 = none */
+int vqe_noise_kraus_info(vqe_t* h, int32_t out[2]);
+/* 1: the exact channel mode takes VQE_GATE_RXX / RYY / RZZ - a two-qubit rotation is a member of a superoperator block
+ * like a CNOT - on the serial and the batched path, gradient and L-BFGS included.  0 (default): refused with VQE_EINVAL
+ * as before.  Accepted on any handle; it takes effect in mode 1. */
+int vqe_set_dm_rot2(vqe_t* h, int enable);
 /* host only (needs no device): the superoperator blocks the exact channel mode would sweep for this circuit - windows[2k],
  * windows[2k+1] = the two qubits (a, b) of block k, S[k][2][16][16] = real and imaginary part of its 16 x 16 matrix, entry
  * index = ket_a + 2 ket_b + 4 bra_a + 8 bra_b.  windows == NULL or S == NULL: only the count.  For tests of the fusion. */

@@ -13,16 +13,33 @@
 namespace vqe {
 
 // entry (r, k) of one member's superoperator: G[(i, j), (i', j')] = U[i][i'] conj(U[j][j']), r = i + 4 j, k = i' + 4 j'
-// (i = ket bits (a, b), j = bra bits).  cs / sn: cos / sin of half the member's angle (rotations only); dep: the three
-// channel tables of DmBatchTables.
+// (i = ket bits (a, b), j = bra bits).  cs / sn: cos / sin of half the member's angle (rotations only); dep: the
+// channel tables of DmBatchTables (a two-qubit channel reads slice 2 + pos; pos is 0 unless a two-qubit Kraus set is
+// installed).
+
+// entry [x][y] of P (x) P on the window for kind = G_RXX / G_RYY / G_RZZ: real and symmetric for all three
+VQE_HD inline double dm_pauli2_entry(int kind, int x, int y) {
+  const double even = ((x ^ (x >> 1)) & 1) ? -1.0 : 1.0;      // +1 on |00>, |11>
+  if (kind == G_RZZ) return x == y ? even : 0.0;
+  if (x != (y ^ 3)) return 0.0;
+  return kind == G_RXX ? 1.0 : -even;                          // Y (x) Y: -1 between |00> and |11>, +1 between |01> and |10>
+}
+
 VQE_HD inline void dm_member_entry(int kind, int pos, double cs, double sn, const double* dep, int r, int k, double& gr, double& gi) {
   if (kind == G_DEPOL1 || kind == G_DEPOL2) {
-    const double* t = dep + (kind == G_DEPOL2 ? 2 : pos) * 512;
+    const double* t = dep + (kind == G_DEPOL2 ? 2 + pos : pos) * 512;
     gr = t[r * 16 + k];
     gi = t[256 + r * 16 + k];
     return;
   }
   const int i = r & 3, j = r >> 2, ip = k & 3, jp = k >> 2;
+  if (gate_is_rot2(kind)) {      // U = cs I + i sn P (x) P: U[x][y] = cs [x == y] + i sn PP[x][y]
+    const double ur = i == ip ? cs : 0.0, ui_ = sn * dm_pauli2_entry(kind, i, ip);
+    const double vr = j == jp ? cs : 0.0, vi = sn * dm_pauli2_entry(kind, j, jp);
+    gr = ur * vr + ui_ * vi;      // U[i][ip] conj(U[j][jp])
+    gi = ui_ * vr - ur * vi;
+    return;
+  }
   if (kind == G_CNOT) {      // pos: the control's window position
     const int pt = pos ^ 1;
     const bool ui = i == (ip ^ (((ip >> pos) & 1) << pt)), uj = j == (jp ^ (((jp >> pos) & 1) << pt));
@@ -67,11 +84,16 @@ VQE_HD inline void dm_build_entry(int kind, int pos, double cs, double sn, const
 // ---- the derivative chain (vqe_dm_grad.h) -------------------------------------------------------------
 // A rotation member is rho -> U rho U^+ with U = exp(+i theta/2 P), so d/dtheta of it is D G with the fixed generator
 // D rho = (i/2) (P rho - rho P):  D[(i, j), (i', j')] = (i/2) (P[i][i'] [j == j'] - [i == i'] P[j'][j]), P acting on
-// window position pos.  dS/dtheta of a block is its member list with D inserted behind the member.
+// window position pos.  dS/dtheta of a block is its member list with D inserted behind the member.  A two-qubit
+// rotation has P (x) P on the whole window in P's place (real and symmetric: D is purely imaginary).
 VQE_HD inline void dm_generator_entry(int kind, int pos, int r, int k, double& gr, double& gi) {
   const int i = r & 3, j = r >> 2, ip = k & 3, jp = k >> 2, other = pos ^ 1;
   gr = 0.0;
   gi = 0.0;
+  if (gate_is_rot2(kind)) {
+    gi = 0.5 * ((j == jp ? dm_pauli2_entry(kind, i, ip) : 0.0) - (i == ip ? dm_pauli2_entry(kind, jp, j) : 0.0));
+    return;
+  }
   for (int side = 0; side < 2; ++side) {      // 0: (i/2) P on the ket index, 1: -(i/2) P^T on the bra index
     const int x = side ? jp : i, y = side ? j : ip;      // the entry P[x][y] that is wanted
     if ((side ? i != ip : j != jp) || ((x >> other) & 1) != ((y >> other) & 1)) continue;

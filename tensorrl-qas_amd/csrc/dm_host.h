@@ -66,10 +66,62 @@ inline void sup_depol(int mask, double p, Sup& S) {
   }
 }
 
+// A Kraus set in the place of a depolarising channel (vqe_set_noise_kraus): rho -> sum_k K_k rho K_k^+.
+// One-qubit operators K[k][2][2] on window position pos.
+inline void sup_kraus_1q(const cplx* K, int n1, int pos, Sup& S) {
+  for (int r = 0; r < 16; ++r) for (int c = 0; c < 16; ++c) S.m[r][c] = 0.0;
+  for (int k = 0; k < n1; ++k) {
+    cplx R[2][2] = {{K[4 * k], K[4 * k + 1]}, {K[4 * k + 2], K[4 * k + 3]}}, U[4][4];
+    embed_1q(R, pos, U);
+    Sup P;
+    sup_conj(U, P);
+    for (int r = 0; r < 16; ++r) for (int c = 0; c < 16; ++c) S.m[r][c] += P.m[r][c];
+  }
+}
+// Two-qubit operators K[k][4][4], basis index = bit(q0) + 2 bit(q1) of the GATE's qubits.  swapped: the gate's q0 sits on
+// window position 1 (qubit b), so the two bits of every index change places on the way into the window.
+inline void sup_kraus_2q(const cplx* K, int n2, bool swapped, Sup& S) {
+  for (int r = 0; r < 16; ++r) for (int c = 0; c < 16; ++c) S.m[r][c] = 0.0;
+  for (int k = 0; k < n2; ++k) {
+    cplx U[4][4];
+    for (int i = 0; i < 4; ++i) for (int ip = 0; ip < 4; ++ip) {
+      const int gi = swapped ? ((i & 1) << 1) | (i >> 1) : i, gp = swapped ? ((ip & 1) << 1) | (ip >> 1) : ip;
+      U[i][ip] = K[16 * k + 4 * gi + gp];
+    }
+    Sup P;
+    sup_conj(U, P);
+    for (int r = 0; r < 16; ++r) for (int c = 0; c < 16; ++c) S.m[r][c] += P.m[r][c];
+  }
+}
+// The override of a handle: K1 (n1 x 2 x 2) replaces the channel of G_DEPOL1, K2 (n2 x 4 x 4) that of G_DEPOL2; a count
+// of 0 leaves that slot on the depolarising channel.
+struct DmKraus {
+  int n1 = 0, n2 = 0;
+  std::vector<cplx> K1, K2;
+  bool any() const { return n1 > 0 || n2 > 0; }
+};
+// max |sum_k K_k^+ K_k - I| of `count` d x d operators: 0 for a trace preserving set, NaN if an entry is no number
+inline double kraus_tp_defect(const cplx* K, int count, int d) {
+  double worst = 0.0;
+  for (int r = 0; r < d; ++r) for (int c = 0; c < d; ++c) {
+    cplx v = r == c ? -1.0 : 0.0;
+    for (int k = 0; k < count; ++k) for (int m = 0; m < d; ++m) v += std::conj(K[(k * d + m) * d + r]) * K[(k * d + m) * d + c];
+    const double a = std::abs(v);
+    if (a != a) return a;      // (std::max would drop it)
+    worst = std::max(worst, a);
+  }
+  return worst;
+}
+// What the plan depends on beside the gate list.  orient2: a two-qubit Kraus set is installed, so a G_DEPOL2 member
+// carries the window position of the gate's q0 (depolarising noise is symmetric under exchange of its qubits: pos 0).
+// rot2: RXX / RYY / RZZ are window-sized members like a CNOT (vqe_set_dm_rot2).
+struct DmPlanOpts { bool orient2 = false, rot2 = false; };
+
 struct DmBlockHost { int a, b; Sup S; };
 
 // One gate or channel inside a block.  pos: the window position (0: qubit a, 1: qubit b) a rotation or a one-qubit
-// channel acts on; the position of the CONTROL for a CNOT; 0 for the two-qubit channel.  pidx: the rotation's parameter.
+// channel acts on; the position of the CONTROL for a CNOT and of q0 for a two-qubit rotation; for the two-qubit channel
+// 0, or the position of q0 when a two-qubit Kraus set is installed (DmPlanOpts).  pidx: the rotation's parameter.
 struct DmMember { int kind, pos, pidx; };
 struct DmBlockPlan { int a, b; std::vector<DmMember> members; };
 
@@ -80,14 +132,15 @@ struct DmBlockPlan { int a, b; std::vector<DmMember> members; };
 // window without fitting into it closes that block first (blocks are emitted in the order they are closed, which keeps
 // every qubit's own sequence of operations intact).  Bench circuits (63 gates + 63 channels on 12 qubits): 57 blocks
 // with consecutive fusion only, ~40 with this one.
-inline void dm_plan_blocks(int n, const GateRec* g, int G, std::vector<DmBlockPlan>& out) {
+inline void dm_plan_blocks(int n, const GateRec* g, int G, std::vector<DmBlockPlan>& out, DmPlanOpts opt = DmPlanOpts{}) {
   out.clear();
+  const auto is_two = [&](int kind) { return kind == G_CNOT || kind == G_DEPOL2 || (opt.rot2 && gate_is_rot2(kind)); };
   std::vector<DmBlockPlan> open;            // pairwise disjoint windows
   auto owner = [&](int q) { for (size_t k = 0; k < open.size(); ++k) if (open[k].a == q || open[k].b == q) return (int)k; return -1; };
   auto close = [&](int k) { out.push_back(std::move(open[k])); open.erase(open.begin() + k); };
   for (int i = 0; i < G; ++i) {
     const GateRec r = g[i];
-    const bool two = r.kind == G_CNOT || r.kind == G_DEPOL2;
+    const bool two = is_two(r.kind);
     const int qa = r.q0, qb = two ? r.q1 : -1;
     int k = owner(qa);
     const int k2 = two ? owner(qb) : k;
@@ -105,7 +158,7 @@ inline void dm_plan_blocks(int n, const GateRec* g, int G, std::vector<DmBlockPl
         // if that qubit is free; else any free qubit; if every other qubit sits in an open window, the oldest block goes
         int want = -1;
         for (int j = i + 1; j < G && want < 0; ++j) {
-          const bool t2 = g[j].kind == G_CNOT || g[j].kind == G_DEPOL2;
+          const bool t2 = is_two(g[j].kind);
           if (t2 && g[j].q0 == qa) want = g[j].q1;
           else if (t2 && g[j].q1 == qa) want = g[j].q0;
         }
@@ -118,14 +171,15 @@ inline void dm_plan_blocks(int n, const GateRec* g, int G, std::vector<DmBlockPl
     }
     DmBlockPlan& cur = open[k];
     const int pos = r.q0 == cur.a ? 0 : 1;
-    cur.members.push_back(DmMember{r.kind, r.kind == G_DEPOL2 ? 0 : pos, (r.kind >= G_RX && r.kind <= G_RZ) ? r.pidx : -1});
+    cur.members.push_back(DmMember{r.kind, (r.kind == G_DEPOL2 && !opt.orient2) ? 0 : pos, gate_is_rot(r.kind) ? r.pidx : -1});
   }
   while (!open.empty()) close(0);
 }
 
 // Plan + angles + channel strengths -> the superoperators: identity, then the members in list order.  Gate semantics as
-// in vqe_device.h (qulacs: R = exp(+i theta/2 P), CNOT(control, target)).
-inline void dm_fill_blocks(const std::vector<DmBlockPlan>& plan, const double* theta, double p1, double p2, std::vector<DmBlockHost>& out) {
+// in vqe_device.h (qulacs: R = exp(+i theta/2 P), CNOT(control, target)).  kr: the Kraus override, or NULL.
+inline void dm_fill_blocks(const std::vector<DmBlockPlan>& plan, const double* theta, double p1, double p2, std::vector<DmBlockHost>& out,
+                           const DmKraus* kr = nullptr) {
   out.clear();
   out.reserve(plan.size());
   for (const DmBlockPlan& b : plan) {
@@ -149,10 +203,23 @@ inline void dm_fill_blocks(const std::vector<DmBlockPlan>& plan, const double* t
         else { R[0][0] = cplx(c, sn); R[1][1] = cplx(c, -sn); R[0][1] = R[1][0] = 0.0; }
         embed_1q(R, m.pos, U);
         sup_conj(U, Gs);
+      } else if (gate_is_rot2(m.kind)) {      // U = cos(theta/2) I + i sin(theta/2) P (x) P on the window
+        const double c = std::cos(0.5 * theta[m.pidx]), sn = std::sin(0.5 * theta[m.pidx]);
+        cplx R[2][2], Ua[4][4], Ub[4][4], U[4][4];
+        pauli_1q(m.kind - G_RXX + 1, R);
+        embed_1q(R, 0, Ua); embed_1q(R, 1, Ub);
+        for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) {
+          cplx v = 0.0;
+          for (int k = 0; k < 4; ++k) v += Ua[i][k] * Ub[k][j];
+          U[i][j] = (i == j ? cplx(c) : cplx(0.0)) + cplx(0.0, sn) * v;
+        }
+        sup_conj(U, Gs);
       } else if (m.kind == G_DEPOL1) {
-        sup_depol(m.pos == 0 ? 1 : 2, p1, Gs);
+        if (kr && kr->n1) sup_kraus_1q(kr->K1.data(), kr->n1, m.pos, Gs);
+        else sup_depol(m.pos == 0 ? 1 : 2, p1, Gs);
       } else {
-        sup_depol(3, p2, Gs);
+        if (kr && kr->n2) sup_kraus_2q(kr->K2.data(), kr->n2, m.pos == 1, Gs);
+        else sup_depol(3, p2, Gs);
       }
       sup_apply(cur.S, Gs);
     }
@@ -160,10 +227,11 @@ inline void dm_fill_blocks(const std::vector<DmBlockPlan>& plan, const double* t
 }
 
 // Gate list -> superoperator blocks: the plan, filled.
-inline void dm_make_blocks(int n, const GateRec* g, int G, const double* theta, double p1, double p2, std::vector<DmBlockHost>& out) {
+inline void dm_make_blocks(int n, const GateRec* g, int G, const double* theta, double p1, double p2, std::vector<DmBlockHost>& out,
+                           const DmKraus* kr = nullptr, bool rot2 = false) {
   std::vector<DmBlockPlan> plan;
-  dm_plan_blocks(n, g, G, plan);
-  dm_fill_blocks(plan, theta, p1, p2, out);
+  dm_plan_blocks(n, g, G, plan, DmPlanOpts{kr && kr->n2 > 0, rot2});
+  dm_fill_blocks(plan, theta, p1, p2, out, kr);
 }
 
 // ---- the batched path (vqe_dm_batch.h): the plans of a resident batch, flattened for the device -------------------
@@ -171,7 +239,9 @@ inline void dm_make_blocks(int n, const GateRec* g, int G, const double* theta, 
 // blk_win[6 k] = a, [6 k + 1] = b, [6 k + 2 .. 6 k + 5] = the four index bits of the window in rho (a, b, a + n, b + n)
 // ascending; its members mem[3 m] = kind, [3 m + 1] = pos, [3 m + 2] = pidx for m in mem_begin[k] .. mem_begin[k + 1].
 // dep: the three channel superoperators [which][re / im][16][16] (which 0: one-qubit channel on window position 0,
-// 1: on position 1, 2: the two-qubit channel), from sup_depol - they depend on p1 / p2 only.
+// 1: on position 1, 2: the two-qubit channel), from sup_depol - they depend on p1 / p2 only.  With a Kraus override
+// (dm_channel_tables) FOUR slices: 2 = the two-qubit channel with the gate's q0 on window position 0, 3 = with q0 on
+// position 1; a member reads slice 2 + pos, and without a two-qubit Kraus set pos is 0, so slice 3 is never read.
 struct DmBatchTables {
   std::vector<int32_t> blk_begin, blk_circ, blk_win, mem_begin, mem;
   std::vector<double> dep;
@@ -188,14 +258,28 @@ inline void dm_depol_tables(double p1, double p2, std::vector<double>& dep) {
     }
   }
 }
+// the four slices: every slot from its Kraus set where one is installed, else from sup_depol
+inline void dm_channel_tables(double p1, double p2, const DmKraus* kr, std::vector<double>& dep) {
+  dep.assign(4 * 512, 0.0);
+  for (int w = 0; w < 4; ++w) {
+    Sup S;
+    if (w < 2) { if (kr && kr->n1) sup_kraus_1q(kr->K1.data(), kr->n1, w, S); else sup_depol(w + 1, p1, S); }
+    else if (kr && kr->n2) sup_kraus_2q(kr->K2.data(), kr->n2, w == 3, S);
+    else sup_depol(3, p2, S);
+    for (int r = 0; r < 16; ++r) for (int c = 0; c < 16; ++c) {
+      dep[w * 512 + r * 16 + c] = S.m[r][c].real();
+      dep[w * 512 + 256 + r * 16 + c] = S.m[r][c].imag();
+    }
+  }
+}
 inline void dm_flatten_plans(int n, int batch, const GateRec* gates, const int64_t* gate_begin, const int32_t* gate_count,
-                             double p1, double p2, DmBatchTables& T) {
+                             double p1, double p2, DmBatchTables& T, const DmKraus* kr = nullptr, bool rot2 = false) {
   T = DmBatchTables{};
   T.blk_begin.push_back(0);
   T.mem_begin.push_back(0);
   std::vector<DmBlockPlan> plan;
   for (int b = 0; b < batch; ++b) {
-    dm_plan_blocks(n, gates + gate_begin[b], gate_count[b], plan);
+    dm_plan_blocks(n, gates + gate_begin[b], gate_count[b], plan, DmPlanOpts{kr && kr->n2 > 0, rot2});
     for (const DmBlockPlan& k : plan) {
       int hb[4] = {k.a, k.b, k.a + n, k.b + n};
       std::sort(hb, hb + 4);
@@ -207,7 +291,8 @@ inline void dm_flatten_plans(int n, int batch, const GateRec* gates, const int64
     T.blk_begin.push_back((int32_t)T.blk_circ.size());
     T.max_blocks = std::max(T.max_blocks, (int)plan.size());
   }
-  dm_depol_tables(p1, p2, T.dep);
+  if (kr && kr->any()) dm_channel_tables(p1, p2, kr, T.dep);
+  else dm_depol_tables(p1, p2, T.dep);
 }
 
 // ---- the adjoint gradient of the batched path (vqe_dm_grad.h) ------------------------------------------------------

@@ -130,6 +130,10 @@ struct vqe_handle {
   DmPlanSlot dmb_full, dmb_pre;
   // adjoint gradient of that path (vqe_set_dm_grad, vqe_dm_grad.h): opt-in; the partial sums of M of a chunk's level
   bool dm_grad = false;
+  // Kraus sets in the two channel slots (vqe_set_noise_kraus) and RXX / RYY / RZZ as members (vqe_set_dm_rot2), DESIGN
+  // 4.16: both are part of what a plan is made for, so setting either bumps `gen`
+  DmKraus kraus;
+  bool dm_rot2 = false;
   DevBuf<double> dmg_part;
   DevBuf<int32_t> dmg_active;
   // the lock-step driver of the device optimisers (lockstep_run): results of the circuits that stopped, the count of
@@ -746,7 +750,7 @@ int dm_prepare_ham(vqe_t* h) {
 int dm_energy_one(vqe_t* h, const GateRec* g, int G, const double* theta, double* e_host) {
   const int n = h->n;
   std::vector<DmBlockHost> blocks;
-  dm_make_blocks(n, g, G, theta, h->noise.p1, h->noise.p2, blocks);
+  dm_make_blocks(n, g, G, theta, h->noise.p1, h->noise.p2, blocks, h->kraus.any() ? &h->kraus : nullptr, h->dm_rot2);
   std::vector<double> S(blocks.size() * 512);
   for (size_t k = 0; k < blocks.size(); ++k)
     for (int r = 0; r < 16; ++r) for (int c = 0; c < 16; ++c) {
@@ -795,7 +799,8 @@ int dm_batch_plan(vqe_t* h, DmPlanSlot& P, const std::vector<GateRec>& gates, co
                   const std::vector<int32_t>& gcnt) {
   if (P.gen == h->gen) return VQE_OK;
   DmBatchTables T;
-  dm_flatten_plans(h->n, h->batch, gates.data(), gbeg.data(), gcnt.data(), h->noise.p1, h->noise.p2, T);
+  dm_flatten_plans(h->n, h->batch, gates.data(), gbeg.data(), gcnt.data(), h->noise.p1, h->noise.p2, T,
+                   h->kraus.any() ? &h->kraus : nullptr, h->dm_rot2);
   VQE_TRY(upload(h, P.blk_begin, T.blk_begin));
   VQE_TRY(upload(h, P.blk_circ, T.blk_circ));
   VQE_TRY(upload(h, P.blk_win, T.blk_win));
@@ -904,8 +909,9 @@ int dm_run_batched(vqe_t* h, Run mode, BatchArgs A) {
 // What the exact channel mode cannot serve (checked by run(), before anything of the handle changes)
 int dm_refusal(vqe_t* h) {
   if (h->n < 2 || h->n > 13) return fail(h, VQE_EINVAL, "the exact channel mode (density matrix) serves 2 <= n_qubits <= 13");
-  // the superoperator blocks (dm_host.h) are built from CNOT, RX, RY, RZ and the two channels only: refused before anything is launched
-  for (int b = 0; b < h->batch; ++b)
+  // without vqe_set_dm_rot2 the superoperator blocks (dm_host.h) are built from CNOT, RX, RY, RZ and the two channels only:
+  // refused before anything is launched
+  for (int b = 0; !h->dm_rot2 && b < h->batch; ++b)
     for (int64_t i = h->h_gate_begin[b]; i < h->h_gate_begin[b] + h->h_gate_count[b]; ++i)
       if (gate_is_rot2(h->h_gates[i].kind))
         return fail(h, VQE_EINVAL, "the exact channel mode does not take RXX / RYY / RZZ gates (use Pauli-trajectory noise, vqe_set_noise_mode 0)");
@@ -970,7 +976,7 @@ bool dm_grad_path(const vqe_t* h) { return h->noise_mode == 1 && h->dm_grad && h
 // dm_refusal's gate test on the single circuit of vqe_set_circuit, for the calls that would load it as the batch:
 // refused before the resident batch changes
 int dm_circuit_refusal(vqe_t* h) {
-  if (!dm_grad_path(h)) return VQE_OK;
+  if (!dm_grad_path(h) || h->dm_rot2) return VQE_OK;
   for (const GateRec& g : h->circ)
     if (gate_is_rot2(g.kind))
       return fail(h, VQE_EINVAL, "the exact channel mode does not take RXX / RYY / RZZ gates (use Pauli-trajectory noise, vqe_set_noise_mode 0)");
@@ -1163,6 +1169,16 @@ int dm_run_lbfgs(vqe_t* h, bool env_step, const vqe_lbfgs_opts_t& o) {
   return VQE_OK;
 }
 
+// A Kraus override (vqe_set_noise_kraus) has no trajectory form: with one installed only the exact channel mode runs,
+// and no state vector is handed out in any mode.  Checked before anything is loaded or launched.
+int kraus_refusal(vqe_t* h, bool state_call) {
+  if (!h->kraus.any()) return VQE_OK;
+  if (state_call) return fail(h, VQE_ESTATE, "a Kraus channel (vqe_set_noise_kraus) has no state vector: vqe_get_state* is refused while it is installed");
+  if (h->noise_mode != 1)
+    return fail(h, VQE_ESTATE, "a Kraus channel (vqe_set_noise_kraus) has no Pauli-trajectory form: use the exact channel mode (vqe_set_noise_mode 1)");
+  return VQE_OK;
+}
+
 // The evaluation trace of an optimiser run (vqe_batch_set_trace): [batch][maxfun][1 + max_params] doubles, zeroed
 int arm_trace(vqe_t* h, BatchArgs& A, int maxfun) {
   const size_t stride = (size_t)1 + (size_t)h->max_params, words = (size_t)h->batch * (size_t)maxfun * stride;
@@ -1174,6 +1190,7 @@ int arm_trace(vqe_t* h, BatchArgs& A, int maxfun) {
 }
 
 int run(vqe_t* h, Run mode, double rhobeg, double rhoend, int maxfun) {
+  VQE_TRY(kraus_refusal(h, mode == Run::State));
   HIP_TRY(h, hipSetDevice(h->dev));
   BatchArgs A = make_args(h);
   A.rhobeg = rhobeg; A.rhoend = rhoend; A.maxfun = maxfun;
@@ -1237,6 +1254,7 @@ int grad_state_refusal(vqe_t* h) {
     if (h->amp_world > 1) return fail(h, VQE_ESTATE, "the exact channel mode has no amplitude sharding");
     return VQE_OK;
   }
+  VQE_TRY(kraus_refusal(h, false));
   if (h->noise.p1 > 0.0 || h->noise.p2 > 0.0)
     return fail(h, VQE_ESTATE, "energy gradients of Pauli-noise trajectories are refused (set p1 = p2 = 0)");
   if (h->noise_mode == 1) return fail(h, VQE_ESTATE, "energy gradients are not available in the exact channel noise mode");
@@ -1519,6 +1537,7 @@ int vqe_set_init_state_dev(vqe_t* h, const void* dev_amps) {
 int vqe_get_state_dev(vqe_t* h, const double* theta, void* dev_amps) {
   if (!h) return VQE_EINVAL;
   if (!dev_amps || (h->circ_params > 0 && !theta)) return fail(h, VQE_EINVAL, "bad arguments");
+  VQE_TRY(kraus_refusal(h, true));
   HIP_TRY(h, hipSetDevice(h->dev));
   int rc = load_single(h, 1, theta);
   if (rc) return rc;
@@ -1771,6 +1790,37 @@ int vqe_set_dm_grad(vqe_t* h, int enable) {
   return VQE_OK;
 }
 
+int vqe_set_noise_kraus(vqe_t* h, int n1, const double* K1, int n2, const double* K2) {
+  if (!h) return VQE_EINVAL;
+  if (n1 < 0 || n1 > 16 || n2 < 0 || n2 > 64) return fail(h, VQE_EINVAL, "Kraus operators per slot: 0 <= n1 <= 16, 0 <= n2 <= 64");
+  if ((n1 > 0 && !K1) || (n2 > 0 && !K2)) return fail(h, VQE_EINVAL, "Kraus array is NULL");
+  DmKraus k;
+  k.n1 = n1;
+  k.n2 = n2;
+  for (int i = 0; i < n1 * 4; ++i) k.K1.push_back(cplx(K1[2 * i], K1[2 * i + 1]));
+  for (int i = 0; i < n2 * 16; ++i) k.K2.push_back(cplx(K2[2 * i], K2[2 * i + 1]));
+  // (a NaN fails both comparisons)
+  if ((n1 > 0 && !(kraus_tp_defect(k.K1.data(), n1, 2) <= 1e-12)) || (n2 > 0 && !(kraus_tp_defect(k.K2.data(), n2, 4) <= 1e-12)))
+    return fail(h, VQE_EINVAL, "Kraus set is not trace preserving: max |sum K^+ K - I| > 1e-12");
+  h->kraus = std::move(k);
+  ++h->gen;      // the plans and channel tables of the resident batch are made again
+  return VQE_OK;
+}
+
+int vqe_noise_kraus_info(vqe_t* h, int32_t out[2]) {
+  if (!h || !out) return VQE_EINVAL;
+  out[0] = h->kraus.n1;
+  out[1] = h->kraus.n2;
+  return VQE_OK;
+}
+
+int vqe_set_dm_rot2(vqe_t* h, int enable) {
+  if (!h) return VQE_EINVAL;
+  if (h->dm_rot2 != (enable != 0)) ++h->gen;      // (takes effect in noise mode 1: a two-qubit rotation is then a member of the plans)
+  h->dm_rot2 = enable != 0;
+  return VQE_OK;
+}
+
 int vqe_dm_batch_info(vqe_t* h, int64_t out[4]) {
   if (!h || !out) return VQE_EINVAL;
   std::copy(h->dm_info, h->dm_info + 4, out);
@@ -1835,6 +1885,7 @@ int vqe_set_circuit(vqe_t* h, int n_gates, const int32_t* kind, const int32_t* q
 int vqe_energy_batch(vqe_t* h, int batch, const double* theta, double* energy) {
   if (!h) return VQE_EINVAL;
   if (batch < 1 || !energy || (h->circ_params > 0 && !theta)) return fail(h, VQE_EINVAL, "bad arguments");
+  VQE_TRY(kraus_refusal(h, false));
   HIP_TRY(h, hipSetDevice(h->dev));
   int rc = load_single(h, batch, theta);
   if (rc) return rc;
@@ -1850,6 +1901,7 @@ int vqe_energy(vqe_t* h, const double* theta, double* energy) { return vqe_energ
 int vqe_get_state(vqe_t* h, const double* theta, double* amps) {
   if (!h) return VQE_EINVAL;
   if (!amps || (h->circ_params > 0 && !theta)) return fail(h, VQE_EINVAL, "bad arguments");
+  VQE_TRY(kraus_refusal(h, true));
   HIP_TRY(h, hipSetDevice(h->dev));
   int rc = load_single(h, 1, theta);
   if (rc) return rc;
@@ -1866,6 +1918,7 @@ int vqe_minimize_cobyla(vqe_t* h, const double* x0, double rhobeg, double rhoend
   if (!h) return VQE_EINVAL;
   if (maxfun < 1 || !(rhobeg > 0) || !(rhoend > 0)) return fail(h, VQE_EINVAL, "bad COBYLA arguments");
   if (h->circ_params > 0 && (!x0 || !x)) return fail(h, VQE_EINVAL, "x0/x is NULL");
+  VQE_TRY(kraus_refusal(h, false));
   HIP_TRY(h, hipSetDevice(h->dev));
   int rc = load_single(h, 1, x0);
   if (rc) return rc;

@@ -48,7 +48,7 @@ __global__ void __launch_bounds__(256) k_dm_build(DmBatchDev T, const double* __
   for (int m = T.mem_begin[k]; m < T.mem_begin[k + 1]; ++m) {
     const int kind = T.mem[3 * m], pos = T.mem[3 * m + 1], pidx = T.mem[3 * m + 2];
     double cs = 1.0, sn = 0.0;
-    if (kind >= G_RX && kind <= G_RZ) sincos(0.5 * th[pidx], &sn, &cs);
+    if (gate_is_rot(kind)) sincos(0.5 * th[pidx], &sn, &cs);
     double vr, vi;
     dm_build_entry(kind, pos, cs, sn, T.dep, buf[cur][0], buf[cur][1], r, c, vr, vi);
     buf[cur ^ 1][0][t] = vr;

@@ -213,7 +213,7 @@ __global__ void __launch_bounds__(256) k_dmg_contract(DmBatchDev T, const int32_
   __shared__ double buf[2][2][256];
   __shared__ double red[4];
   const int which = blockIdx.x, wkind = T.mem[3 * which];
-  if (wkind < G_RX || wkind > G_RZ) return;
+  if (!gate_is_rot(wkind)) return;
   const int k = mem_blk[which], b = T.blk_circ[k];
   if (active && !active[b]) return;
   const int t = threadIdx.x, r = t >> 4, c = t & 15;
@@ -225,7 +225,7 @@ __global__ void __launch_bounds__(256) k_dmg_contract(DmBatchDev T, const int32_
   for (int m = T.mem_begin[k]; m < T.mem_begin[k + 1]; ++m) {
     const int kind = T.mem[3 * m], pos = T.mem[3 * m + 1], pidx = T.mem[3 * m + 2];
     double cs = 1.0, sn = 0.0;
-    if (kind >= G_RX && kind <= G_RZ) sincos(0.5 * th[pidx], &sn, &cs);
+    if (gate_is_rot(kind)) sincos(0.5 * th[pidx], &sn, &cs);
     double vr, vi;
     dm_build_entry(kind, pos, cs, sn, T.dep, buf[cur][0], buf[cur][1], r, c, vr, vi);
     buf[cur ^ 1][0][t] = vr;
@@ -262,7 +262,7 @@ __global__ void __launch_bounds__(64) k_dmg_scatter(DmBatchDev T, const int64_t*
   if (threadIdx.x != 0) return;
   for (int m = T.mem_begin[T.blk_begin[b]]; m < T.mem_begin[T.blk_begin[b + 1]]; ++m) {
     const int kind = T.mem[3 * m];
-    if (kind >= G_RX && kind <= G_RZ) g[T.mem[3 * m + 2]] += val[m];
+    if (gate_is_rot(kind)) g[T.mem[3 * m + 2]] += val[m];
   }
 }
 

@@ -253,6 +253,36 @@ class VQEEngine:
         mode 1.  A resident circuit then costs levels + 2 density matrices (dm_batch_info reports the resident count)."""
         self._chk(self._lib.vqe_set_dm_grad(self._h, 1 if enable else 0))
 
+    def set_noise_kraus(self, K1=None, K2=None):
+        """Exact channel mode: Kraus sets in the two noise slots (see ``channels``).  ``K1``: (k, 2, 2) complex, applied
+        at GATE_DEPOL1 gates in the depolarising channel's place; ``K2``: (k, 4, 4) complex for GATE_DEPOL2, basis index
+        = bit(q0) + 2 bit(q1) of the gate's two qubits.  ``None`` (or an empty set) leaves that slot on the depolarising
+        channel of set_noise; both ``None`` removes the override.  While one is installed only mode 1 runs are served:
+        mode 0 runs and get_state* raise."""
+        def pack(K, d, name):
+            if K is None:
+                return 0, None
+            a = np.ascontiguousarray(K, dtype=np.complex128)
+            if a.size == 0:
+                return 0, None
+            if a.ndim != 3 or a.shape[1:] != (d, d):
+                raise ValueError(f"{name} must have shape (k, {d}, {d})")
+            return int(a.shape[0]), a.view(np.float64)
+        n1, a1 = pack(K1, 2, "K1")
+        n2, a2 = pack(K2, 4, "K2")
+        self._chk(self._lib.vqe_set_noise_kraus(self._h, n1, _p(a1, c_f64p), n2, _p(a2, c_f64p)))
+
+    def noise_kraus_info(self):
+        """Kraus operators installed in the one- / two-qubit slot (0: that slot runs the depolarising channel)."""
+        out = (C.c_int32 * 2)()
+        self._chk(self._lib.vqe_noise_kraus_info(self._h, out))
+        return {"n1": out[0], "n2": out[1]}
+
+    def set_dm_rot2(self, enable: bool = True):
+        """Exact channel mode: take GATE_RXX / RYY / RZZ as members of the superoperator blocks (serial and batched path,
+        gradient and L-BFGS included).  Off by default: circuits with those gates are refused in mode 1."""
+        self._chk(self._lib.vqe_set_dm_rot2(self._h, 1 if enable else 0))
+
     def dm_batch_info(self):
         """The last batched exact-channel run (all 0 after a serial one)."""
         out = (C.c_int64 * 4)()

@@ -84,10 +84,15 @@ class VecCircuitEnv:
     ``noise_channel``: how the noisy environment classes evaluate their depolarising channels - "trajectory" (default:
     one Pauli trajectory per evaluation, as the reference's qulacs circuits do) or "exact" (the channel those draws
     sample from: the engine's exact channel mode on the batched lock-step path, set_noise_mode(1) + set_dm_batched(-1);
-    deterministic energies, 2 <= n <= 13)."""
+    deterministic energies, 2 <= n <= 13).
+    ``noise_kraus``: ``(K1, K2)``, Kraus sets (``channels``) for the channel behind every rotation and behind every CNOT
+    in the depolarising channels' place, either of them ``None`` for the depolarising channel; needs
+    noise_channel = "exact" (a general channel has no Pauli-trajectory form).  Set on the engine once, for the life of
+    the batch."""
 
     def __init__(self, env_cls, conf, device, num_envs: int, seed: int = 0, native: bool | None = None,
-                 device_optimizer: str = "cobyla", lbfgs_opts: dict | None = None, noise_channel: str = "trajectory"):
+                 device_optimizer: str = "cobyla", lbfgs_opts: dict | None = None, noise_channel: str = "trajectory",
+                 noise_kraus=None):
         if not issubclass(env_cls, CircuitEnvBase):
             raise TypeError("env_cls must be one of the CircuitEnv classes of this package")
         if device_optimizer not in ("cobyla", "lbfgs"):
@@ -98,6 +103,11 @@ class VecCircuitEnv:
             raise ValueError('noise_channel must be "trajectory" or "exact"')
         if noise_channel == "exact" and not getattr(env_cls, "NOISY", False):
             raise ValueError('noise_channel = "exact" is for the noisy environment classes (Pauli noise behind every gate)')
+        if noise_kraus is not None:
+            if noise_channel != "exact":
+                raise ValueError('noise_kraus needs noise_channel = "exact"')
+            if len(noise_kraus) != 2:
+                raise ValueError("noise_kraus is a pair (K1, K2)")
         first = env_cls(conf, device, seed=seed)
         if first.optimizer_kind not in (None, "device_cobyla"):
             raise NotImplementedError(f"VecCircuitEnv runs the device COBYLA of batch_run_env_step only; optim_alg = "
@@ -117,6 +127,8 @@ class VecCircuitEnv:
             self.engine.set_dm_batched(-1)
             if device_optimizer == "lbfgs":
                 self.engine.set_dm_grad(True)            # the adjoint gradient of tr(rho H) on the batched path
+            if noise_kraus is not None:                  # (after the constructor's set_noise and its get_state)
+                self.engine.set_noise_kraus(noise_kraus[0], noise_kraus[1])
         if device_optimizer == "lbfgs" and first.num_qubits >= 14:
             self.engine.set_stream_lbfgs(True)           # the streaming path runs the device L-BFGS on request only
         self._proto = first

@@ -224,6 +224,37 @@ int vqe_set_dm_grad(vqe_t* h, int enable);
 int vqe_set_noise_kraus(vqe_t* h, int n1, const double* K1, int n2, const double* K2);
 /* out[0], out[1]: Kraus operators installed in the one- / two-qubit slot, 0 = none */
 int vqe_noise_kraus_info(vqe_t* h, int32_t out[2]);
+/* Mode 0 under a Kraus override (vqe_set_noise_kraus): evaluate an energy as the mean of n_traj quantum-jump
+ * trajectories.  0 (default): those runs are refused with VQE_ESTATE as before.  1 .. 4096.  Accepted on any handle;
+ * takes effect in mode 0 while an override is installed, 1 <= n <= 13, unsharded handles.  Touches neither seed,
+ * counter, p1/p2, the override nor the resident batch's results.  VQE_EINVAL, handle unchanged, for a count outside
+ * [0, 4096].
+ * A trajectory (csrc/vqe_qjump.h).  The draw of (stream b, evaluation e, trajectory t, noise gate at position g of the
+ * executed gate list) is u = noise_uniform_k(noise_key(seed, b, e), ((uint64_t)(t + 1) << 44) | g), the hash of the Pauli
+ * draws; g is numbered as there (gates left out by an env-step's pre-action rule do not count), one draw per noise
+ * gate.  With rho_red the reduced density matrix of the gate's one or two qubits (index = bit(q0) + 2 bit(q1)) and
+ * p_k = tr(K_k^+ K_k rho_red), k is the smallest index with u < p_0 + ... + p_k (accumulated in k order in double; if
+ * rounding leaves none, the last k with p_k > 0), and psi <- K_k psi / sqrt(p_k).  A slot without an override (n1 == 0 or
+ * n2 == 0) runs the depolarising Kraus set of its p1 / p2 - sqrt(1 - p) 1, then sqrt(p / 3) X, Y, Z resp.
+ * sqrt(p / 15) P_b (x) P_a at k = a + 4 b - and is the identity, skipped, at probability 0.
+ * The energy of an evaluation is the mean over t = 0 .. n_traj - 1 of <psi_t|H|psi_t>, summed in t order, plus
+ * shot_sigma * noise_gauss(seed, b, e) once per evaluation.  The same seed, counter, batch position and n_traj give the
+ * same bits, whatever the batch around the circuit.  The counter follows the mode 0 rules of vqe_set_noise: an energy
+ * run or a state draws at the counter and adds 1, an optimiser run with maxfun draws its k-th evaluation at counter + k,
+ * an env-step its final full-circuit evaluation at counter + maxfun + 1, either then adds maxfun + 1; a refused call
+ * leaves it alone.
+ * Served: vqe_energy, vqe_energy_batch, vqe_batch_run_energy, vqe_minimize_cobyla, vqe_batch_run_minimize,
+ * vqe_batch_run_env_step (COBYLA on the device, all circuits in lock-step), and vqe_get_state / vqe_get_state_dev in
+ * either noise mode: the normalised state of trajectory 0 at the counter.  Still refused with VQE_ESTATE before anything
+ * is loaded or launched: gradient and L-BFGS calls, vqe_batch_run_reduction, term- or amplitude-sharded handles,
+ * n >= 14. */
+int vqe_set_kraus_traj(vqe_t* h, int n_traj);
+/* out[0] n_traj, [1] workgroups of the last trajectory launch, [2] jumps (selections k != 0) of the last evaluation,
+ * summed over circuits and trajectories, [3] lock-step evaluations of the last run (1 for an energy run) */
+int vqe_kraus_traj_info(vqe_t* h, int64_t out[4]);
+/* per-trajectory energies e[b * n_traj + t] of the last energy run, or of the final full-circuit evaluation of the last
+ * env-step; VQE_ESTATE after anything else (a new batch, any other run, a vqe_set_kraus_traj that changes n_traj) */
+int vqe_batch_fetch_traj(vqe_t* h, double* e /* batch x n_traj */);
 /* 1: the exact channel mode takes VQE_GATE_RXX / RYY / RZZ - a two-qubit rotation is a member of a superoperator block
  * like a CNOT - on the serial and the batched path, gradient and L-BFGS included.  0 (default): refused with VQE_EINVAL
  * as before.  Accepted on any handle; it takes effect in mode 1. */

@@ -11,6 +11,7 @@
 #include "vqe_lbfgs.h"
 #include "vqe_stream_lbfgs.h"
 #include "vqe_lanczos.h"
+#include "vqe_qjump.h"
 #include "ham_layout.h"
 #include "dm_host.h"
 #include "env_step_host.h"
@@ -164,6 +165,18 @@ struct vqe_handle {
   // device L-BFGS of the streaming path (vqe_stream_lbfgs.h): opt-in (vqe_set_stream_lbfgs); per-stream records
   bool stream_lbfgs = false;
   DevBufExact<StreamLbfgsRec> lb_rec;
+  // quantum-jump trajectories of a Kraus override in mode 0 (vqe_set_kraus_traj, vqe_qjump.h): the count (0: refused as
+  // before), the channel tables of the two slots (made again when the override or p1 / p2 change: qj_ver), per-trajectory
+  // energies and jump counts of the last evaluation, per-circuit jump sums
+  int kraus_traj = 0;
+  uint64_t qj_ver = 0, qj_tab_ver = ~0ull;
+  DevBuf<double> qj_K1, qj_W1, qj_K2, qj_W2, qj_e;
+  DevBuf<int32_t> qj_jumps;
+  DevBuf<long long> qj_jsum;
+  int qj_n1 = 0, qj_n2 = 0;
+  int64_t qj_info[4] = {0, 0, 0, 0};
+  int qj_traj_batch = 0;       // circuits whose per-trajectory energies vqe_batch_fetch_traj hands out (0: none)
+  int qj_jsum_batch = 0;       // circuits of the last evaluation (its jump sums wait in qj_jsum)
   // device Lanczos (vqe_lanczos.h): the solver's own copy of the full operator (logical frame) and its vectors
   LzWork lz;
 };
@@ -448,6 +461,7 @@ int load_batch(vqe_t* h, int batch, const std::vector<GateRec>& gates,
   h->h_theta.assign(theta0, theta0 + total_params);
   h->has_new_gate = false;
   h->lb_batch = 0;
+  h->qj_traj_batch = 0;
   ++h->gen;
   return VQE_OK;
 }
@@ -1171,8 +1185,17 @@ int dm_run_lbfgs(vqe_t* h, bool env_step, const vqe_lbfgs_opts_t& o) {
 
 // A Kraus override (vqe_set_noise_kraus) has no trajectory form: with one installed only the exact channel mode runs,
 // and no state vector is handed out in any mode.  Checked before anything is loaded or launched.
-int kraus_refusal(vqe_t* h, bool state_call) {
+// traj_ok: the call is one that quantum-jump trajectories serve (vqe_set_kraus_traj, vqe_qjump.h) - energies, COBYLA runs
+// and env-steps in mode 0, states in either mode; then only what that path cannot hold is refused.
+int kraus_refusal(vqe_t* h, bool state_call, bool traj_ok = false) {
   if (!h->kraus.any()) return VQE_OK;
+  if (traj_ok && h->kraus_traj >= 1 && (state_call || h->noise_mode != 1)) {
+    if (h->shard_world > 1 || h->amp_world > 1)
+      return fail(h, VQE_ESTATE, "quantum-jump trajectories of a Kraus channel (vqe_set_kraus_traj) take no term- or amplitude-sharded handle");
+    if (!h->lds_path)
+      return fail(h, VQE_ESTATE, "quantum-jump trajectories of a Kraus channel (vqe_set_kraus_traj) run for n_qubits <= 13 (LDS-resident path) only");
+    return VQE_OK;
+  }
   if (state_call) return fail(h, VQE_ESTATE, "a Kraus channel (vqe_set_noise_kraus) has no state vector: vqe_get_state* is refused while it is installed");
   if (h->noise_mode != 1)
     return fail(h, VQE_ESTATE, "a Kraus channel (vqe_set_noise_kraus) has no Pauli-trajectory form: use the exact channel mode (vqe_set_noise_mode 1)");
@@ -1189,8 +1212,100 @@ int arm_trace(vqe_t* h, BatchArgs& A, int maxfun) {
   return VQE_OK;
 }
 
+// ---- quantum-jump trajectories of a Kraus override in mode 0 (vqe_set_kraus_traj; kernels: vqe_qjump.h) ----
+
+int build_grad_tables(vqe_t* h);      // (below: the GradHam tables of the adjoint kernels, whose energy step this path runs)
+
+// The run is served by trajectories: the switch, an override, and mode 0 (a state: either mode)
+bool qj_serves(const vqe_t* h, Run mode) {
+  return h->kraus_traj >= 1 && h->kraus.any() && mode != Run::Reduce && (mode == Run::State || h->noise_mode != 1);
+}
+
+// The channel tables of the two slots: the override, or the depolarising Kraus set of p1 / p2 (none at probability 0)
+int qj_prepare(vqe_t* h) {
+  if (h->qj_tab_ver == h->qj_ver) return VQE_OK;
+  std::vector<cplx> dep;
+  std::vector<double> k1, w1, k2, w2;
+  h->qj_n1 = h->kraus.n1;
+  h->qj_n2 = h->kraus.n2;
+  if (h->kraus.n1 > 0) {
+    qj_build_tables(h->kraus.K1.data(), h->kraus.n1, 2, k1, w1);
+  } else if (h->noise.p1 > 0.0) {
+    qj_depol_kraus(h->noise.p1, 2, dep);
+    qj_build_tables(dep.data(), h->qj_n1 = 4, 2, k1, w1);
+  }
+  if (h->kraus.n2 > 0) {
+    qj_build_tables(h->kraus.K2.data(), h->kraus.n2, 4, k2, w2);
+  } else if (h->noise.p2 > 0.0) {
+    qj_depol_kraus(h->noise.p2, 4, dep);
+    qj_build_tables(dep.data(), h->qj_n2 = 16, 4, k2, w2);
+  }
+  VQE_TRY(upload(h, h->qj_K1, k1));
+  VQE_TRY(upload(h, h->qj_W1, w1));
+  VQE_TRY(upload(h, h->qj_K2, k2));
+  VQE_TRY(upload(h, h->qj_W2, w2));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));  // host vectors go out of scope
+  h->qj_tab_ver = h->qj_ver;
+  return VQE_OK;
+}
+
+// One evaluation: T trajectories of every active circuit of the batch A describes at A.theta with evaluation id eval_id,
+// their mean into A.fout.  Queued on the handle's stream; nothing is copied back.  state_out: the state of work item 0.
+int qj_eval(vqe_t* h, const BatchArgs& A, int T, uint64_t eval_id, const int32_t* active, int32_t* nfev, double2* state_out) {
+  const int B = A.batch;
+  HIP_TRY(h, h->qj_e.reserve((size_t)B * T));
+  HIP_TRY(h, h->qj_jumps.reserve((size_t)B * T));
+  HIP_TRY(h, h->qj_jsum.reserve(B));
+  const QjDev Q{h->qj_n1, h->qj_n2, h->qj_K1.p, h->qj_W1.p, h->qj_K2.p, h->qj_W2.p, T, eval_id, active,
+                h->qj_e.p, h->qj_jumps.p, state_out};
+  int grid = 0, wg_per_cu = 1;
+  hipError_t herr = hipSuccess;
+  const int rc = qj_launch(A, h->gham, Q, nfev, h->qj_jsum.p, h->lds_per_cu, h->cu_count, h->stream, &grid, &wg_per_cu, &herr);
+  if (rc == QJ_ETOOLARGE) return fail(h, VQE_EINVAL, "circuit too large for the trajectory kernel (gates + parameters)");
+  if (rc == QJ_ESIZE) return fail(h, VQE_EINVAL, "quantum-jump trajectories run for n_qubits <= 13 (LDS-resident path) only");
+  HIP_TRY(h, herr);
+  h->last_wg_per_cu = std::min(8, wg_per_cu);
+  h->qj_info[1] = grid;
+  h->qj_jsum_batch = B;
+  return VQE_OK;
+}
+
+// Run::Energy / State / Minimize / EnvStep on trajectories, in the shape of dm_run_batched: the optimiser of every circuit
+// lives on the device (k_s_cobyla through lockstep_cobyla), an evaluation is qj_eval.  The k-th evaluation of an
+// optimiser run draws at counter + k, the final full-circuit evaluation of an env-step at counter + maxfun + 1.
+int qj_run(vqe_t* h, Run mode, BatchArgs A) {
+  VQE_TRY(build_grad_tables(h));
+  VQE_TRY(qj_prepare(h));
+  const int T = h->kraus_traj;
+  const uint64_t base = h->noise.eval_base;
+  h->qj_traj_batch = 0;
+  h->qj_info[0] = T;
+  h->qj_info[3] = 1;
+  HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
+  if (mode == Run::Energy) {
+    VQE_TRY(qj_eval(h, A, T, base, nullptr, A.nfev, nullptr));
+    h->qj_traj_batch = h->batch;
+  } else if (mode == Run::State) {
+    A.batch = 1;                                  // trajectory 0 of the one circuit
+    VQE_TRY(qj_eval(h, A, 1, base, nullptr, nullptr, A.state_out));
+  } else {
+    std::vector<int32_t> nfev;
+    VQE_TRY(minimize_or_env_step(h, mode == Run::EnvStep, A, nfev,
+        [&](BatchArgs& a, const PreActionBatch*, std::vector<double>& x, std::vector<double>& f, std::vector<int32_t>& nf) {
+          return lockstep_cobyla(h, a, x, f, nf, [h, T, base](const BatchArgs& t, uint64_t it, const int32_t* active) {
+            return qj_eval(h, t, T, base + it, active, nullptr, nullptr);
+          });
+        },
+        [&](const BatchArgs& a) { return qj_eval(h, a, T, base + (uint64_t)a.maxfun + 1, nullptr, nullptr, nullptr); }));
+    h->qj_info[3] = *std::max_element(nfev.begin(), nfev.end()) + (mode == Run::EnvStep ? 1 : 0);
+    if (mode == Run::EnvStep) h->qj_traj_batch = h->batch;
+  }
+  HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
+  return VQE_OK;
+}
+
 int run(vqe_t* h, Run mode, double rhobeg, double rhoend, int maxfun) {
-  VQE_TRY(kraus_refusal(h, mode == Run::State));
+  VQE_TRY(kraus_refusal(h, mode == Run::State, mode != Run::Reduce));
   HIP_TRY(h, hipSetDevice(h->dev));
   BatchArgs A = make_args(h);
   A.rhobeg = rhobeg; A.rhoend = rhoend; A.maxfun = maxfun;
@@ -1203,7 +1318,11 @@ int run(vqe_t* h, Run mode, double rhobeg, double rhoend, int maxfun) {
   // Everything else a run can be refused for, before the trace, the L-BFGS info and the timing of the previous run are
   // given up: a refused run leaves the handle and what can be fetched from it as they were.
   const bool exact = h->noise_mode == 1 && (mode == Run::Energy || optimise);
-  if (exact) {
+  const bool traj = qj_serves(h, mode);
+  if (traj) {
+    if (qj_lds_bytes(h->n, A.max_ops, A.max_params) > (size_t)h->lds_per_cu)
+      return fail(h, VQE_EINVAL, "circuit too large for the trajectory kernel (gates + parameters)");
+  } else if (exact) {
     VQE_TRY(dm_refusal(h));
   } else if (h->lds_path) {
     const size_t lds = lds_bytes(h->n, A.max_ops, A.max_params, A.ham.n_groups, A.max_pair, optimise && wide_launch(h->n, A.max_params));
@@ -1213,11 +1332,12 @@ int run(vqe_t* h, Run mode, double rhobeg, double rhoend, int maxfun) {
       return fail(h, VQE_ESTATE, "the states of the last run were undone by its gradient sweep: run the energy first");
     if (h->sw.states.cap < ((size_t)h->batch << h->n)) return fail(h, VQE_ESTATE, "no states: run the energy first");
   }
-  if (h->trace_on && optimise && h->lds_path) VQE_TRY(arm_trace(h, A, maxfun));
+  if (h->trace_on && optimise && h->lds_path && !traj) VQE_TRY(arm_trace(h, A, maxfun));
   h->last_run_dm = false;
   h->lb_batch = 0;             // fout / nfev are about to be another run's: the L-BFGS info of an earlier one is stale
-  if (exact) return dm_run(h, mode, A);
-  VQE_TRY(h->lds_path ? dispatch_lds(h, mode, A) : stream_run(h, mode, A));
+  h->qj_traj_batch = 0;        // ... and so are the per-trajectory energies of an earlier trajectory run
+  if (exact && !traj) return dm_run(h, mode, A);
+  VQE_TRY(traj ? qj_run(h, mode, A) : h->lds_path ? dispatch_lds(h, mode, A) : stream_run(h, mode, A));
   // every evaluation of a stochastic run consumes fresh trajectory numbers
   if (mode != Run::Reduce) h->noise.eval_base += (optimise ? (uint64_t)maxfun + 1 : 1);
   return VQE_OK;
@@ -1326,6 +1446,7 @@ int run_grad(vqe_t* h) {
   HIP_TRY(h, h->d_grad.reserve((size_t)h->total_params + 1));
   const BatchArgs A = make_args(h);
   h->last_run_dm = false;
+  h->qj_traj_batch = 0;
   if (!h->lds_path) return stream_grad(h, A);
   return dispatch_n(h, "energy gradients are computed for n_qubits <= 13 (LDS-resident path) only",
                     [&](auto n) -> int { return launch_grad<decltype(n)::value>(h, A); }, LdsSizes{});
@@ -1537,7 +1658,7 @@ int vqe_set_init_state_dev(vqe_t* h, const void* dev_amps) {
 int vqe_get_state_dev(vqe_t* h, const double* theta, void* dev_amps) {
   if (!h) return VQE_EINVAL;
   if (!dev_amps || (h->circ_params > 0 && !theta)) return fail(h, VQE_EINVAL, "bad arguments");
-  VQE_TRY(kraus_refusal(h, true));
+  VQE_TRY(kraus_refusal(h, true, true));
   HIP_TRY(h, hipSetDevice(h->dev));
   int rc = load_single(h, 1, theta);
   if (rc) return rc;
@@ -1765,6 +1886,7 @@ int vqe_set_noise(vqe_t* h, double p1, double p2, uint64_t seed) {
   if (!(p1 >= 0.0 && p1 <= 1.0 && p2 >= 0.0 && p2 <= 1.0)) return fail(h, VQE_EINVAL, "noise probability outside [0,1]");
   h->noise = NoiseCfg{p1, p2, seed, 0ull, h->noise.shot_sigma};
   ++h->gen;
+  ++h->qj_ver;
   return VQE_OK;
 }
 
@@ -1804,6 +1926,42 @@ int vqe_set_noise_kraus(vqe_t* h, int n1, const double* K1, int n2, const double
     return fail(h, VQE_EINVAL, "Kraus set is not trace preserving: max |sum K^+ K - I| > 1e-12");
   h->kraus = std::move(k);
   ++h->gen;      // the plans and channel tables of the resident batch are made again
+  ++h->qj_ver;
+  return VQE_OK;
+}
+
+int vqe_set_kraus_traj(vqe_t* h, int n_traj) {
+  if (!h) return VQE_EINVAL;
+  if (n_traj < 0 || n_traj > 4096) return fail(h, VQE_EINVAL, "trajectories per evaluation: 0 (off) or 1 .. 4096");
+  if (n_traj != h->kraus_traj) h->qj_traj_batch = 0;      // (vqe_batch_fetch_traj hands out batch x n_traj of the run that made them)
+  h->kraus_traj = n_traj;
+  return VQE_OK;
+}
+
+int vqe_kraus_traj_info(vqe_t* h, int64_t out[4]) {
+  if (!h || !out) return VQE_EINVAL;
+  if (h->qj_jsum_batch > 0) {      // the jump sums of the last evaluation wait on the device
+    HIP_TRY(h, hipSetDevice(h->dev));
+    std::vector<long long> js((size_t)h->qj_jsum_batch);
+    HIP_TRY(h, hipMemcpyAsync(js.data(), h->qj_jsum.p, js.size() * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    h->qj_info[2] = 0;
+    for (long long j : js) h->qj_info[2] += j;
+    h->qj_jsum_batch = 0;
+  }
+  out[0] = h->kraus_traj;
+  std::copy(h->qj_info + 1, h->qj_info + 4, out + 1);
+  return VQE_OK;
+}
+
+int vqe_batch_fetch_traj(vqe_t* h, double* e) {
+  if (!h) return VQE_EINVAL;
+  if (!e) return fail(h, VQE_EINVAL, "e is NULL");
+  if (h->qj_traj_batch <= 0 || h->qj_traj_batch != h->batch)
+    return fail(h, VQE_ESTATE, "no per-trajectory energies: the last run was no trajectory energy run or env-step (vqe_set_kraus_traj)");
+  HIP_TRY(h, hipSetDevice(h->dev));
+  HIP_TRY(h, hipMemcpyAsync(e, h->qj_e.p, (size_t)h->batch * (size_t)h->qj_info[0] * 8, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));
   return VQE_OK;
 }
 
@@ -1885,7 +2043,7 @@ int vqe_set_circuit(vqe_t* h, int n_gates, const int32_t* kind, const int32_t* q
 int vqe_energy_batch(vqe_t* h, int batch, const double* theta, double* energy) {
   if (!h) return VQE_EINVAL;
   if (batch < 1 || !energy || (h->circ_params > 0 && !theta)) return fail(h, VQE_EINVAL, "bad arguments");
-  VQE_TRY(kraus_refusal(h, false));
+  VQE_TRY(kraus_refusal(h, false, true));
   HIP_TRY(h, hipSetDevice(h->dev));
   int rc = load_single(h, batch, theta);
   if (rc) return rc;
@@ -1901,7 +2059,7 @@ int vqe_energy(vqe_t* h, const double* theta, double* energy) { return vqe_energ
 int vqe_get_state(vqe_t* h, const double* theta, double* amps) {
   if (!h) return VQE_EINVAL;
   if (!amps || (h->circ_params > 0 && !theta)) return fail(h, VQE_EINVAL, "bad arguments");
-  VQE_TRY(kraus_refusal(h, true));
+  VQE_TRY(kraus_refusal(h, true, true));
   HIP_TRY(h, hipSetDevice(h->dev));
   int rc = load_single(h, 1, theta);
   if (rc) return rc;
@@ -1918,7 +2076,7 @@ int vqe_minimize_cobyla(vqe_t* h, const double* x0, double rhobeg, double rhoend
   if (!h) return VQE_EINVAL;
   if (maxfun < 1 || !(rhobeg > 0) || !(rhoend > 0)) return fail(h, VQE_EINVAL, "bad COBYLA arguments");
   if (h->circ_params > 0 && (!x0 || !x)) return fail(h, VQE_EINVAL, "x0/x is NULL");
-  VQE_TRY(kraus_refusal(h, false));
+  VQE_TRY(kraus_refusal(h, false, true));
   HIP_TRY(h, hipSetDevice(h->dev));
   int rc = load_single(h, 1, x0);
   if (rc) return rc;

@@ -15,86 +15,8 @@
     if (tid == 0) L.meta[3] = 0;                  // no final gather: run_ops leaves psi physical
     __syncthreads();
     run_ops<N, false>(L, theta, P);
-    // physical index of logical index i: A^-1 (i ^ c)
-    auto phys = [&](uint32_t i) {
-      const uint32_t v = i ^ coff;
-      uint32_t p = 0;
-#pragma unroll
-      for (int q = 0; q < N; ++q) p ^= ((v >> q) & 1u) ? L.xm[q] : 0u;
-      return p;
-    };
-    double2 own[NA];
-    if (permuted) {
-#pragma unroll
-      for (int k = 0; k < NA; ++k) {
-        const uint32_t i = tid + (uint32_t)k * NT;
-        if (DIM >= NT || i < DIM) own[k] = L.psi[phys(i)];
-      }
-      __syncthreads();
-#pragma unroll
-      for (int k = 0; k < NA; ++k) {
-        const uint32_t i = tid + (uint32_t)k * NT;
-        if (DIM >= NT || i < DIM) L.psi[i] = own[k];
-      }
-      __syncthreads();
-    } else {
-#pragma unroll
-      for (int k = 0; k < NA; ++k) {
-        const uint32_t i = tid + (uint32_t)k * NT;
-        if (DIM >= NT || i < DIM) own[k] = L.psi[i];
-      }
-    }
-    // ---- 2. lambda = H psi (logical frame), E = Re <psi|lambda>
-    double2 acc[NA];
-#pragma unroll
-    for (int k = 0; k < NA; ++k) acc[k] = make_double2(0.0, 0.0);
-    for (int g = 0; g < GH.n_groups; ++g) {
-      const uint32_t x = (uint32_t)__builtin_amdgcn_readfirstlane((int)GH.gx[g]);
-      const double* t = GH.tab + GH.off[g];
-      if (x == 0u) {
-#pragma unroll
-        for (int k = 0; k < NA; ++k) {
-          const uint32_t i = tid + (uint32_t)k * NT;
-          if (DIM >= NT || i < DIM) {
-            const double d = t[i];
-            acc[k].x += d * own[k].x;
-            acc[k].y += d * own[k].y;
-          }
-        }
-        continue;
-      }
-      const int hb = 31 - __clz((int)x);
-      const bool cplx = __builtin_amdgcn_readfirstlane(GH.cplx[g]) != 0;
-#pragma unroll
-      for (int k = 0; k < NA; ++k) {
-        const uint32_t i = tid + (uint32_t)k * NT;
-        if (DIM >= NT || i < DIM) {
-          const uint32_t j = i ^ x;
-          const uint32_t up = (i >> hb) & 1u;            // 1: i is the p0 ^ x member of its pair
-          const uint32_t i0 = up ? j : i;
-          const uint32_t q = ((i0 >> (hb + 1)) << hb) | (i0 & ((1u << hb) - 1u));
-          const double2 a = L.psi[j];
-          if (cplx) {
-            const double2 d = ((const double2*)t)[q];
-            const double di = up ? d.y : -d.y;           // T for the p0 -> p0 ^ x direction, conj(T) for the other
-            acc[k].x += d.x * a.x - di * a.y;
-            acc[k].y += d.x * a.y + di * a.x;
-          } else {
-            const double d = t[q];
-            acc[k].x += d * a.x;
-            acc[k].y += d * a.y;
-          }
-        }
-      }
-    }
-    double e_part = 0.0;
-#pragma unroll
-    for (int k = 0; k < NA; ++k) {
-      const uint32_t i = tid + (uint32_t)k * NT;
-      if (DIM >= NT || i < DIM) e_part += own[k].x * acc[k].x + own[k].y * acc[k].y;
-    }
-    const double e = block_sum<NW>(e_part, L.red);   // (its barriers also end every read of psi above)
-    __syncthreads();
+    // ---- gather into logical order and 2. lambda = H psi, E = Re <psi|lambda> (shared with vqe_qjump.h)
+#include "vqe_grad_energy.h"
     if constexpr (BACKWARD) {                     // (not for the energy alone: the last evaluation of an environment step)
     // back to the physical frame: psi[phys(i)] = psi_logical[i], the same for lambda
 #pragma unroll

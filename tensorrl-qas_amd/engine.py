@@ -86,6 +86,9 @@ class VQEEngine:
             self._h = C.c_void_p()
             raise VQEError(f"vqe_create failed ({rc}): {msg.decode() if msg else ''}")
         self._batch = 0
+        self._traj_rows = 0      # the rows of batch_fetch_traj: the circuits of the last energy call / batch load that
+                                 # succeeded, and never fewer than the library's resident batch (a call that fails may
+                                 # or may not have loaded its batch: the count only grows until one succeeds)
         self._total_params = 0
 
     # -- plumbing -------------------------------------------------------------------------
@@ -258,7 +261,7 @@ class VQEEngine:
         at GATE_DEPOL1 gates in the depolarising channel's place; ``K2``: (k, 4, 4) complex for GATE_DEPOL2, basis index
         = bit(q0) + 2 bit(q1) of the gate's two qubits.  ``None`` (or an empty set) leaves that slot on the depolarising
         channel of set_noise; both ``None`` removes the override.  While one is installed only mode 1 runs are served:
-        mode 0 runs and get_state* raise."""
+        mode 0 runs and get_state* raise, unless set_kraus_traj switched the quantum-jump trajectories on."""
         def pack(K, d, name):
             if K is None:
                 return 0, None
@@ -277,6 +280,29 @@ class VQEEngine:
         out = (C.c_int32 * 2)()
         self._chk(self._lib.vqe_noise_kraus_info(self._h, out))
         return {"n1": out[0], "n2": out[1]}
+
+    def set_kraus_traj(self, n_traj: int):
+        """Mode 0 under a Kraus override (set_noise_kraus): evaluate an energy as the mean of ``n_traj`` quantum-jump
+        trajectories (1 .. 4096; 0, the default, leaves those runs refused).  Served: energy / energy_batch /
+        batch_run_energy, minimize_cobyla / batch_run_minimize / batch_run_env_step (COBYLA on the device, in
+        lock-step) and get_state* (the normalised state of trajectory 0); n <= 13, unsharded handles.  Gradient, L-BFGS
+        and reduction calls stay refused.  The definition of a trajectory: include/vqe_hip.h."""
+        self._chk(self._lib.vqe_set_kraus_traj(self._h, int(n_traj)))
+
+    def kraus_traj_info(self):
+        """The trajectory count and the last trajectory run: workgroups of its last launch, jumps (selections k != 0)
+        of its last evaluation summed over circuits and trajectories, lock-step evaluations (1 for an energy run)."""
+        out = (C.c_int64 * 4)()
+        self._chk(self._lib.vqe_kraus_traj_info(self._h, out))
+        return {"n_traj": out[0], "workgroups": out[1], "jumps": out[2], "evaluations": out[3]}
+
+    def batch_fetch_traj(self) -> np.ndarray:
+        """(batch, n_traj) per-trajectory energies of the last energy run, or of the final full-circuit evaluation of
+        the last env-step; raises after anything else."""
+        info = self.kraus_traj_info()
+        out = np.empty((max(1, self._traj_rows), max(1, int(info["n_traj"]))), np.float64)
+        self._chk(self._lib.vqe_batch_fetch_traj(self._h, _p(out, c_f64p)))
+        return out
 
     def set_dm_rot2(self, enable: bool = True):
         """Exact channel mode: take GATE_RXX / RYY / RZZ as members of the superoperator blocks (serial and batched path,
@@ -303,13 +329,17 @@ class VQEEngine:
         if th.size != self._P:
             raise ValueError("theta has the wrong length")
         e = C.c_double()
+        self._traj_rows = max(self._traj_rows, 1)
         self._chk(self._lib.vqe_energy(self._h, _p(th, c_f64p), C.byref(e)))
+        self._traj_rows = 1
         return e.value
 
     def energy_batch(self, thetas) -> np.ndarray:
         th = _f64(thetas).reshape(-1, self._P) if self._P else np.zeros((len(thetas), 0))
         out = np.empty(th.shape[0], np.float64)
+        self._traj_rows = max(self._traj_rows, th.shape[0])
         self._chk(self._lib.vqe_energy_batch(self._h, th.shape[0], _p(th, c_f64p), _p(out, c_f64p)))
+        self._traj_rows = th.shape[0]
         return out
 
     def energy_grad(self, theta):
@@ -498,9 +528,11 @@ class VQEEngine:
         gate_off, par_off = _i64(gate_off), _i64(par_off)
         kind, q0, q1, pidx, theta = _i32(kind), _i32(q0), _i32(q1), _i32(pidx), _f64(theta)
         B = gate_off.size - 1
+        self._traj_rows = max(self._traj_rows, B)
         self._chk(self._lib.vqe_batch_load(self._h, B, _p(gate_off, c_i64p), _p(kind, c_i32p), _p(q0, c_i32p),
                                            _p(q1, c_i32p), _p(pidx, c_i32p), _p(par_off, c_i64p), _p(theta, c_f64p)))
         self._batch, self._total_params, self._par_off = B, int(par_off[-1]), par_off
+        self._traj_rows = B
 
     def batch_run_energy(self):
         self._chk(self._lib.vqe_batch_run_energy(self._h))

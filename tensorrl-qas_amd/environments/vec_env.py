@@ -87,12 +87,13 @@ class VecCircuitEnv:
     deterministic energies, 2 <= n <= 13).
     ``noise_kraus``: ``(K1, K2)``, Kraus sets (``channels``) for the channel behind every rotation and behind every CNOT
     in the depolarising channels' place, either of them ``None`` for the depolarising channel; needs
-    noise_channel = "exact" (a general channel has no Pauli-trajectory form).  Set on the engine once, for the life of
-    the batch."""
+    noise_channel = "exact" (a general channel has no Pauli-trajectory form), or noise_channel = "trajectory" together
+    with ``kraus_trajectories`` = T >= 1: every evaluation is then the mean of T quantum-jump trajectories of the
+    channel (the engine's set_kraus_traj; n <= 13).  Set on the engine once, for the life of the batch."""
 
     def __init__(self, env_cls, conf, device, num_envs: int, seed: int = 0, native: bool | None = None,
                  device_optimizer: str = "cobyla", lbfgs_opts: dict | None = None, noise_channel: str = "trajectory",
-                 noise_kraus=None):
+                 noise_kraus=None, kraus_trajectories: int | None = None):
         if not issubclass(env_cls, CircuitEnvBase):
             raise TypeError("env_cls must be one of the CircuitEnv classes of this package")
         if device_optimizer not in ("cobyla", "lbfgs"):
@@ -103,8 +104,15 @@ class VecCircuitEnv:
             raise ValueError('noise_channel must be "trajectory" or "exact"')
         if noise_channel == "exact" and not getattr(env_cls, "NOISY", False):
             raise ValueError('noise_channel = "exact" is for the noisy environment classes (Pauli noise behind every gate)')
+        if kraus_trajectories is not None:
+            if noise_kraus is None or noise_channel != "trajectory":
+                raise ValueError('kraus_trajectories needs noise_kraus and noise_channel = "trajectory"')
+            if not 1 <= int(kraus_trajectories) <= 4096:
+                raise ValueError("kraus_trajectories must be in [1, 4096]")
+            if not getattr(env_cls, "NOISY", False):
+                raise ValueError("kraus_trajectories is for the noisy environment classes (a channel behind every gate)")
         if noise_kraus is not None:
-            if noise_channel != "exact":
+            if noise_channel != "exact" and kraus_trajectories is None:
                 raise ValueError('noise_kraus needs noise_channel = "exact"')
             if len(noise_kraus) != 2:
                 raise ValueError("noise_kraus is a pair (K1, K2)")
@@ -129,6 +137,11 @@ class VecCircuitEnv:
                 self.engine.set_dm_grad(True)            # the adjoint gradient of tr(rho H) on the batched path
             if noise_kraus is not None:                  # (after the constructor's set_noise and its get_state)
                 self.engine.set_noise_kraus(noise_kraus[0], noise_kraus[1])
+        if kraus_trajectories is not None:               # (after the constructor's set_noise and its get_state)
+            if device_optimizer != "cobyla":
+                raise NotImplementedError("quantum-jump trajectories are served by the device COBYLA")
+            self.engine.set_noise_kraus(noise_kraus[0], noise_kraus[1])
+            self.engine.set_kraus_traj(int(kraus_trajectories))
         if device_optimizer == "lbfgs" and first.num_qubits >= 14:
             self.engine.set_stream_lbfgs(True)           # the streaming path runs the device L-BFGS on request only
         self._proto = first
@@ -157,6 +170,7 @@ class VecCircuitEnv:
         lib = _lib.load()
         self._lib = lib
         n, L, B = self.num_qubits, self.num_layers, self.num_envs
+        self.engine._traj_rows = B          # the compiled loop loads its batches itself (engine.batch_fetch_traj)
         base_obs = first.reset()                         # E(initial circuit), TN encoding of the trainable path
         st = first.state.numpy()
         lay, row, col = np.nonzero(st[:, :n + 3, :] == 1)

@@ -247,11 +247,28 @@ int vqe_noise_kraus_info(vqe_t* h, int32_t out[2]);
  * vqe_batch_run_env_step (COBYLA on the device, all circuits in lock-step), and vqe_get_state / vqe_get_state_dev in
  * either noise mode: the normalised state of trajectory 0 at the counter.  Still refused with VQE_ESTATE before anything
  * is loaded or launched: gradient and L-BFGS calls, vqe_batch_run_reduction, term- or amplitude-sharded handles,
- * n >= 14. */
+ * n >= 14 (unless vqe_set_stream_kraus_traj switched the streaming path's trajectories on). */
 int vqe_set_kraus_traj(vqe_t* h, int n_traj);
-/* out[0] n_traj, [1] workgroups of the last trajectory launch, [2] jumps (selections k != 0) of the last evaluation,
- * summed over circuits and trajectories, [3] lock-step evaluations of the last run (1 for an energy run) */
+/* out[0] n_traj, [1] workgroups of the last trajectory launch (n >= 14: of the last state sweep launched), [2] jumps
+ * (selections k != 0) of the last evaluation, summed over circuits and trajectories, [3] lock-step evaluations of the
+ * last run (1 for an energy run) */
 int vqe_kraus_traj_info(vqe_t* h, int64_t out[4]);
+/* Quantum-jump trajectories on the streaming path (n >= 14, csrc/vqe_stream_qjump.h), opt-in per handle.  max_resident:
+ * 0 (default) off - a handle with n >= 14 refuses trajectory runs with VQE_ESTATE as before, code and text; -1 on, with
+ * as many (circuit, trajectory) states resident as fit into a quarter of the free device memory at the first run (at
+ * least 1, at most batch x n_traj); R >= 1 on, with at most R resident; < -1 VQE_EINVAL, handle unchanged.  Accepted on
+ * any handle; no effect at n <= 13, where the LDS-resident path keeps serving.  With the switch on, an override (or
+ * depolarising slots beside one), vqe_set_kraus_traj(T >= 1) and n >= 14, every call vqe_set_kraus_traj lists as served
+ * runs T trajectories per circuit, each a state of 16 * 2^n bytes in device memory, batch x T of them chunk by chunk:
+ * the same trajectory definition, draws and counter rules.  The per-trajectory energies, the mean and the state of
+ * trajectory 0 have the same bits for the same seed, counter, batch position and T, whatever the batch around the
+ * circuit and whatever max_resident.  Still refused with VQE_ESTATE before anything is loaded or launched: sharded
+ * handles, gradient, L-BFGS and reduction-only calls. */
+int vqe_set_stream_kraus_traj(vqe_t* h, int max_resident);
+/* out[0] states resident per chunk in the last run on that path, [1] chunks per evaluation, [2] jump rounds (the most
+ * noise records of a resident circuit), [3] state sweeps launched per chunk and evaluation before the energy (the
+ * initial state, the rotation sweeps of every round, two per jump round); all 0 before such a run */
+int vqe_stream_kraus_traj_info(vqe_t* h, int64_t out[4]);
 /* per-trajectory energies e[b * n_traj + t] of the last energy run, or of the final full-circuit evaluation of the last
  * env-step; VQE_ESTATE after anything else (a new batch, any other run, a vqe_set_kraus_traj that changes n_traj) */
 int vqe_batch_fetch_traj(vqe_t* h, double* e /* batch x n_traj */);

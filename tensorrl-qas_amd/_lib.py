@@ -73,6 +73,8 @@ SIGNATURES = {
     "vqe_set_kraus_traj": (C.c_int, [vp, C.c_int]),
     "vqe_kraus_traj_info": (C.c_int, [vp, c_i64p]),
     "vqe_batch_fetch_traj": (C.c_int, [vp, c_f64p]),
+    "vqe_set_stream_kraus_traj": (C.c_int, [vp, C.c_int]),
+    "vqe_stream_kraus_traj_info": (C.c_int, [vp, c_i64p]),
     "vqe_set_dm_rot2": (C.c_int, [vp, C.c_int]),
     "vqe_dm_plan": (C.c_int, [C.c_int, C.c_int, c_i32p, c_i32p, c_i32p, c_i32p, c_f64p, C.c_double, C.c_double, C.c_int, c_i32p,
                               c_i32p, c_f64p]),

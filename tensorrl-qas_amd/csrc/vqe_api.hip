@@ -12,6 +12,7 @@
 #include "vqe_stream_lbfgs.h"
 #include "vqe_lanczos.h"
 #include "vqe_qjump.h"
+#include "vqe_stream_qjump.h"
 #include "ham_layout.h"
 #include "dm_host.h"
 #include "env_step_host.h"
@@ -177,6 +178,17 @@ struct vqe_handle {
   int64_t qj_info[4] = {0, 0, 0, 0};
   int qj_traj_batch = 0;       // circuits whose per-trajectory energies vqe_batch_fetch_traj hands out (0: none)
   int qj_jsum_batch = 0;       // circuits of the last evaluation (its jump sums wait in qj_jsum)
+  // ... on the streaming path (vqe_set_stream_kraus_traj, vqe_stream_qjump.h): max_resident (0: refused as before, -1 a
+  // quarter of the free memory, R >= 1), the states that fit (fixed at the first run), the compiled circuits (records,
+  // frame, jump positions, cos / sin), the partial rows and the matrix of the jump in flight of every resident state
+  int sq_resident = 0;
+  size_t sq_auto_cap = 0;
+  int64_t sq_info[4] = {0, 0, 0, 0};
+  DevBuf<QjOp> sq_ops;
+  DevBuf<uint32_t> sq_masks;
+  DevBuf<int32_t> sq_meta, sq_jpos;
+  DevBuf<double2> sq_cs;
+  DevBuf<double> sq_part, sq_kmat;
   // device Lanczos (vqe_lanczos.h): the solver's own copy of the full operator (logical frame) and its vectors
   LzWork lz;
 };
@@ -1192,7 +1204,7 @@ int kraus_refusal(vqe_t* h, bool state_call, bool traj_ok = false) {
   if (traj_ok && h->kraus_traj >= 1 && (state_call || h->noise_mode != 1)) {
     if (h->shard_world > 1 || h->amp_world > 1)
       return fail(h, VQE_ESTATE, "quantum-jump trajectories of a Kraus channel (vqe_set_kraus_traj) take no term- or amplitude-sharded handle");
-    if (!h->lds_path)
+    if (!h->lds_path && h->sq_resident == 0)
       return fail(h, VQE_ESTATE, "quantum-jump trajectories of a Kraus channel (vqe_set_kraus_traj) run for n_qubits <= 13 (LDS-resident path) only");
     return VQE_OK;
   }
@@ -1270,33 +1282,118 @@ int qj_eval(vqe_t* h, const BatchArgs& A, int T, uint64_t eval_id, const int32_t
   return VQE_OK;
 }
 
+// qj_eval on the streaming path (n >= 14, vqe_set_stream_kraus_traj; kernels: vqe_stream_qjump.h): the B T work items
+// are virtual streams with their states in HBM, resident a chunk at a time.  Per chunk: the lock-step rounds `size`
+// counts (sq_trajectories), the frame of every stream in the layout of the streaming path, and that path's own
+// Pauli-term reduction on the virtual batch, whose energies are the chunk's slice of qj_e.  The mean after the last
+// chunk.  Every circuit is evaluated, waited for or not: `active` only keeps f and the jump sums of the others.
+int sq_eval(vqe_t* h, const BatchArgs& A, const SqSize& size, int T, uint64_t eval_id, const int32_t* active, int32_t* nfev,
+            double2* state_out) {
+  const int B = A.batch, n = h->n;
+  const size_t dim = (size_t)1 << n, total = (size_t)B * T;
+  const size_t blocks = (size_t)sq_blocks(n);
+  if (h->sq_resident < 0 && !h->sq_auto_cap) {
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(h, hipMemGetInfo(&free_b, &total_b));
+    h->sq_auto_cap = std::max<size_t>(1, (free_b / 4) / (dim * sizeof(double2) + (blocks * 16 + 32) * sizeof(double)));
+  }
+  const size_t cap = h->sq_resident > 0 ? (size_t)h->sq_resident : h->sq_auto_cap;
+  const int R = (int)std::min<size_t>(std::min<size_t>(cap, total), 65535);      // a chunk is the y extent of a grid
+  StreamWork& sw = h->sw;
+  HIP_TRY(h, sw.states.reserve((size_t)R * dim));
+  HIP_TRY(h, sw.masks.reserve((size_t)R * 64));
+  HIP_TRY(h, sw.meta.reserve((size_t)R * 8));
+  HIP_TRY(h, h->sq_ops.reserve((size_t)B * A.max_ops));
+  HIP_TRY(h, h->sq_jpos.reserve((size_t)B * A.max_ops));
+  HIP_TRY(h, h->sq_masks.reserve((size_t)B * 64));
+  HIP_TRY(h, h->sq_meta.reserve((size_t)B * 8));
+  HIP_TRY(h, h->sq_cs.reserve((size_t)B * A.max_params));
+  HIP_TRY(h, h->sq_part.reserve((size_t)R * blocks * 16));
+  HIP_TRY(h, h->sq_kmat.reserve((size_t)R * 32));
+  HIP_TRY(h, h->qj_e.reserve(total));
+  HIP_TRY(h, h->qj_jumps.reserve(total));
+  HIP_TRY(h, h->qj_jsum.reserve(B));
+  HIP_TRY(h, sq_compile(A, h->qj_n1 > 0, h->qj_n2 > 0, h->sq_ops.p, h->sq_masks.p, h->sq_meta.p, h->sq_jpos.p, h->sq_cs.p, h->stream));
+  HIP_TRY(h, hipMemsetAsync(h->qj_jumps.p, 0, total * sizeof(int32_t), h->stream));
+  SqDev D{};
+  D.n = n; D.T = T;
+  D.states = sw.states.p; D.init = A.init;
+  D.ops = h->sq_ops.p; D.meta = h->sq_meta.p; D.jpos = h->sq_jpos.p; D.cs = h->sq_cs.p;
+  D.max_ops = A.max_ops; D.max_params = A.max_params;
+  D.part = h->sq_part.p; D.kmat = h->sq_kmat.p; D.jumps = h->qj_jumps.p;
+  D.n1 = h->qj_n1; D.n2 = h->qj_n2;
+  D.K1 = h->qj_K1.p; D.W1 = h->qj_W1.p; D.K2 = h->qj_K2.p; D.W2 = h->qj_W2.p;
+  D.seed = A.noise.seed; D.eval_id = eval_id;
+  // the virtual batch of the energy: no circuit of its own (the plans are made per chunk), no noise, no shot term
+  BatchArgs V = A;
+  V.noise.p1 = V.noise.p2 = 0.0;
+  V.noise.shot_sigma = 0.0;
+  int grid = 0;
+  for (size_t c0 = 0; c0 < total; c0 += (size_t)R) {
+    D.cnt = (int)std::min<size_t>((size_t)R, total - c0);
+    D.w0 = (long long)c0;
+    HIP_TRY(h, sq_trajectories(D, size, h->stream, &grid));
+    HIP_TRY(h, sq_frames(D, h->sq_masks.p, sw.masks.p, sw.meta.p, h->stream));
+    V.batch = D.cnt;
+    V.fout = h->qj_e.p + c0;
+    sw.plan_ops_ok = sw.plan_energy_ok = false;
+    VQE_TRY(evaluate(h, V, eval_id, StreamWant::Energy));
+    if (state_out && c0 == 0) {
+      hipLaunchKernelGGL(k_s_state_out, dim3((unsigned)(dim / kThreads)), dim3(kThreads), 0, h->stream, A, sw.states.p, sw.masks.p,
+                         sw.meta.p);
+      HIP_TRY(h, hipGetLastError());
+    }
+  }
+  sw.plan_ops_ok = sw.plan_energy_ok = false;      // (the plans of the last chunk are no circuit's of the resident batch)
+  HIP_TRY(h, sq_mean(B, T, h->qj_e.p, h->qj_jumps.p, active, A.noise, eval_id, A.fout, nfev, h->qj_jsum.p, h->stream));
+  h->qj_info[1] = grid;
+  h->qj_jsum_batch = B;
+  h->sq_info[0] = R;
+  h->sq_info[1] = (int64_t)((total + (size_t)R - 1) / (size_t)R);
+  h->sq_info[2] = size.rounds;
+  h->sq_info[3] = (int64_t)sq_state_sweeps(size);
+  return VQE_OK;
+}
+
 // Run::Energy / State / Minimize / EnvStep on trajectories, in the shape of dm_run_batched: the optimiser of every circuit
 // lives on the device (k_s_cobyla through lockstep_cobyla), an evaluation is qj_eval.  The k-th evaluation of an
 // optimiser run draws at counter + k, the final full-circuit evaluation of an env-step at counter + maxfun + 1.
 int qj_run(vqe_t* h, Run mode, BatchArgs A) {
-  VQE_TRY(build_grad_tables(h));
+  const bool streaming = !h->lds_path;      // (n >= 14: vqe_set_stream_kraus_traj, sq_eval)
+  if (!streaming) VQE_TRY(build_grad_tables(h));
   VQE_TRY(qj_prepare(h));
   const int T = h->kraus_traj;
   const uint64_t base = h->noise.eval_base;
+  // the streaming path's loop is sized on the host, by the walk of the batch an evaluation runs
+  const auto size_of = [&](const std::vector<GateRec>& g, const std::vector<int64_t>& gbeg, const std::vector<int32_t>& gcnt, int batch) {
+    return streaming ? sq_size(g.data(), gbeg.data(), gcnt.data(), batch, h->n, h->qj_n1 > 0, h->qj_n2 > 0) : SqSize{};
+  };
+  const SqSize full = size_of(h->h_gates, h->h_gate_begin, h->h_gate_count, mode == Run::State ? 1 : h->batch);
+  const auto eval = [h, streaming](const BatchArgs& a, const SqSize& size, int n_traj, uint64_t id, const int32_t* active, int32_t* nf,
+                                   double2* state_out) {
+    return streaming ? sq_eval(h, a, size, n_traj, id, active, nf, state_out) : qj_eval(h, a, n_traj, id, active, nf, state_out);
+  };
   h->qj_traj_batch = 0;
   h->qj_info[0] = T;
   h->qj_info[3] = 1;
+  if (streaming) h->stream_states_undone = true;      // (the states this run leaves are no batch's a reduction-only launch may take)
   HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
   if (mode == Run::Energy) {
-    VQE_TRY(qj_eval(h, A, T, base, nullptr, A.nfev, nullptr));
+    VQE_TRY(eval(A, full, T, base, nullptr, A.nfev, nullptr));
     h->qj_traj_batch = h->batch;
   } else if (mode == Run::State) {
     A.batch = 1;                                  // trajectory 0 of the one circuit
-    VQE_TRY(qj_eval(h, A, 1, base, nullptr, nullptr, A.state_out));
+    VQE_TRY(eval(A, full, 1, base, nullptr, nullptr, A.state_out));
   } else {
     std::vector<int32_t> nfev;
     VQE_TRY(minimize_or_env_step(h, mode == Run::EnvStep, A, nfev,
-        [&](BatchArgs& a, const PreActionBatch*, std::vector<double>& x, std::vector<double>& f, std::vector<int32_t>& nf) {
-          return lockstep_cobyla(h, a, x, f, nf, [h, T, base](const BatchArgs& t, uint64_t it, const int32_t* active) {
-            return qj_eval(h, t, T, base + it, active, nullptr, nullptr);
+        [&](BatchArgs& a, const PreActionBatch* pre, std::vector<double>& x, std::vector<double>& f, std::vector<int32_t>& nf) {
+          const SqSize size = pre ? size_of(pre->gates, pre->gbeg, pre->gcnt, h->batch) : full;
+          return lockstep_cobyla(h, a, x, f, nf, [&eval, size, T, base](const BatchArgs& t, uint64_t it, const int32_t* active) {
+            return eval(t, size, T, base + it, active, nullptr, nullptr);
           });
         },
-        [&](const BatchArgs& a) { return qj_eval(h, a, T, base + (uint64_t)a.maxfun + 1, nullptr, nullptr, nullptr); }));
+        [&](const BatchArgs& a) { return eval(a, full, T, base + (uint64_t)a.maxfun + 1, nullptr, nullptr, nullptr); }));
     h->qj_info[3] = *std::max_element(nfev.begin(), nfev.end()) + (mode == Run::EnvStep ? 1 : 0);
     if (mode == Run::EnvStep) h->qj_traj_batch = h->batch;
   }
@@ -1320,7 +1417,7 @@ int run(vqe_t* h, Run mode, double rhobeg, double rhoend, int maxfun) {
   const bool exact = h->noise_mode == 1 && (mode == Run::Energy || optimise);
   const bool traj = qj_serves(h, mode);
   if (traj) {
-    if (qj_lds_bytes(h->n, A.max_ops, A.max_params) > (size_t)h->lds_per_cu)
+    if (h->lds_path && qj_lds_bytes(h->n, A.max_ops, A.max_params) > (size_t)h->lds_per_cu)
       return fail(h, VQE_EINVAL, "circuit too large for the trajectory kernel (gates + parameters)");
   } else if (exact) {
     VQE_TRY(dm_refusal(h));
@@ -1384,6 +1481,7 @@ int grad_state_refusal(vqe_t* h) {
 }
 int grad_refusal(vqe_t* h) {
   if (h->noise_mode == 1 && h->dm_grad) return grad_state_refusal(h);
+  if (!h->lds_path && h->sq_resident != 0) VQE_TRY(kraus_refusal(h, false));      // (trajectories on: the override refuses, as at n <= 13)
   if (!h->lds_path && !h->stream_grad)
     return fail(h, VQE_EINVAL, "energy gradients are computed for n_qubits <= 13 (LDS-resident path) only");
   return grad_state_refusal(h);
@@ -1459,6 +1557,7 @@ int lbfgs_check(vqe_t* h, const vqe_lbfgs_opts_t* opts, vqe_lbfgs_opts_t* o) {
   (void)vqe_lbfgs_default_opts(o);
   if (opts) *o = *opts;
   if (h->amp_world > 1) return fail(h, VQE_ESTATE, "the device L-BFGS takes no amplitude shard");      // (only n >= 14 can hold one)
+  if (!h->lds_path && h->sq_resident != 0) VQE_TRY(kraus_refusal(h, false));      // (as in grad_refusal)
   if (!h->lds_path && !h->stream_lbfgs)      // (with or without vqe_set_stream_grad: the optimiser has a switch of its own)
     return fail(h, VQE_EINVAL, "the device L-BFGS runs for n_qubits <= 13 (LDS-resident path) only; "
                                "n_qubits >= 14 after vqe_set_stream_lbfgs");
@@ -1935,6 +2034,20 @@ int vqe_set_kraus_traj(vqe_t* h, int n_traj) {
   if (n_traj < 0 || n_traj > 4096) return fail(h, VQE_EINVAL, "trajectories per evaluation: 0 (off) or 1 .. 4096");
   if (n_traj != h->kraus_traj) h->qj_traj_batch = 0;      // (vqe_batch_fetch_traj hands out batch x n_traj of the run that made them)
   h->kraus_traj = n_traj;
+  return VQE_OK;
+}
+
+int vqe_set_stream_kraus_traj(vqe_t* h, int max_resident) {
+  if (!h) return VQE_EINVAL;
+  if (max_resident < -1) return fail(h, VQE_EINVAL, "max_resident: 0 (off), -1 (a quarter of the free device memory) or R >= 1");
+  h->sq_resident = max_resident;      // (n <= 13: the LDS-resident kernel serves every trajectory; nothing to switch)
+  h->sq_auto_cap = 0;
+  return VQE_OK;
+}
+
+int vqe_stream_kraus_traj_info(vqe_t* h, int64_t out[4]) {
+  if (!h || !out) return VQE_EINVAL;
+  std::copy(h->sq_info, h->sq_info + 4, out);
   return VQE_OK;
 }
 

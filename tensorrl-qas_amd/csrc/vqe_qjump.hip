@@ -1,6 +1,7 @@
 // vqe_qjump.hip - the kernels of vqe_qjump.h and their launcher, in a translation unit of their own (see qj_launch).
 #define VQE_QJUMP_KERNELS
 #include "vqe_qjump.h"
+#include "vqe_stream_qjump.h"      // the streaming path's trajectory kernels share the helpers above
 
 #include <algorithm>
 #include <utility>

@@ -285,9 +285,24 @@ class VQEEngine:
         """Mode 0 under a Kraus override (set_noise_kraus): evaluate an energy as the mean of ``n_traj`` quantum-jump
         trajectories (1 .. 4096; 0, the default, leaves those runs refused).  Served: energy / energy_batch /
         batch_run_energy, minimize_cobyla / batch_run_minimize / batch_run_env_step (COBYLA on the device, in
-        lock-step) and get_state* (the normalised state of trajectory 0); n <= 13, unsharded handles.  Gradient, L-BFGS
-        and reduction calls stay refused.  The definition of a trajectory: include/vqe_hip.h."""
+        lock-step) and get_state* (the normalised state of trajectory 0); unsharded handles, n <= 13 on the
+        LDS-resident path and n >= 14 on the streaming path once set_stream_kraus_traj switched it on.  Gradient,
+        L-BFGS and reduction calls stay refused.  The definition of a trajectory: include/vqe_hip.h."""
         self._chk(self._lib.vqe_set_kraus_traj(self._h, int(n_traj)))
+
+    def set_stream_kraus_traj(self, max_resident: int = -1):
+        """Quantum-jump trajectories at n >= 14 (the streaming path), opt-in per handle: every (circuit, trajectory)
+        pair is a state of 16 * 2^n bytes in device memory, ``max_resident`` of them at a time (-1: as many as fit
+        into a quarter of the free device memory at the first run; 0: off, the runs are refused as before).  The bits
+        of an energy do not depend on it.  No effect at n <= 13."""
+        self._chk(self._lib.vqe_set_stream_kraus_traj(self._h, int(max_resident)))
+
+    def stream_kraus_traj_info(self):
+        """The last trajectory run on the streaming path (all 0 before one): states resident per chunk, chunks per
+        evaluation, jump rounds, state sweeps launched per chunk and evaluation ahead of the energy."""
+        out = (C.c_int64 * 4)()
+        self._chk(self._lib.vqe_stream_kraus_traj_info(self._h, out))
+        return {"resident": out[0], "chunks": out[1], "rounds": out[2], "sweeps": out[3]}
 
     def kraus_traj_info(self):
         """The trajectory count and the last trajectory run: workgroups of its last launch, jumps (selections k != 0)

@@ -89,7 +89,8 @@ class VecCircuitEnv:
     in the depolarising channels' place, either of them ``None`` for the depolarising channel; needs
     noise_channel = "exact" (a general channel has no Pauli-trajectory form), or noise_channel = "trajectory" together
     with ``kraus_trajectories`` = T >= 1: every evaluation is then the mean of T quantum-jump trajectories of the
-    channel (the engine's set_kraus_traj; n <= 13).  Set on the engine once, for the life of the batch."""
+    channel (the engine's set_kraus_traj; at 14 qubits and more the engine's set_stream_kraus_traj is switched on for
+    it, while noise_channel = "exact" stays at n <= 13).  Set on the engine once, for the life of the batch."""
 
     def __init__(self, env_cls, conf, device, num_envs: int, seed: int = 0, native: bool | None = None,
                  device_optimizer: str = "cobyla", lbfgs_opts: dict | None = None, noise_channel: str = "trajectory",
@@ -142,6 +143,8 @@ class VecCircuitEnv:
                 raise NotImplementedError("quantum-jump trajectories are served by the device COBYLA")
             self.engine.set_noise_kraus(noise_kraus[0], noise_kraus[1])
             self.engine.set_kraus_traj(int(kraus_trajectories))
+            if first.num_qubits >= 14:
+                self.engine.set_stream_kraus_traj(-1)    # the streaming path runs trajectories on request only
         if device_optimizer == "lbfgs" and first.num_qubits >= 14:
             self.engine.set_stream_lbfgs(True)           # the streaming path runs the device L-BFGS on request only
         self._proto = first

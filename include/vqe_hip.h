@@ -224,6 +224,28 @@ int vqe_set_dm_grad(vqe_t* h, int enable);
 int vqe_set_noise_kraus(vqe_t* h, int n1, const double* K1, int n2, const double* K2);
 /* out[0], out[1]: Kraus operators installed in the one- / two-qubit slot, 0 = none */
 int vqe_noise_kraus_info(vqe_t* h, int32_t out[2]);
+/* Pauli channels in the two noise slots (csrc/noise_pauli.h): qulacs BitFlipNoise, DephasingNoise,
+ * IndependentXZNoise, or any biased channel rho -> w_0 rho + sum_k w_k P_k rho P_k.  w1[k - 1], k = 1 .. 3: the
+ * probability of X, Y, Z at a VQE_GATE_DEPOL1 gate.  w2[k - 1], k = 1 .. 15: the probability of code k = a | b << 2 at a
+ * VQE_GATE_DEPOL2 gate, a acting on q0 and b on q1, each 1 = X, 2 = Y, 3 = Z.  The identity's probability w_0 is the
+ * remainder.  NULL leaves that slot on the depolarising channel of p1 / p2; both NULL removes the tables.
+ * The draw: cum_0 = 0, cum_k = cum_{k-1} + w_k in this order in double; u is the uniform of the depolarising draw - same
+ * hash, key and position numbering in the executed (pre-action) gate list; the code is 0 where u >= cum_m, else the
+ * smallest k with u < cum_k, so an entry with w_k = 0 is never selected.  A slot without a table keeps the rule
+ * 1 + (int)(u / p * m) and its bits; a table with w_k = p / m is not promised to reproduce that rule at marginal draws.
+ * A table is the generalisation of p1 / p2: wherever the depolarising channel of its slot is used, the table's channel
+ * is used instead - the mode 0 sampler on the LDS-resident and the streaming path (energies, states, reduction, device
+ * COBYLA, env-step), mode 1 (serial, batched, gradient and L-BFGS under vqe_set_dm_grad) and the quantum-jump runs of
+ * vqe_set_kraus_traj for a slot without an override, through the Kraus set sqrt(w_0) 1, sqrt(w_k) P_k in the order
+ * k = a + 4 b.  A Kraus override on a slot wins over the table, as it wins over p1 / p2.  Mode 0 gradients and L-BFGS
+ * stay refused while a table has a positive total, as for depolarising noise.  Term-sharded handles serve the tables.
+ * The call touches neither the seed, the evaluation counter, p1 / p2, a Kraus override nor the results of the resident
+ * batch; a later vqe_set_noise does not remove a table; the counter rules of vqe_set_noise hold unchanged.
+ * VQE_EINVAL, handle unchanged, for a NaN, an entry outside [0, 1] or a total above 1 + 1e-12; VQE_ESTATE on an
+ * amplitude-sharded handle (and vqe_set_amplitude_shard refuses a world > 1 while a table is installed). */
+int vqe_set_noise_pauli(vqe_t* h, const double* w1 /* 3, or NULL */, const double* w2 /* 15, or NULL */);
+/* out[0], out[1]: 1 where a table is installed in the one- / two-qubit slot, else 0 */
+int vqe_noise_pauli_info(vqe_t* h, int32_t out[2]);
 /* Mode 0 under a Kraus override (vqe_set_noise_kraus): evaluate an energy as the mean of n_traj quantum-jump
  * trajectories.  0 (default): those runs are refused with VQE_ESTATE as before.  1 .. 4096.  Accepted on any handle;
  * takes effect in mode 0 while an override is installed, 1 <= n <= 13, unsharded handles.  Touches neither seed,

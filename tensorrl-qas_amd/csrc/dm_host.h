@@ -112,6 +112,24 @@ inline double kraus_tp_defect(const cplx* K, int count, int d) {
   }
   return worst;
 }
+// The Kraus set of a Pauli channel (vqe_set_noise_pauli): sqrt(w_0) 1 first, w_0 = 1 - (w_1 + ... + w_m) summed in this
+// order and not below 0, then sqrt(w_k) P_k at k = 1 .. m: X, Y, Z for d = 2; P_b (x) P_a at k = a + 4 b for d = 4 (P_a on
+// q0, the low index bit) - the order of the depolarising set of vqe_set_kraus_traj.  4 or 16 operators; a zero weight
+// leaves a zero operator, which no trajectory selects and which adds nothing to a superoperator.
+inline void pauli_kraus(const double* w, int d, std::vector<cplx>& K) {
+  const int m = d == 2 ? 3 : 15;
+  double tot = 0.0;
+  for (int k = 0; k < m; ++k) tot += w[k];
+  K.clear();
+  for (int b = 0; b < (d == 2 ? 1 : 4); ++b) for (int a = 0; a < 4; ++a) {
+    const int k = a + 4 * b;
+    const double s = std::sqrt(k ? w[k - 1] : std::max(0.0, 1.0 - tot));
+    cplx Ra[2][2], Rb[2][2];
+    pauli_1q(a, Ra); pauli_1q(b, Rb);
+    for (int r = 0; r < d; ++r) for (int c = 0; c < d; ++c)
+      K.push_back(d == 2 ? s * Ra[r][c] : s * Ra[r & 1][c & 1] * Rb[r >> 1][c >> 1]);
+  }
+}
 // What the plan depends on beside the gate list.  orient2: a two-qubit Kraus set is installed, so a G_DEPOL2 member
 // carries the window position of the gate's q0 (depolarising noise is symmetric under exchange of its qubits: pos 0).
 // rot2: RXX / RYY / RZZ are window-sized members like a CNOT (vqe_set_dm_rot2).

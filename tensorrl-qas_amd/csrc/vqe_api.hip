@@ -80,6 +80,12 @@ struct vqe_handle {
   HamDev ham{};
   double unit_score[4] = {1.0, 1.0, 1.0, 1.0};   // bank swizzle: mean / worst slot depth of the unit reads, identity then chosen
   NoiseCfg noise{0.0, 0.0, 0ull, 0ull, 0.0};
+  // Pauli channels of the two noise slots (vqe_set_noise_pauli, noise_pauli.h): the weights as given, the
+  // thresholds (host copy and the device buffer the samplers read), and the Kraus set of every slot that mode 1 and
+  // the quantum-jump runs use - the override where one is installed, else the table's Pauli set, else none (channels)
+  double pauli_w1[3] = {}, pauli_w2[15] = {};
+  NoisePauliTab pauli_tab{};
+  DevBuf<NoisePauliTab> d_pauli_tab;
 
   // single circuit
   std::vector<GateRec> circ;
@@ -135,6 +141,7 @@ struct vqe_handle {
   // Kraus sets in the two channel slots (vqe_set_noise_kraus) and RXX / RYY / RZZ as members (vqe_set_dm_rot2), DESIGN
   // 4.16: both are part of what a plan is made for, so setting either bumps `gen`
   DmKraus kraus;
+  DmKraus channels;      // (set_channels: made again by vqe_set_noise_kraus and vqe_set_noise_pauli)
   bool dm_rot2 = false;
   DevBuf<double> dmg_part;
   DevBuf<int32_t> dmg_active;
@@ -372,6 +379,27 @@ int dispatch_lds(vqe_t* h, Run mode, const BatchArgs& A) {
                     [&](auto n) -> int { return launch_lds<decltype(n)::value>(h, mode, A); }, LdsSizes{});
 }
 
+// The noise setting a launch reads: p1 / p2 of vqe_set_noise, or for a slot with a table (vqe_set_noise_pauli) the
+// table's total, and the address of the thresholds.  The handle's own p1 / p2 stay what vqe_set_noise made them.
+NoiseCfg launch_noise(const vqe_t* h) {
+  NoiseCfg nz = h->noise;
+  if (h->pauli_tab.has1) nz.p1 = h->pauli_tab.cum1[2];
+  if (h->pauli_tab.has2) nz.p2 = h->pauli_tab.cum2[14];
+  nz.pauli = (h->pauli_tab.has1 || h->pauli_tab.has2) ? h->d_pauli_tab.p : nullptr;
+  return nz;
+}
+// Pauli errors are drawn in mode 0 (by either rule)
+bool pauli_noise_on(const vqe_t* h) {
+  const NoiseCfg nz = launch_noise(h);
+  return nz.p1 > 0.0 || nz.p2 > 0.0;
+}
+// The Kraus set of each slot for mode 1 and the quantum-jump runs: the override, else the table's Pauli set, else none
+void set_channels(vqe_t* h) {
+  h->channels = h->kraus;
+  if (h->kraus.n1 == 0 && h->pauli_tab.has1) { pauli_kraus(h->pauli_w1, 2, h->channels.K1); h->channels.n1 = 4; }
+  if (h->kraus.n2 == 0 && h->pauli_tab.has2) { pauli_kraus(h->pauli_w2, 4, h->channels.K2); h->channels.n2 = 16; }
+}
+
 BatchArgs make_args(vqe_t* h) {
   BatchArgs A{};
   A.n = h->n;
@@ -393,7 +421,7 @@ BatchArgs make_args(vqe_t* h) {
   A.scratch_begin = h->d_scratch_begin.p;
   A.init = h->init.p;
   A.ham = h->ham;
-  A.noise = h->noise;
+  A.noise = launch_noise(h);
   A.max_ops = h->max_ops;
   A.max_pair = h->max_pair;
   A.max_params = h->max_params;
@@ -776,7 +804,7 @@ int dm_prepare_ham(vqe_t* h) {
 int dm_energy_one(vqe_t* h, const GateRec* g, int G, const double* theta, double* e_host) {
   const int n = h->n;
   std::vector<DmBlockHost> blocks;
-  dm_make_blocks(n, g, G, theta, h->noise.p1, h->noise.p2, blocks, h->kraus.any() ? &h->kraus : nullptr, h->dm_rot2);
+  dm_make_blocks(n, g, G, theta, h->noise.p1, h->noise.p2, blocks, h->channels.any() ? &h->channels : nullptr, h->dm_rot2);
   std::vector<double> S(blocks.size() * 512);
   for (size_t k = 0; k < blocks.size(); ++k)
     for (int r = 0; r < 16; ++r) for (int c = 0; c < 16; ++c) {
@@ -826,7 +854,7 @@ int dm_batch_plan(vqe_t* h, DmPlanSlot& P, const std::vector<GateRec>& gates, co
   if (P.gen == h->gen) return VQE_OK;
   DmBatchTables T;
   dm_flatten_plans(h->n, h->batch, gates.data(), gbeg.data(), gcnt.data(), h->noise.p1, h->noise.p2, T,
-                   h->kraus.any() ? &h->kraus : nullptr, h->dm_rot2);
+                   h->channels.any() ? &h->channels : nullptr, h->dm_rot2);
   VQE_TRY(upload(h, P.blk_begin, T.blk_begin));
   VQE_TRY(upload(h, P.blk_circ, T.blk_circ));
   VQE_TRY(upload(h, P.blk_win, T.blk_win));
@@ -1233,21 +1261,22 @@ bool qj_serves(const vqe_t* h, Run mode) {
   return h->kraus_traj >= 1 && h->kraus.any() && mode != Run::Reduce && (mode == Run::State || h->noise_mode != 1);
 }
 
-// The channel tables of the two slots: the override, or the depolarising Kraus set of p1 / p2 (none at probability 0)
+// The channel tables of the two slots: the override, else the Pauli set of a table (vqe_set_noise_pauli), else the
+// depolarising Kraus set of p1 / p2 (none at probability 0)
 int qj_prepare(vqe_t* h) {
   if (h->qj_tab_ver == h->qj_ver) return VQE_OK;
   std::vector<cplx> dep;
   std::vector<double> k1, w1, k2, w2;
-  h->qj_n1 = h->kraus.n1;
-  h->qj_n2 = h->kraus.n2;
-  if (h->kraus.n1 > 0) {
-    qj_build_tables(h->kraus.K1.data(), h->kraus.n1, 2, k1, w1);
+  h->qj_n1 = h->channels.n1;
+  h->qj_n2 = h->channels.n2;
+  if (h->channels.n1 > 0) {
+    qj_build_tables(h->channels.K1.data(), h->channels.n1, 2, k1, w1);
   } else if (h->noise.p1 > 0.0) {
     qj_depol_kraus(h->noise.p1, 2, dep);
     qj_build_tables(dep.data(), h->qj_n1 = 4, 2, k1, w1);
   }
-  if (h->kraus.n2 > 0) {
-    qj_build_tables(h->kraus.K2.data(), h->kraus.n2, 4, k2, w2);
+  if (h->channels.n2 > 0) {
+    qj_build_tables(h->channels.K2.data(), h->channels.n2, 4, k2, w2);
   } else if (h->noise.p2 > 0.0) {
     qj_depol_kraus(h->noise.p2, 4, dep);
     qj_build_tables(dep.data(), h->qj_n2 = 16, 4, k2, w2);
@@ -1327,6 +1356,7 @@ int sq_eval(vqe_t* h, const BatchArgs& A, const SqSize& size, int T, uint64_t ev
   // the virtual batch of the energy: no circuit of its own (the plans are made per chunk), no noise, no shot term
   BatchArgs V = A;
   V.noise.p1 = V.noise.p2 = 0.0;
+  V.noise.pauli = nullptr;
   V.noise.shot_sigma = 0.0;
   int grid = 0;
   for (size_t c0 = 0; c0 < total; c0 += (size_t)R) {
@@ -1472,7 +1502,7 @@ int grad_state_refusal(vqe_t* h) {
     return VQE_OK;
   }
   VQE_TRY(kraus_refusal(h, false));
-  if (h->noise.p1 > 0.0 || h->noise.p2 > 0.0)
+  if (pauli_noise_on(h))
     return fail(h, VQE_ESTATE, "energy gradients of Pauli-noise trajectories are refused (set p1 = p2 = 0)");
   if (h->noise_mode == 1) return fail(h, VQE_ESTATE, "energy gradients are not available in the exact channel noise mode");
   if (h->noise.shot_sigma != 0.0) return fail(h, VQE_ESTATE, "energy gradients with shot noise are refused (set sigma_total = 0)");
@@ -1960,6 +1990,8 @@ int vqe_set_amplitude_shard(vqe_t* h, int rank, int world) {
   if (world < 1 || rank < 0 || rank >= world) return fail(h, VQE_EINVAL, "bad shard rank/world");
   if (h->lds_path && world > 1)
     return fail(h, VQE_ESTATE, "amplitude sharding of the energy sweep exists on the streaming path (n >= 14); use vqe_set_term_shard");
+  if (world > 1 && (h->pauli_tab.has1 || h->pauli_tab.has2))
+    return fail(h, VQE_ESTATE, "Pauli channel tables (vqe_set_noise_pauli) take no amplitude-sharded handle: remove them first");
   const size_t blocks = ((size_t)1 << h->n) >> kETileBits;     // tiles of the energy sweep (vqe_tile.h)
   if (!h->lds_path && (blocks % (size_t)world) != 0) return fail(h, VQE_EINVAL, "world must divide the number of sweep tiles of the energy reduction");
   h->amp_rank = rank;
@@ -2024,6 +2056,7 @@ int vqe_set_noise_kraus(vqe_t* h, int n1, const double* K1, int n2, const double
   if ((n1 > 0 && !(kraus_tp_defect(k.K1.data(), n1, 2) <= 1e-12)) || (n2 > 0 && !(kraus_tp_defect(k.K2.data(), n2, 4) <= 1e-12)))
     return fail(h, VQE_EINVAL, "Kraus set is not trace preserving: max |sum K^+ K - I| > 1e-12");
   h->kraus = std::move(k);
+  set_channels(h);
   ++h->gen;      // the plans and channel tables of the resident batch are made again
   ++h->qj_ver;
   return VQE_OK;
@@ -2082,6 +2115,39 @@ int vqe_noise_kraus_info(vqe_t* h, int32_t out[2]) {
   if (!h || !out) return VQE_EINVAL;
   out[0] = h->kraus.n1;
   out[1] = h->kraus.n2;
+  return VQE_OK;
+}
+
+int vqe_set_noise_pauli(vqe_t* h, const double* w1, const double* w2) {
+  if (!h) return VQE_EINVAL;
+  if (h->amp_world > 1) return fail(h, VQE_ESTATE, "Pauli channel tables (vqe_set_noise_pauli) take no amplitude-sharded handle");
+  if ((w1 && !pauli_weights_ok(w1, 3)) || (w2 && !pauli_weights_ok(w2, 15)))
+    return fail(h, VQE_EINVAL, "Pauli channel table: every weight a number in [0, 1], their sum at most 1");
+  NoisePauliTab t{};
+  if (w1) { t.has1 = 1; pauli_cumulate(w1, 3, t.cum1); }
+  if (w2) { t.has2 = 1; pauli_cumulate(w2, 15, t.cum2); }
+  if (w1 || w2) {
+    // (in stream order behind the launches that read the old table; the source lives in this frame)
+    HIP_TRY(h, hipSetDevice(h->dev));
+    HIP_TRY(h, h->d_pauli_tab.reserve(1));
+    HIP_TRY(h, hipMemcpyAsync(h->d_pauli_tab.p, &t, sizeof t, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+  }
+  h->pauli_tab = t;
+  std::fill(h->pauli_w1, h->pauli_w1 + 3, 0.0);
+  std::fill(h->pauli_w2, h->pauli_w2 + 15, 0.0);
+  if (w1) std::copy(w1, w1 + 3, h->pauli_w1);
+  if (w2) std::copy(w2, w2 + 15, h->pauli_w2);
+  set_channels(h);
+  ++h->gen;      // the plans and channel tables of the resident batch are made again
+  ++h->qj_ver;
+  return VQE_OK;
+}
+
+int vqe_noise_pauli_info(vqe_t* h, int32_t out[2]) {
+  if (!h || !out) return VQE_EINVAL;
+  out[0] = h->pauli_tab.has1;
+  out[1] = h->pauli_tab.has2;
   return VQE_OK;
 }
 

@@ -39,6 +39,7 @@ __device__ long long g_cby_t0_unused;
 #endif
 #include "cobyla_m0.h"
 #include "vqe_geo.h"
+#include "noise_pauli.h"
 
 namespace vqe {
 
@@ -90,7 +91,9 @@ struct HamDev {
   const double* term_ci;    // [n_terms]
 };
 
-struct NoiseCfg { double p1, p2; uint64_t seed; uint64_t eval_base; double shot_sigma; };
+// pauli: NULL, or the thresholds of vqe_set_noise_pauli in device memory (noise_pauli.h); a slot with a table has its
+// total probability in p1 / p2, so `u < p` means "an error" for both rules and p1 = p2 = 0 means "no noise" as before
+struct NoiseCfg { double p1, p2; uint64_t seed; uint64_t eval_base; double shot_sigma; const NoisePauliTab* pauli; };
 
 struct BatchArgs {
   int n;                       // qubits
@@ -156,6 +159,18 @@ __device__ __forceinline__ uint32_t insert0(uint32_t q, int hb) {
   return ((q >> hb) << (hb + 1)) | (q & ((1u << hb) - 1u));
 }
 __device__ __forceinline__ int parity32(uint32_t v) { return __popc(v) & 1; }
+
+// The Pauli code of a draw u < p of a slot: 1 + floor(u / p * m) where the slot is depolarising, else the slot's
+// table (noise_pauli.h).  The table's address is wave-uniform and its memory is constant during a launch: read through
+// the constant address space the thresholds arrive as scalar loads.  Inlined like every device helper (a call would
+// cost its kernel registers; tests/test_abi.py): the noiseless instances of k_lds_minimize are compiled without
+// patch_noise and do not see this code at all.
+typedef __attribute__((address_space(4))) const NoisePauliTab const_pauli_tab;
+__device__ __forceinline__ int noise_slot_code(const NoisePauliTab* tab, double p, bool two, double u) {
+  const_pauli_tab* t = (const_pauli_tab*)tab;
+  if (two) return (tab && t->has2) ? pauli_code(u, t->cum2, 15) : 1 + (int)(u / p * 15.0);
+  return (tab && t->has1) ? pauli_code(u, t->cum1, 3) : 1 + (int)(u / p * 3.0);
+}
 
 // Cross-lane moves by DPP (no LDS traffic, unlike ds_bpermute behind __shfl_xor): within a row
 // of 16 lanes the butterfly is quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror,
@@ -683,8 +698,8 @@ __device__ __forceinline__ void patch_noise_wave(const BatchArgs& A, int b, uint
         kind = r.x; q0 = r.y; q1 = r.z < 0 ? 0 : r.z;
         if (kind == G_DEPOL1 || kind == G_DEPOL2) {
           const double u = noise_uniform_k(nkey, (uint64_t)(i - ((skip >= 0 && i >= skip_end) ? skip_end - skip : 0)));
-          if (kind == G_DEPOL1) { if (u < A.noise.p1) code = 1 + (int)(u / A.noise.p1 * 3.0); }
-          else if (u < A.noise.p2) code = 1 + (int)(u / A.noise.p2 * 15.0);
+          const double p = kind == G_DEPOL1 ? A.noise.p1 : A.noise.p2;
+          if (u < p) code = noise_slot_code(A.noise.pauli, p, kind == G_DEPOL2, u);
         }
       }
       // Pauli on q0 / q1: 1=X 2=Y 3=Z (compile_ops' rule: X part first, then the Z slot reads c)

@@ -94,11 +94,11 @@ __global__ void k_s_compile(BatchArgs A, Op* ops, uint32_t* masks, int32_t* meta
       ++nops;
     } else if (r.kind == G_DEPOL1) {
       const double u = noise_uniform(A.noise.seed, (uint64_t)b, eval_id, (uint64_t)i);
-      if (u < A.noise.p1) pauli(r.q0, 1 + (int)(u / A.noise.p1 * 3.0));
+      if (u < A.noise.p1) pauli(r.q0, noise_slot_code(A.noise.pauli, A.noise.p1, false, u));
     } else if (r.kind == G_DEPOL2) {
       const double u = noise_uniform(A.noise.seed, (uint64_t)b, eval_id, (uint64_t)i);
       if (u < A.noise.p2) {
-        const int idx = 1 + (int)(u / A.noise.p2 * 15.0);
+        const int idx = noise_slot_code(A.noise.pauli, A.noise.p2, true, u);
         pauli(r.q0, idx & 3);
         pauli(r.q1, idx >> 2);
       }

@@ -281,6 +281,29 @@ class VQEEngine:
         self._chk(self._lib.vqe_noise_kraus_info(self._h, out))
         return {"n1": out[0], "n2": out[1]}
 
+    def set_noise_pauli(self, w1=None, w2=None):
+        """Pauli channels in the two noise slots, drawn by the mode 0 sampler itself (one Pauli per gate and evaluation,
+        as qulacs samples BitFlipNoise, DephasingNoise, IndependentXZNoise).  ``w1``: 3 probabilities of X, Y, Z at
+        GATE_DEPOL1 gates; ``w2``: 15 probabilities of the codes ``a | b << 2`` (a on q0, b on q1, 1 = X, 2 = Y, 3 = Z)
+        at GATE_DEPOL2 gates; ``channels.pauli_weights`` / ``channels.pauli_twirl`` make them from a Kraus set.  ``None``
+        leaves that slot on the depolarising channel of set_noise; both ``None`` removes the tables.  Mode 1 and the
+        quantum-jump runs use the same channel; a Kraus override (set_noise_kraus) on a slot wins over its table."""
+        def pack(w, m, name):
+            if w is None:
+                return None
+            a = np.ascontiguousarray(w, dtype=np.float64)
+            if a.shape != (m,):
+                raise ValueError(f"{name} must hold {m} probabilities")
+            return a
+        a1, a2 = pack(w1, 3, "w1"), pack(w2, 15, "w2")
+        self._chk(self._lib.vqe_set_noise_pauli(self._h, _p(a1, c_f64p), _p(a2, c_f64p)))
+
+    def noise_pauli_info(self):
+        """Whether a Pauli table is installed in the one- / two-qubit slot (False: the depolarising channel)."""
+        out = (C.c_int32 * 2)()
+        self._chk(self._lib.vqe_noise_pauli_info(self._h, out))
+        return {"w1": bool(out[0]), "w2": bool(out[1])}
+
     def set_kraus_traj(self, n_traj: int):
         """Mode 0 under a Kraus override (set_noise_kraus): evaluate an energy as the mean of ``n_traj`` quantum-jump
         trajectories (1 .. 4096; 0, the default, leaves those runs refused).  Served: energy / energy_batch /

@@ -90,11 +90,16 @@ class VecCircuitEnv:
     noise_channel = "exact" (a general channel has no Pauli-trajectory form), or noise_channel = "trajectory" together
     with ``kraus_trajectories`` = T >= 1: every evaluation is then the mean of T quantum-jump trajectories of the
     channel (the engine's set_kraus_traj; at 14 qubits and more the engine's set_stream_kraus_traj is switched on for
-    it, while noise_channel = "exact" stays at n <= 13).  Set on the engine once, for the life of the batch."""
+    it, while noise_channel = "exact" stays at n <= 13).  Set on the engine once, for the life of the batch.
+    ``noise_pauli``: ``(w1, w2)``, Pauli channels for the same two places as probability tables (3 weights of X, Y, Z /
+    15 of the two-qubit codes: the engine's set_noise_pauli; ``channels.pauli_weights`` and ``channels.pauli_twirl`` make
+    them), either of them ``None`` for the depolarising channel.  Noisy classes only.  With noise_channel = "trajectory"
+    the fused sampler draws from the tables (native and Python host loop alike), with "exact" the density matrix runs
+    their channel.  A slot takes a table or a Kraus set of ``noise_kraus``, not both."""
 
     def __init__(self, env_cls, conf, device, num_envs: int, seed: int = 0, native: bool | None = None,
                  device_optimizer: str = "cobyla", lbfgs_opts: dict | None = None, noise_channel: str = "trajectory",
-                 noise_kraus=None, kraus_trajectories: int | None = None):
+                 noise_kraus=None, kraus_trajectories: int | None = None, noise_pauli=None):
         if not issubclass(env_cls, CircuitEnvBase):
             raise TypeError("env_cls must be one of the CircuitEnv classes of this package")
         if device_optimizer not in ("cobyla", "lbfgs"):
@@ -117,6 +122,13 @@ class VecCircuitEnv:
                 raise ValueError('noise_kraus needs noise_channel = "exact"')
             if len(noise_kraus) != 2:
                 raise ValueError("noise_kraus is a pair (K1, K2)")
+        if noise_pauli is not None:
+            if not getattr(env_cls, "NOISY", False):
+                raise ValueError("noise_pauli is for the noisy environment classes (a channel behind every gate)")
+            if len(noise_pauli) != 2:
+                raise ValueError("noise_pauli is a pair (w1, w2)")
+            if noise_kraus is not None and any(w is not None and K is not None for w, K in zip(noise_pauli, noise_kraus)):
+                raise ValueError("a noise slot takes a Pauli table (noise_pauli) or a Kraus set (noise_kraus), not both")
         first = env_cls(conf, device, seed=seed)
         if first.optimizer_kind not in (None, "device_cobyla"):
             raise NotImplementedError(f"VecCircuitEnv runs the device COBYLA of batch_run_env_step only; optim_alg = "
@@ -145,6 +157,8 @@ class VecCircuitEnv:
             self.engine.set_kraus_traj(int(kraus_trajectories))
             if first.num_qubits >= 14:
                 self.engine.set_stream_kraus_traj(-1)    # the streaming path runs trajectories on request only
+        if noise_pauli is not None:                      # (after the constructor's set_noise, which leaves tables alone)
+            self.engine.set_noise_pauli(noise_pauli[0], noise_pauli[1])
         if device_optimizer == "lbfgs" and first.num_qubits >= 14:
             self.engine.set_stream_lbfgs(True)           # the streaming path runs the device L-BFGS on request only
         self._proto = first

@@ -86,13 +86,25 @@ def energy_pauli(psi, xmask, zmask, coeff):
     return e
 
 
-def run(psi0, kinds, q0, q1, pidx, theta, K1, K2, ham, seed, b, e, T):
+def run(psi0, kinds, q0, q1, pidx, theta, K1, K2, ham, seed, b, e, T, ts=None):
     """T trajectories of (stream b, evaluation e).  K1 / K2: Kraus set (k, 2, 2) / (k, 4, 4) of the one- / two-qubit
     slot, None: the slot is the identity.  Returns a dict: states (T, 2^n), energies (T,), mean (summed in t order),
     ks (T, slots): the chosen index at every executed noise gate, slot_kind (slots,): 1 or 2, margin: the smallest
-    distance of any u to a boundary of the cumulative distribution, jumps: selections k != 0."""
+    distance of any u to a boundary of the cumulative distribution, jumps: selections k != 0.
+    ``ts``: the trajectory indices to simulate (each in 0 .. T-1; default all of them): the rows of every returned array
+    are those trajectories in the order of ``ts``, and mean, margin and jumps are over them alone.  The draw of a
+    trajectory does not depend on T."""
     psi0 = np.asarray(psi0, np.complex128)
     n = int(round(np.log2(psi0.size)))
+    if ts is not None:
+        ts = [int(t) for t in ts]
+        assert all(0 <= t < T for t in ts), (ts, T)
+        return _run(psi0, n, kinds, q0, q1, pidx, theta, K1, K2, ham, seed, b, e, ts)
+    return _run(psi0, n, kinds, q0, q1, pidx, theta, K1, K2, ham, seed, b, e, range(T))
+
+
+def _run(psi0, n, kinds, q0, q1, pidx, theta, K1, K2, ham, seed, b, e, ts):
+    T = len(ts)
     psi = np.tile(psi0, (T, 1))
     key = noise_key(seed, b, e)
     ks, slot_kind, margin = [], [], np.inf
@@ -114,7 +126,7 @@ def run(psi0, kinds, q0, q1, pidx, theta, K1, K2, ham, seed, b, e, T):
             rho = np.einsum("tgi,tgj->tij", sub, sub.conj())                # rho_red[i, j] = sum psi_i conj(psi_j)
             M = np.einsum("kmi,kmj->kij", K.conj(), K)                      # K^+ K
             p = np.real(np.einsum("kij,tji->tk", M, rho))                   # tr(M_k rho_red)
-            u = np.array([noise_uniform_k(key, ((t + 1) << 44) | g) for t in range(T)])
+            u = np.array([noise_uniform_k(key, ((t + 1) << 44) | g) for t in ts])
             cum = np.zeros(T)
             sel = np.full(T, -1)
             for kk in range(K.shape[0]):

@@ -481,11 +481,17 @@ def dm_grad_oracle():
 FIT_N, FIT_B, FIT_STEPS = 22, 66, 2
 
 
+# ---- quantum-jump trajectories on the streaming path: one chunk of B x T resident states of 256 KiB ---------------------
+TRAJ_N, TRAJ_B, TRAJ_T = 14, 17, 964       # 16 388 states (tests/traj_scale_cases.py): the last four begin past the line
+
+
 def big_buffers(case):
     """-> {buffer: (elements, bytes per element, stride in elements)} of the device buffers of a case of part B that pass
     the line, from the library's own size rules: StreamWork::states and ::lam hold B states of 2^n amplitudes, stream b
     at b << n (csrc/vqe_stream.h, csrc/vqe_stream_grad.h)."""
-    if case == "dm_batched":      # dmb_rho: R resident density matrices of 4^n entries, slot s at s << 2 n (csrc/vqe_dm_batch.h)
+    if case == "stream_traj":     # StreamWork::states of sq_eval: the work item w = b T + t of a chunk at (w - w0) << n (csrc/vqe_stream_qjump.h)
+        return {"states": (TRAJ_B * TRAJ_T << TRAJ_N, AMP_BYTES, 1 << TRAJ_N)}
+    if case == "dm_batched":     # dmb_rho: R resident density matrices of 4^n entries, slot s at s << 2 n (csrc/vqe_dm_batch.h)
         return {"rho": (DM_B << (2 * DM_N), AMP_BYTES, 1 << (2 * DM_N))}
     if case == "trainable_scratch":      # d_scratch: circuit b at scratch_begin[b] = b x stride doubles (load_batch, csrc/vqe_api.hip)
         stride = scratch_stride(trainable_words())
@@ -513,7 +519,7 @@ def big_buffers(case):
 
 
 BIG_CASES = ("stream_energy", "stream_energy_bench", "stream_minimize", "stream_grad", "stream_lbfgs", "trainable_scratch", "dm_batched",
-             "dm_grad", "lanczos", "fit_stream", "fit_resident")
+             "dm_grad", "lanczos", "fit_stream", "fit_resident", "stream_traj")
 NOT_CROSSING = ("env partials",)          # counted in a case's memory, not meant to pass the line
 
 

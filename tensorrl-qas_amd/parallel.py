@@ -9,6 +9,7 @@ Two ways the path shards:
 The reference has no counterpart (single process)."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 
@@ -182,8 +183,11 @@ def fit_restarts_sharded(fit_shard, n_restarts_total: int, group=None):
 # factors on rank positions are signs.  The reference has no counterpart (single process; its 2^n x 2^n matrix stops
 # it at 13 qubits, environments/VQAs/VQE_qulacs_TN_notin_RL.py:86).
 # Status: the planner and the executor below are exercised by tests (gloo world 2 / 4 / 8 on the CPU with a CPU stand-in
-# as the local backend; all shards on ONE GPU with device-to-device copies as the exchange); no run on several GPUs
-# exists yet, so there is no scaling curve for it.
+# as the local backend; all shards on ONE GPU with device-to-device copies as the exchange; two processes on one GPU
+# with CUDA shards, gloo, the halves travelling through the host); no run on several GPUs exists yet, so there is no
+# scaling curve for it.
+# Streams: a backend that works on a stream of its own offers exchange_context(); the exchanges run under it, in plain
+# stream order with the backend's copies (tests/test_stream_order_gpu.py delays either side by 30 ms).
 def _log2_exact(v: int) -> int:
     g = int(v).bit_length() - 1
     if v < 1 or (1 << g) != v:
@@ -289,16 +293,22 @@ class EngineShardBackend:
     def new_shard(self, values):
         t = self.torch.as_tensor(np.ascontiguousarray(values, np.complex128)).to(self.device)
         self.stream.wait_stream(self.torch.cuda.current_stream(self.device))
+        t.record_stream(self.stream)      # allocated on the caller's stream, read and written on this object's from here on
         return t
 
+    def exchange_context(self):
+        """What AmplitudeShardedState._exchange runs under: this object's stream as torch's current one, so the
+        half-shard swaps (their clones, the send / recv staging, the final copy_) sit in plain stream order with the
+        handle's device-to-device copies - before them nothing had landed, after them nothing is read early."""
+        return self.torch.cuda.stream(self.stream)
+
     def apply(self, shard, kind, q0, q1, pidx, theta):
-        out = self.torch.empty_like(shard)
         with self.torch.cuda.stream(self.stream):
+            out = self.torch.empty_like(shard)      # (this stream's own block: torch's allocator reuses it in stream order)
             self.engine.set_init_state_dev(shard.data_ptr())
             self.engine.set_circuit(self.Circuit(kind, q0, q1, pidx, len(theta)))
             self.engine.get_state_dev(theta, out.data_ptr())
         shard.record_stream(self.stream)
-        out.record_stream(self.stream)
         return out
 
     def energy(self, shard, xs, zs, cs):
@@ -309,6 +319,7 @@ class EngineShardBackend:
             self.engine.set_hamiltonian(xs, zs, cs)
             self.engine.set_circuit(self.Circuit.empty())
             e = self.engine.energy(np.zeros(0))
+        shard.record_stream(self.stream)
         return e
 
     def halves(self, shard, local_pos):
@@ -345,6 +356,15 @@ class AmplitudeShardedState:
             self.shards[r] = self.backend.new_shard(psi0[r << self.nl:(r + 1) << self.nl])
 
     def _exchange(self, k, local_pos):
+        """One half-shard exchange, under the backend's ``exchange_context()`` if it has one: a backend that works on a
+        stream of its own (EngineShardBackend) makes that stream the current one, so the exchange is ordered behind the
+        copy that wrote the shard and ahead of the copy that reads it next.  A backend without the hook (host arrays)
+        gets a null context."""
+        ctx = getattr(self.backend, "exchange_context", None)
+        with ctx() if ctx is not None else contextlib.nullcontext():
+            self._exchange_in_order(k, local_pos)
+
+    def _exchange_in_order(self, k, local_pos):
         bit = 1 << k
         done = set()
         for r in self.my_ranks:

@@ -180,6 +180,38 @@ def amp_sharded_cpu(rank, world, port):
     return out
 
 
+AMP_GPU_CASE = (15, 16, 1502)          # n, gates, seed of amp_sharded_gpu (the test rebuilds the case from them)
+
+
+def amp_sharded_gpu(rank, world, port):
+    """Both ranks on cuda:0, gloo: amplitude-sharded STATES across processes with CUDA shards - every process holds one
+    shard of a 15-qubit register as the state of a 14-qubit handle (EngineShardBackend), the half-shard exchanges
+    travel as send / recv pairs through the host, and every exchange is late on its stream (the delayed halves() of
+    tests/stream_order_helpers.py).  One all-reduce sums the partial energies."""
+    dist = _setup(rank, world, port)
+    import numpy as np
+    import torch
+    from tensorrl_qas_amd import parallel
+    from stream_order_helpers import cycles_per_ms, delayed_engine_backend, heisenberg_case, independent_stream
+    n, G, seed = AMP_GPU_CASE
+    case = heisenberg_case(n, world, G, seed)
+    nl = n - (world.bit_length() - 1)
+    backend = delayed_engine_backend(nl, "cuda:0")
+    st = parallel.AmplitudeShardedState(n, world, [rank], backend)
+    with torch.cuda.stream(independent_stream(backend.stream)):      # (no hardware queue shared with the backend's stream)
+        st.load(case["psi0"])
+        part = st.run(case["steps"], *case["gates"], *case["ham"])
+    tot = parallel.allreduce_sum(np.array([part]))
+    ms = [d.ms for d in backend.delays]
+    out = dict(total=float(tot[0]), part=float(part), swaps=int(case["swaps"]), bytes=int(st.exchanged_bytes),
+               shard=int(st.shards[rank].numel()), delays=len(ms), min_delay_ms=float(min(ms)) if ms else 0.0,
+               cycles_per_ms=float(cycles_per_ms()))
+    backend.close()
+    dist.barrier()
+    dist.destroy_process_group()
+    return out
+
+
 def mps2qc_stream_fit(rank, world, port):
     """One process, no process group: the streaming MPS -> PQC fit at 6 qubits (2 layers, batch 2, 5 steps) through
     the C ABI, every output as the hex of its bytes.  MPS2QC_STREAM_GRAPH is read once per process, so each of its
@@ -199,7 +231,7 @@ def mps2qc_stream_fit(rank, world, port):
 
 
 WORKERS = {"sharded_gpu": sharded_gpu, "sharding_cpu": sharding_cpu, "amp_sharded_cpu": amp_sharded_cpu,
-           "mps2qc_stream_fit": mps2qc_stream_fit}
+           "amp_sharded_gpu": amp_sharded_gpu, "mps2qc_stream_fit": mps2qc_stream_fit}
 
 
 def main(argv):

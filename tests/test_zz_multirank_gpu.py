@@ -28,3 +28,23 @@ def test_term_sharded_engine_two_ranks_on_one_gpu(tmp_path):
         x = np.array(r0[key]["x"])
         assert abs(r0[key]["f"] - vo.energy_pauli(vo.run_circuit(psi0, kind, q0, q1, pidx, x), *ham)) < 1e-10
         assert 1 <= r0[key]["nfev"] <= 40
+
+
+def test_amplitude_sharded_states_two_processes_cuda_shards(tmp_path):
+    """world_size 2 (gloo, both ranks on cuda:0), one CUDA shard of a 15-qubit register per process on a 14-qubit
+    handle: the cross-process branch of AmplitudeShardedState._exchange (send / recv through the host, copy back to
+    the device) with every exchange 30 ms late on its stream.  Both ranks report the same total, it is the oracle's
+    energy, and each rank sent half a shard per exchange."""
+    from rank_workers import AMP_GPU_CASE, run_ranks
+    from stream_order_helpers import MIN_DELAY_MS, heisenberg_case
+    n, G, seed = AMP_GPU_CASE
+    case = heisenberg_case(n, 2, G, seed)
+    r0, r1 = run_ranks("amp_sharded_gpu", 2, tmp_path, timeout=120)
+    print("ranks:", r0, r1, "oracle:", case["e"])
+    for r in (r0, r1):
+        assert r["shard"] == 1 << 14 and r["swaps"] == case["swaps"] >= 1
+        assert r["delays"] == 2 * r["swaps"] and r["min_delay_ms"] >= MIN_DELAY_MS      # before the send, before the copy back
+        assert r["bytes"] == r["swaps"] * (1 << 14) * 8
+    assert r0["total"] == r1["total"]
+    assert abs(r0["total"] - case["e"]) < 1e-10
+    assert abs(r0["part"] + r1["part"] - r0["total"]) < 1e-12

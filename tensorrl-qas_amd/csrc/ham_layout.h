@@ -396,7 +396,7 @@ struct HamLayout {
   // distance of the pair members); uaddr: the LDS byte address S(p0) << 4 of the selector-0 member of each
   // (unit, thread); utab: the table values (exactly 0.0 below the zero bound).  uaddr and utab are laid out per trip
   // of kUnitTrip units as [trip][thread][unit of the trip].  The unit count is a multiple of kUnitUnroll (padding:
-  // urec 0, tables of zeros, addresses 0).
+  // urec 0, tables of zeros, addresses 0).  What is uploaded is unit_arrays() below: these plus the look-ahead trips.
   std::vector<uint32_t> urec, uaddr;
   std::vector<double> utab;
   // explicit terms of the group list (all the streaming path, n >= 14, reads)
@@ -477,7 +477,8 @@ inline bool build_units(const HamHost& H, int n, int lt, const std::vector<int>&
       }
     }
   }
-  if (L.utab.size() * sizeof(double) + (size_t)kUnitUnroll * NT * sizeof(double) > 0x7FFFFFFFu) { err = kTooLarge; return false; }
+  // (byte offsets into the table array are 31-bit scalars; the padding below and the look-ahead trips of unit_arrays count)
+  if (L.utab.size() * sizeof(double) + (size_t)(kUnitUnroll + kUnitAhead) * NT * sizeof(double) > 0x7FFFFFFFu) { err = kTooLarge; return false; }
   // padding to a multiple of kUnitUnroll: units with a table of zeros (both members at address 0)
   while (L.urec.size() % kUnitUnroll) {
     L.urec.push_back(0u);
@@ -634,6 +635,27 @@ inline bool plan_hamiltonian(const HamHost& H, int n, bool lds_path, int rank, i
     L.mrow[i] = row;
   }
   return true;
+}
+
+// The unit arrays as the unit loop (vqe_device.h: unit_energy) reads them: the n_units units of the layout - whole
+// turns of accumulated trips - followed by kUnitAhead zero units (record 0, table values 0.0, addresses 0: valid LDS
+// addresses).  The loop requests tables and addresses two trips and the record one trip ahead of the trip it
+// accumulates; with these look-ahead trips behind the last accumulated one it steps its offsets by constants and
+// clamps nothing.  They are only ever prefetched: the loop bound stays n_units.  A layout without units has none.
+struct UnitArrays {
+  int n_units = 0;                   // accumulated units (HamLayout::urec.size()): the loop bound
+  std::vector<uint32_t> urec, uaddr; // [n_units + kUnitAhead], [(n_units + kUnitAhead) * NT]
+  std::vector<double> utab;          // [(n_units + kUnitAhead) * NT]
+};
+inline UnitArrays unit_arrays(const HamLayout& L, int lt) {
+  UnitArrays A;
+  A.n_units = (int)L.urec.size();
+  if (!A.n_units) return A;
+  const size_t NT = (size_t)1 << lt, total = L.urec.size() + (size_t)kUnitAhead;
+  A.urec = L.urec;   A.urec.resize(total, 0u);
+  A.uaddr = L.uaddr; A.uaddr.resize(total * NT, 0u);     // ([trip][thread][unit of the trip]: whole trips go at the end)
+  A.utab = L.utab;   A.utab.resize(total * NT, 0.0);
+  return A;
 }
 
 // ---- adjoint gradient (vqe_grad.h) -----------------------------------------------------------

@@ -242,14 +242,15 @@ int build_hamiltonian(vqe_t* h, HamHost* H, int rank, int world) {
   VQE_TRY(upload(h, h->d_term_z, L.term_z));
   VQE_TRY(upload(h, h->d_term_cr, L.term_cr));
   VQE_TRY(upload(h, h->d_term_ci, L.term_ci));
-  VQE_TRY(upload(h, h->d_urec, L.urec));
-  VQE_TRY(upload(h, h->d_uaddr, L.uaddr));
-  VQE_TRY(upload(h, h->d_utab, L.utab));
+  const UnitArrays UA = unit_arrays(L, geo_lt(h->n));     // the units and the look-ahead trips behind them
+  VQE_TRY(upload(h, h->d_urec, UA.urec));
+  VQE_TRY(upload(h, h->d_uaddr, UA.uaddr));
+  VQE_TRY(upload(h, h->d_utab, UA.utab));
   HIP_TRY(h, hipStreamSynchronize(h->stream));  // the layout goes out of scope
   HamDev& d = h->ham;
   d.n_groups = (int)L.gx.size();
   d.n_terms = (int)L.term_z.size();
-  d.n_units = (int)L.urec.size();
+  d.n_units = UA.n_units;
   d.gx = h->d_gx.p; d.tab_r = h->d_tab_r.p; d.tab_i = h->d_tab_i.p; d.tables = h->d_tables.p;
   d.urec = h->d_urec.p; d.uaddr = h->d_uaddr.p; d.utab = h->d_utab.p;
   d.term_off = h->d_term_off.p; d.term_z = h->d_term_z.p; d.term_cr = h->d_term_cr.p; d.term_ci = h->d_term_ci.p;
@@ -360,7 +361,7 @@ int launch_lds(vqe_t* h, Run mode, BatchArgs A) {
              : (noisy ? k_lds_minimize<N, kW, true> : k_lds_minimize<N, kW, false>);
   const void* fn = (const void*)kernel;
   HIP_TRY(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  {   // the unit loop addresses the state region absolutely (lds_load_abs): the dynamic LDS must start at 0
+  {   // the unit loop addresses the state region absolutely (unit_lds_read): the dynamic LDS must start at 0
     hipFuncAttributes fa;
     HIP_TRY(h, hipFuncGetAttributes(&fa, fn));
     if (fa.sharedSizeBytes != 0) return fail(h, VQE_ESTATE, "LDS-resident kernel was built with static LDS");

@@ -78,9 +78,10 @@ struct HamDev {
   int n_cls;                // register path: leading real groups whose x' has a register bit (multiple of energy_pd(n))
   uint32_t mrow[16];        // row i of S M: bit i of the LDS slot of p' = parity(mrow[i] & p) (the final scatter's map)
   uint64_t swz;             // bank swizzle: p' lives at LDS slot swz_slot(swz, p'); 0 = identity
-  // unit path: n_units a multiple of kUnitUnroll; uaddr and utab as [trip][thread][unit of the trip]
+  // unit path: n_units a multiple of kUnitUnroll; uaddr and utab as [trip][thread][unit of the trip]; all three arrays
+  // end with kUnitAhead zero units behind the n_units accumulated ones (ham_layout.h: unit_arrays)
   int n_units;
-  const uint32_t* urec;     // [n_units] S(x') << 4: the byte-address distance of the pair members
+  const uint32_t* urec;     // [n_units + kUnitAhead] S(x') << 4: the byte-address distance of the pair members
   const uint32_t* uaddr;    // LDS byte address of the selector-0 member of each (unit, thread)
   const double* utab;       // table values
   // streaming path (n >= 14): explicit terms
@@ -1232,15 +1233,33 @@ __device__ __forceinline__ void pair_fma1(double& acc0, const double2& a0, const
 // (Measured and dropped: trips whose four units share ONE deposit - a hopping pair's four units differ in two filler
 // bits only -: 13 instead of 28 integer instructions for 28 of the bench Hamiltonian's 45 trips, but a second loop, its
 // own prologue and padding of both phases to whole turns: 326.4 ms against 327.8, not worth a second code path.)
+typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(4))) const u32x4_t const_u32x4;
+
 // LDS read at an ABSOLUTE byte address.  The state region starts the dynamic LDS of these kernels and they have no
 // static LDS (launch_lds checks the function's static size), so its address is 0; going through the `smem` symbol
 // costs a v_add_u32 of that late-bound zero per read.
-__device__ __forceinline__ double2 lds_load_abs(uint32_t addr) {
-  const d2v_t v = *(const __attribute__((address_space(3))) d2v_t*)(uintptr_t)addr;
-  return make_double2(v.x, v.y);
+// The reads of a trip are hidden from the compiler's wait bookkeeping.  The record load of the next trip shares their
+// counter and returns out of order, so the compiler waits for ALL of a trip's reads in front of its first FP64
+// instruction; counted by hand, the arithmetic of a unit starts when its own two reads are in (unit_energy).  A read's
+// destination counts as written where its statement ends: nothing but unit_wait may touch it before the wait that
+// covers it, so unit_wait names the registers it releases as read-write operands and every consumer hangs off those.
+// (One statement per read, not one block per trip: a block cannot name the 64-bit halves of a 128-bit operand, and a
+// read's destination may then overlap its own address register, as the compiler's own reads did - no more registers.)
+__device__ __forceinline__ void unit_lds_read(d2v_t& dst, uint32_t addr) {
+  asm volatile("ds_read_b128 %0, %1" : "=v"(dst) : "v"(addr) : "memory");
 }
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(4))) const u32x4_t const_u32x4;
+template <int CNT>
+__device__ __forceinline__ void unit_wait(d2v_t& p0, d2v_t& p1) {
+  asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(p0), "+v"(p1) : "n"(CNT));
+}
+// acc += (a.x * b.x + a.y * b.y) * d, rounded as the compiler's contraction of that expression rounds it (the y
+// product first, the x product fused onto it, the sum fused onto acc): results are pinned bit for bit
+__device__ __forceinline__ void unit_fma(double& acc, const d2v_t& a, const d2v_t& b, double d) {
+  double t;
+  asm("v_mul_f64 %1, %3, %5\n\tv_fmac_f64 %1, %2, %4\n\tv_fmac_f64 %0, %1, %6"
+      : "+v"(acc), "=&v"(t) : "v"(a.x), "v"(a.y), "v"(b.x), "v"(b.y), "v"(d));
+}
 
 template <int N>
 __device__ __forceinline__ void unit_energy(const Lds& L, const HamDev& H, double& acc0, double& acc1) {
@@ -1256,35 +1275,35 @@ __device__ __forceinline__ void unit_energy(const Lds& L, const HamDev& H, doubl
   asm volatile("" : "+v"(tid));
   const __amdgpu_buffer_rsrc_t ru = table_rsrc(H.utab);
   const __amdgpu_buffer_rsrc_t ra = table_rsrc(H.uaddr);
-  const const_u32x4* rec = (const const_u32x4*)H.urec;     // X masks << 4 of the U units of a trip
+  typedef __attribute__((address_space(4))) const unsigned char const_byte;
+  const_byte* rec = (const_byte*)H.urec;                   // X masks << 4 of the U units of a trip: 16 bytes per trip
   // A trip = U units.  Table values and addresses come from L2 two trips ahead (ring of three register buffers, the
   // loop body is three trips so that the buffer indices are static).  The X masks of the next trip are requested into
   // the SAME scalar registers once the partner addresses of this trip are formed, and land while its LDS reads are in
   // flight (scalar and LDS loads share one counter: requested earlier, a wait for a record would also wait for LDS
-  // reads).
+  // reads).  The arrays end with kUnitAhead zero units (ham_layout.h: unit_arrays), so the last trips prefetch like
+  // every other one and the three offsets - table bytes and address bytes of the trip two ahead, record bytes of the
+  // next trip - just step by constants: nothing is clamped, divided or multiplied per trip.
+  static_assert(kUnitAhead == 2 * kUnitTrip, "the loop prefetches two trips beyond the one it accumulates");
   double d[3][U];
   u32x4_t ad[3];
-  u32x4_t X = rec[0];
+  u32x4_t X = *(const const_u32x4*)rec;
   const uint32_t tid32 = tid << 5;      // the thread's U table values of a trip are 32 contiguous bytes
   const uint32_t tid16 = tid << 4;      // ... and its U addresses 16
-  auto load_trip = [&](double (&dst)[U], u32x4_t& adst, uint32_t first_unit) {
-    const uint32_t trip = first_unit / U;
-    const v4i_t av = __builtin_amdgcn_raw_buffer_load_b128(ra, (int)tid16, (int)(trip * TRIP_ABYTES), 0);
+  auto load_trip = [&](double (&dst)[U], u32x4_t& adst, uint32_t soff_a, uint32_t soff_t) {
+    const v4i_t av = __builtin_amdgcn_raw_buffer_load_b128(ra, (int)tid16, (int)soff_a, 0);
     adst = u32x4_t{(uint32_t)av.x, (uint32_t)av.y, (uint32_t)av.z, (uint32_t)av.w};
-    const uint32_t soff = trip * TRIP_BYTES;
-    const double2 lo = buf_load_d2(ru, tid32, soff), hi = buf_load_d2(ru, tid32 + 16u, soff);
+    const double2 lo = buf_load_d2(ru, tid32, soff_t), hi = buf_load_d2(ru, tid32 + 16u, soff_t);
     dst[0] = lo.x; dst[1] = lo.y; dst[2] = hi.x; dst[3] = hi.y;
   };
-  load_trip(d[0], ad[0], 0u);
-  load_trip(d[1], ad[1], (uint32_t)(U < nu ? U : 0));
-  const int last = nu - U;       // first unit of the last trip
-  for (int u = 0; u < nu; u += 3 * U) {
+  load_trip(d[0], ad[0], 0u, 0u);
+  load_trip(d[1], ad[1], TRIP_ABYTES, TRIP_BYTES);     // (n_units is a positive multiple of kUnitUnroll: trip 1 exists)
+  uint32_t st = 2u * TRIP_BYTES, sa = 2u * TRIP_ABYTES, sr = 16u;
+  const uint32_t st_end = ((uint32_t)nu / U + 2u) * TRIP_BYTES;     // st once the last trip is accumulated
+  do {
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-      const int ub = u + k * U;
-      const int u1 = ub + U < last ? ub + U : last;             // (past the end: re-read the last trip)
-      const int u2 = ub + 2 * U < last ? ub + 2 * U : last;
-      double2 pa[U], pb[U];
+      d2v_t pa[U], pb[U];
       uint32_t a[U], ax[U];
 #pragma unroll
       for (int j = 0; j < U; ++j) {
@@ -1294,21 +1313,30 @@ __device__ __forceinline__ void unit_energy(const Lds& L, const HamDev& H, doubl
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int j = 0; j < U; ++j) {
-        pb[j] = lds_load_abs(a[j]);
-        pa[j] = lds_load_abs(ax[j]);
+        unit_lds_read(pb[j], a[j]);
+        unit_lds_read(pa[j], ax[j]);
       }
-      load_trip(d[(k + 2) % 3], ad[(k + 2) % 3], (uint32_t)u2);
+      load_trip(d[(k + 2) % 3], ad[(k + 2) % 3], sa, st);
       __builtin_amdgcn_sched_barrier(0);
-      X = rec[u1 / U];
+      X = *(const const_u32x4*)(rec + sr);
+      st += TRIP_BYTES; sa += TRIP_ABYTES; sr += 16u;
       __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int j = 0; j < U; ++j) {
-        const double v = (pa[j].x * pb[j].x + pa[j].y * pb[j].y) * d[k][j];
-        if (j & 1) acc1 += v; else acc0 += v;
-      }
+      // 8 LDS reads and the record load are outstanding on one counter.  LDS reads return in order, the record at any
+      // time: once at most 6 operations are outstanding the first two reads are in, at 4 the first four, and so on.
+      unit_wait<6>(pb[0], pa[0]);
+      unit_fma(acc0, pa[0], pb[0], d[k][0]);
+      __builtin_amdgcn_sched_barrier(0);
+      unit_wait<4>(pb[1], pa[1]);
+      unit_fma(acc1, pa[1], pb[1], d[k][1]);
+      __builtin_amdgcn_sched_barrier(0);
+      unit_wait<2>(pb[2], pa[2]);
+      unit_fma(acc0, pa[2], pb[2], d[k][2]);
+      __builtin_amdgcn_sched_barrier(0);
+      unit_wait<0>(pb[3], pa[3]);
+      unit_fma(acc1, pa[3], pb[3], d[k][3]);
       __builtin_amdgcn_sched_barrier(0);
     }
-  }
+  } while (st < st_end);
 }
 
 // Register path (n >= 10).  The state arrives in LDS in canonical order p' = tid | r << LT; each

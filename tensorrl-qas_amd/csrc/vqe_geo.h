@@ -102,6 +102,9 @@ VQE_HD inline uint32_t swz_slot(uint64_t swz, uint32_t p) {
 constexpr int kUnitMinQubits = 8;             // below: a group has no more pairs than a workgroup has threads
 constexpr int kUnitTrip = 4;                  // units per trip of the unit loop
 constexpr int kUnitUnroll = 3 * kUnitTrip;    // HamDev::n_units is padded to a multiple of this (three trips per turn of the loop)
+// The loop prefetches two trips beyond the one it accumulates: the arrays it reads (ham_layout.h: unit_arrays) end
+// with this many zero units, so that the last turns prefetch without clamping their offsets
+constexpr int kUnitAhead = 2 * kUnitTrip;
 // Sign-sum entries below kUnitZeroTol x sum_k |c_k| are rounding residues of sums that cancel exactly in real
 // arithmetic (3w - w - w - w is not 0 in floating point) and count as zero.
 constexpr double kUnitZeroTol = 0x1p-44;       // 5.7e-14 relative: far above the residues (~1e-16), far below any term

@@ -238,7 +238,8 @@ int vqe_noise_kraus_info(vqe_t* h, int32_t out[2]);
  * COBYLA, env-step), mode 1 (serial, batched, gradient and L-BFGS under vqe_set_dm_grad) and the quantum-jump runs of
  * vqe_set_kraus_traj for a slot without an override, through the Kraus set sqrt(w_0) 1, sqrt(w_k) P_k in the order
  * k = a + 4 b.  A Kraus override on a slot wins over the table, as it wins over p1 / p2.  Mode 0 gradients and L-BFGS
- * stay refused while a table has a positive total, as for depolarising noise.  Term-sharded handles serve the tables.
+ * stay refused while a table has a positive total, as for depolarising noise, unless vqe_set_noise_grad switched the
+ * gradients of frozen realisations on.  Term-sharded handles serve the tables.
  * The call touches neither the seed, the evaluation counter, p1 / p2, a Kraus override nor the results of the resident
  * batch; a later vqe_set_noise does not remove a table; the counter rules of vqe_set_noise hold unchanged.
  * VQE_EINVAL, handle unchanged, for a NaN, an entry outside [0, 1] or a total above 1 + 1e-12; VQE_ESTATE on an
@@ -246,6 +247,33 @@ int vqe_noise_kraus_info(vqe_t* h, int32_t out[2]);
 int vqe_set_noise_pauli(vqe_t* h, const double* w1 /* 3, or NULL */, const double* w2 /* 15, or NULL */);
 /* out[0], out[1]: 1 where a table is installed in the one- / two-qubit slot, else 0 */
 int vqe_noise_pauli_info(vqe_t* h, int32_t out[2]);
+/* Mode 0 Pauli noise: adjoint gradient and device L-BFGS on frozen draws (csrc/vqe_grad.h).
+ * n_real = T, 0 <= T <= 4096.  T = 0 is off, which is the default.  It is refused on an amplitude-sharded handle with
+ * VQE_ESTATE.  That matches vqe_set_noise_pauli.
+ * While on, with mode 0 and Pauli noise installed (depolarising p1 / p2 or a vqe_set_noise_pauli table), the gradient and
+ * L-BFGS entry points are served at n <= 13 instead of refused.  The value they differentiate is
+ *   E_T(theta) = (1/T) sum_{t=0}^{T-1} E(theta; draws of (seed, stream b, evaluation id eval_base + t)),
+ * summed in ascending t.  The draws are exactly those that vqe_batch_run_energy uses for evaluation id eval_base + t of
+ * batch position b.  Noise gates are numbered by position in the executed gate list.  The gradient is
+ * (1/T) sum_t dE/dtheta in the same order.  The result has the same bits for the same (seed, eval_base, batch position, T).
+ * The counter:
+ *  - vqe_energy_grad_batch / vqe_batch_run_energy_grad: eval_base += T after the run.  With hold != 0 the counter stays,
+ *    and vqe_noise_grad_advance adds T.  A host optimiser then sees one deterministic function per run.
+ *  - vqe_minimize_lbfgs / vqe_batch_run_minimize_lbfgs: every evaluation of the run uses the same T realisations.
+ *    Afterwards eval_base += T, whatever hold is.
+ *  - vqe_batch_run_env_step_lbfgs: the optimisation runs on the pre-action circuit with the T realisations.  The one
+ *    closing energy of the full circuit is a single trajectory with id eval_base + T (the COBYLA env-step also reports
+ *    one draw there).  Afterwards eval_base += T + 1.
+ * Still refused, with the codes they had: shot noise, Kraus sets without a Pauli form and vqe_set_kraus_traj runs (their
+ * probabilities depend on theta), n >= 14, L-BFGS on a term shard.  A term-sharded handle gets its partial E_T and its
+ * partial gradient, as without noise; every rank draws the same errors.  A refused call changes nothing.
+ * With the switch off, every call answers as before.  With the switch on and p1 = p2 = 0 and no table, the noiseless
+ * kernels run and their bits are unchanged.  VQE_EINVAL, handle unchanged, for T outside [0, 4096]. */
+int vqe_set_noise_grad(vqe_t* h, int n_real, int hold);
+/* eval_base += T (the T of vqe_set_noise_grad; nothing with the switch off) */
+int vqe_noise_grad_advance(vqe_t* h);
+/* out[0] T, [1] hold, [2] the current eval_base, [3] 0 */
+int vqe_noise_grad_info(vqe_t* h, int64_t out[4]);
 /* Mode 0 under a Kraus override (vqe_set_noise_kraus): evaluate an energy as the mean of n_traj quantum-jump
  * trajectories.  0 (default): those runs are refused with VQE_ESTATE as before.  1 .. 4096.  Accepted on any handle;
  * takes effect in mode 0 while an override is installed, 1 <= n <= 13, unsharded handles.  Touches neither seed,

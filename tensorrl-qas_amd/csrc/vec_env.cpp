@@ -449,11 +449,15 @@ int vqe_vecenv_set_optimizer(vqe_vecenv_t* v, int kind, const vqe_lbfgs_opts_t* 
   if (kind != VQE_ENV_OPT_COBYLA && kind != VQE_ENV_OPT_LBFGS) return fail(v, VQE_EINVAL, "unknown optimiser kind");
   if (v->pending) return fail(v, VQE_ESTATE, "set_optimizer between step_begin and step_end");
   if (kind == VQE_ENV_OPT_LBFGS) {
-    // a noisy batch has gradients in the engine's exact channel mode only (there the engine checks its own switches,
-    // vqe_set_dm_batched and vqe_set_dm_grad, at every step)
+    // a noisy batch has gradients in the engine's exact channel mode (there the engine checks its own switches,
+    // vqe_set_dm_batched and vqe_set_dm_grad, at every step) or, on Pauli trajectories, on frozen realisations
+    // (vqe_set_noise_grad; what else it needs the engine checks at every step as well)
     int32_t mode[2] = {0, 0};
-    if (v->cfg.noisy && (vqe_noise_mode_info(v->eng, mode) != VQE_OK || mode[0] != 1))
-      return fail(v, VQE_ESTATE, "the device L-BFGS takes no noisy batch on Pauli trajectories (exact channel mode: vqe_set_noise_mode 1)");
+    int64_t ng[4] = {0, 0, 0, 0};
+    if (v->cfg.noisy && (vqe_noise_mode_info(v->eng, mode) != VQE_OK || mode[0] != 1) &&
+        (vqe_noise_grad_info(v->eng, ng) != VQE_OK || ng[0] < 1))
+      return fail(v, VQE_ESTATE, "the device L-BFGS takes no noisy batch on Pauli trajectories (exact channel mode: vqe_set_noise_mode 1, "
+                                 "or frozen realisations: vqe_set_noise_grad)");
     if (!opts) return fail(v, VQE_EINVAL, "VQE_ENV_OPT_LBFGS needs its options");
     v->lbfgs = *opts;
   }

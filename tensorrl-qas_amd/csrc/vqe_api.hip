@@ -16,6 +16,7 @@
 #include "ham_layout.h"
 #include "dm_host.h"
 #include "env_step_host.h"
+#include "noise_grad_host.h"
 
 #include <algorithm>
 #include <cassert>
@@ -95,6 +96,7 @@ struct vqe_handle {
   int batch = 0;
   int64_t total_params = 0;
   int max_ops = 0, max_params = 0, max_pair = 0;
+  int max_rot = 0;       // most ops WITH a parameter in a circuit of the batch (rows of the noisy adjoint kernels' gacc)
   std::vector<int64_t> h_par_begin;
   std::vector<int32_t> h_par_count;
   DevBuf<GateRec> d_gates;
@@ -176,6 +178,10 @@ struct vqe_handle {
   // quantum-jump trajectories of a Kraus override in mode 0 (vqe_set_kraus_traj, vqe_qjump.h): the count (0: refused as
   // before), the channel tables of the two slots (made again when the override or p1 / p2 change: qj_ver), per-trajectory
   // energies and jump counts of the last evaluation, per-circuit jump sums
+  // gradients of frozen Pauli-noise realisations in mode 0 (vqe_set_noise_grad): T (0: refused as before)
+  // and whether a gradient run leaves eval_base where it is (a host optimiser's one deterministic function)
+  int noise_grad_T = 0;
+  bool noise_grad_hold = false;
   int kraus_traj = 0;
   uint64_t qj_ver = 0, qj_tab_ver = ~0ull;
   DevBuf<double> qj_K1, qj_W1, qj_K2, qj_W2, qj_e;
@@ -441,7 +447,7 @@ int load_batch(vqe_t* h, int batch, const std::vector<GateRec>& gates,
                const double* theta0, int64_t total_params) {
   std::vector<int64_t> sbeg(batch);
   int64_t stot = 0;
-  int max_ops = 1, max_par = 1, max_pair = 0;
+  int max_ops = 1, max_par = 1, max_pair = 0, max_rot = 1;
   std::vector<double> cost(batch);
   for (int b = 0; b < batch; ++b) {
     sbeg[b] = stot;
@@ -455,12 +461,14 @@ int load_batch(vqe_t* h, int batch, const std::vector<GateRec>& gates,
     stot += (int64_t)sdoubles;
     stot = (stot + 15) & ~(int64_t)15;  // 128-byte alignment: rows of the optimiser's global arrays are whole sectors / lines
     max_par = std::max(max_par, (int)pcnt[b]);
-    int ops = 0, pair = 0;
+    int ops = 0, pair = 0, rot = 0;
     for (int64_t i = gbeg[b]; i < gbeg[b] + gcnt[b]; ++i) {
       const int k = gates[i].kind;
       ops += (k == G_CNOT) ? 0 : (k == G_DEPOL2 ? 2 : 1);
       pair += (k == G_RX || k == G_RY || k == G_RXX || k == G_RYY) ? 1 : 0;
+      rot += gate_is_rot(k) ? 1 : 0;
     }
+    max_rot = std::max(max_rot, rot);
     max_ops = std::max(max_ops, ops);
     max_pair = std::max(max_pair, pair);
     // expected cycles of one evaluation of the fused kernel beyond the constant energy step:
@@ -494,6 +502,7 @@ int load_batch(vqe_t* h, int batch, const std::vector<GateRec>& gates,
   h->max_ops = (max_ops + 3) & ~3;
   h->max_pair = std::min(h->max_ops, (max_pair + 3) & ~3);
   h->max_params = (max_par + 3) & ~3;
+  h->max_rot = max_rot;
   h->h_par_begin = pbeg;
   h->h_par_count = pcnt;
   h->h_gate_count = gcnt;
@@ -1491,7 +1500,15 @@ int build_grad_tables(vqe_t* h) {
 // What the adjoint kernels cannot serve: a gradient of a stochastic trajectory is of no use to an optimiser, and the
 // streaming path (n >= 14) computes gradients only after vqe_set_stream_grad (a second state-sized buffer per stream).
 // Checked before anything is loaded, so a refused call leaves the handle as it was.
+// noise_grad_on: the run is the mean over frozen Pauli-noise realisations (after grad_state_refusal let it through).
 // (grad_state_refusal: everything but the path test - the device L-BFGS has a switch of its own for n >= 14)
+NoiseGradVerdict noise_grad_state(const vqe_t* h) {
+  return noise_grad_verdict(NoiseGradState{h->noise_grad_T, h->noise_mode, pauli_noise_on(h), h->lds_path});
+}
+bool noise_grad_on(const vqe_t* h) { return noise_grad_state(h) == NG_SERVED; }
+NoiseGrad noise_grad_args(const vqe_t* h) {
+  return noise_grad_on(h) ? NoiseGrad{h->noise_grad_T, std::max(1, h->max_rot)} : NoiseGrad{0, -1};
+}
 int grad_state_refusal(vqe_t* h) {
   if (h->noise_mode == 1 && h->dm_grad) {
     // the exact channel mode after vqe_set_dm_grad: deterministic energies whatever p1 / p2, no shot noise in this mode;
@@ -1503,8 +1520,15 @@ int grad_state_refusal(vqe_t* h) {
     return VQE_OK;
   }
   VQE_TRY(kraus_refusal(h, false));
-  if (pauli_noise_on(h))
-    return fail(h, VQE_ESTATE, "energy gradients of Pauli-noise trajectories are refused (set p1 = p2 = 0)");
+  // frozen realisations (vqe_set_noise_grad, noise_grad_host.h): served in mode 0 on the LDS-resident path; shot noise
+  // and shards are refused below as without noise
+  const NoiseGradVerdict ng = noise_grad_state(h);
+  if (ng == NG_REFUSED_OFF)
+    return fail(h, VQE_ESTATE, "energy gradients of Pauli-noise trajectories are refused (set p1 = p2 = 0, or in noise mode 0 "
+                               "freeze the draws: vqe_set_noise_grad)");
+  if (ng == NG_REFUSED_PATH)
+    return fail(h, VQE_ESTATE, "energy gradients of Pauli-noise trajectories (vqe_set_noise_grad) are computed for "
+                               "n_qubits <= 13 (LDS-resident path) only");
   if (h->noise_mode == 1) return fail(h, VQE_ESTATE, "energy gradients are not available in the exact channel noise mode");
   if (h->noise.shot_sigma != 0.0) return fail(h, VQE_ESTATE, "energy gradients with shot noise are refused (set sigma_total = 0)");
   if (h->amp_world > 1) return fail(h, VQE_ESTATE, "energy gradients of an amplitude shard are refused");
@@ -1522,16 +1546,17 @@ int grad_refusal(vqe_t* h) {
 // (A, gham, x, lambda scratch) and size their LDS by a formula of grad_lds_bytes' form.  lambda lives in the LDS unless
 // N >= 13 or psi + lambda + ops exceed it; in global memory it is one slice per workgroup of a persistent grid.
 // prepare(grid, x): what the caller has to size by the chosen grid (a hipError_t).
+// ng: {T, rows of gacc} of the NOISY instances (the caller passes those kernels), {0, -1} for the noiseless ones.
 template <int N, class X, class Prepare>
-int launch_adjoint(vqe_t* h, const BatchArgs& A, size_t (*lds_bytes)(int, bool, int, int, int),
-                   void (*k_global)(BatchArgs, GradHam, X, double2*), void (*k_lds)(BatchArgs, GradHam, X, double2*),
+int launch_adjoint(vqe_t* h, const BatchArgs& A, NoiseGrad ng, size_t (*lds_bytes)(int, bool, int, int, int, int),
+                   void (*k_global)(BatchArgs, GradHam, X, double2*, NoiseGrad), void (*k_lds)(BatchArgs, GradHam, X, double2*, NoiseGrad),
                    const char* too_large, X x, Prepare prepare) {
   constexpr int NW = Geo<N>::NW;
   bool lam_global = N >= 13;
-  size_t lds = lds_bytes(N, lam_global, A.max_ops, A.max_params, NW);
+  size_t lds = lds_bytes(N, lam_global, A.max_ops, A.max_params, NW, ng.rows);
   if (!lam_global && lds > (size_t)h->lds_per_cu) {      // psi + lambda + ops do not fit: lambda moves to global memory
     lam_global = true;
-    lds = lds_bytes(N, true, A.max_ops, A.max_params, NW);
+    lds = lds_bytes(N, true, A.max_ops, A.max_params, NW, ng.rows);
   }
   if (lds > (size_t)h->lds_per_cu) return fail(h, VQE_EINVAL, too_large);
   const int wg_per_cu = std::max(1, (int)(h->lds_per_cu / lds));
@@ -1545,7 +1570,7 @@ int launch_adjoint(vqe_t* h, const BatchArgs& A, size_t (*lds_bytes)(int, bool, 
   }
   HIP_TRY(h, prepare(grid, x));
   HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(Geo<N>::NT), lds, h->stream, A, h->gham, x, lam_global ? h->g_lam.p : (double2*)nullptr);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(Geo<N>::NT), lds, h->stream, A, h->gham, x, lam_global ? h->g_lam.p : (double2*)nullptr, ng);
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
   return VQE_OK;
@@ -1553,9 +1578,14 @@ int launch_adjoint(vqe_t* h, const BatchArgs& A, size_t (*lds_bytes)(int, bool, 
 
 template <int N>
 int launch_grad(vqe_t* h, const BatchArgs& A) {
-  return launch_adjoint<N>(h, A, grad_lds_bytes, k_lds_energy_grad<N, true>, k_lds_energy_grad<N, false>,
-                           "circuit too large for the adjoint gradient kernel (gates + parameters)", h->d_grad.p,
-                           [](int, double*) { return hipSuccess; });
+  const NoiseGrad ng = noise_grad_args(h);
+  const char* too_large = "circuit too large for the adjoint gradient kernel (gates + parameters)";
+  const auto prepare = [](int, double*) { return hipSuccess; };
+  if (ng.rows >= 0)
+    return launch_adjoint<N>(h, A, ng, grad_lds_bytes, k_lds_energy_grad<N, true, true>, k_lds_energy_grad<N, false, true>,
+                             too_large, h->d_grad.p, prepare);
+  return launch_adjoint<N>(h, A, ng, grad_lds_bytes, k_lds_energy_grad<N, true, false>, k_lds_energy_grad<N, false, false>,
+                           too_large, h->d_grad.p, prepare);
 }
 
 // Streaming path (n >= 14, vqe_set_stream_grad): forward sweeps, lambda = H psi, backward sweeps (vqe_stream_grad.h)
@@ -1577,8 +1607,11 @@ int run_grad(vqe_t* h) {
   h->last_run_dm = false;
   h->qj_traj_batch = 0;
   if (!h->lds_path) return stream_grad(h, A);
-  return dispatch_n(h, "energy gradients are computed for n_qubits <= 13 (LDS-resident path) only",
-                    [&](auto n) -> int { return launch_grad<decltype(n)::value>(h, A); }, LdsSizes{});
+  VQE_TRY(dispatch_n(h, "energy gradients are computed for n_qubits <= 13 (LDS-resident path) only",
+                     [&](auto n) -> int { return launch_grad<decltype(n)::value>(h, A); }, LdsSizes{}));
+  // frozen realisations: the launch read ids eval_base .. eval_base + T - 1 (a held counter waits for vqe_noise_grad_advance)
+  if (noise_grad_on(h)) h->noise.eval_base += noise_grad_consumed(NoiseGradRun::Gradient, h->noise_grad_T, h->noise_grad_hold);
+  return VQE_OK;
 }
 
 // ---- device L-BFGS (vqe_lbfgs.h) -------------------------------------------------------------
@@ -1604,13 +1637,18 @@ int lbfgs_check(vqe_t* h, const vqe_lbfgs_opts_t* opts, vqe_lbfgs_opts_t* o) {
 
 template <int N>
 int launch_lbfgs(vqe_t* h, const BatchArgs& A, const LbfgsArgs& O) {
-  return launch_adjoint<N>(h, A, lbfgs_lds_bytes, k_lds_minimize_lbfgs<N, true>, k_lds_minimize_lbfgs<N, false>,
-                           "circuit too large for the device L-BFGS kernel (gates + parameters)", O,
-                           [&](int grid, LbfgsArgs& o) {      // the optimiser's vectors: one slice per workgroup
-                             const hipError_t e = h->lb_work.reserve((size_t)grid * lbfgs_work_doubles(A.max_params, o.m));
-                             o.work = h->lb_work.p;
-                             return e;
-                           });
+  const NoiseGrad ng = noise_grad_args(h);
+  const char* too_large = "circuit too large for the device L-BFGS kernel (gates + parameters)";
+  const auto prepare = [&](int grid, LbfgsArgs& o) {      // the optimiser's vectors: one slice per workgroup
+    const hipError_t e = h->lb_work.reserve((size_t)grid * lbfgs_work_doubles(A.max_params, o.m));
+    o.work = h->lb_work.p;
+    return e;
+  };
+  if (ng.rows >= 0)
+    return launch_adjoint<N>(h, A, ng, lbfgs_lds_bytes, k_lds_minimize_lbfgs<N, true, true>, k_lds_minimize_lbfgs<N, false, true>,
+                             too_large, O, prepare);
+  return launch_adjoint<N>(h, A, ng, lbfgs_lds_bytes, k_lds_minimize_lbfgs<N, true, false>, k_lds_minimize_lbfgs<N, false, false>,
+                           too_large, O, prepare);
 }
 
 // The device L-BFGS of all resident streams in lock-step (vqe_stream_lbfgs.h) through lockstep_run: an evaluation is
@@ -1678,6 +1716,9 @@ int run_lbfgs(vqe_t* h, bool env_step, const vqe_lbfgs_opts_t& o) {
   VQE_TRY(dispatch_n(h, "the device L-BFGS serves n_qubits <= 13 (LDS-resident path) only",
                      [&](auto n) -> int { return launch_lbfgs<decltype(n)::value>(h, A, O); }, LdsSizes{}));
   h->lb_batch = h->batch;
+  // frozen realisations: every evaluation read ids eval_base .. eval_base + T - 1, an env-step's closing energy id eval_base + T
+  if (noise_grad_on(h))
+    h->noise.eval_base += noise_grad_consumed(env_step ? NoiseGradRun::EnvStepLbfgs : NoiseGradRun::Lbfgs, h->noise_grad_T, h->noise_grad_hold);
   return VQE_OK;
 }
 
@@ -2142,6 +2183,30 @@ int vqe_set_noise_pauli(vqe_t* h, const double* w1, const double* w2) {
   set_channels(h);
   ++h->gen;      // the plans and channel tables of the resident batch are made again
   ++h->qj_ver;
+  return VQE_OK;
+}
+
+int vqe_set_noise_grad(vqe_t* h, int n_real, int hold) {
+  if (!h) return VQE_EINVAL;
+  if (n_real < 0 || n_real > kNoiseGradMaxReal) return fail(h, VQE_EINVAL, "vqe_set_noise_grad: n_real must be in [0, 4096]");
+  if (h->amp_world > 1) return fail(h, VQE_ESTATE, "gradients of frozen noise realisations (vqe_set_noise_grad) take no amplitude-sharded handle");
+  h->noise_grad_T = n_real;
+  h->noise_grad_hold = hold != 0;
+  return VQE_OK;
+}
+
+int vqe_noise_grad_advance(vqe_t* h) {
+  if (!h) return VQE_EINVAL;
+  h->noise.eval_base += (uint64_t)h->noise_grad_T;
+  return VQE_OK;
+}
+
+int vqe_noise_grad_info(vqe_t* h, int64_t out[4]) {
+  if (!h || !out) return VQE_EINVAL;
+  out[0] = h->noise_grad_T;
+  out[1] = h->noise_grad_hold ? 1 : 0;
+  out[2] = (int64_t)h->noise.eval_base;
+  out[3] = 0;
   return VQE_OK;
 }
 

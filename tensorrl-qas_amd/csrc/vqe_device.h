@@ -673,7 +673,9 @@ __device__ __forceinline__ void compile_ops(const BatchArgs& A, int b, uint64_t 
 // is numbered by its position in the circuit that is actually executed, so a stochastic COBYLA
 // phase is exactly a run on the pre-action gate list (reference scipy_optim builds its circuit
 // from the pre-action state: environment_qulacs_TN_notin_agent_noise.py:372-380).
-template <int N>
+// RAW: the executed list is the unscheduled L.ops at every N and record k sits at position k (the adjoint kernels of
+// vqe_grad.h, which run no schedule and carve no L.sidx); the draws and the walk are the same code.
+template <int N, bool RAW = false>
 __device__ __forceinline__ void patch_noise_wave(const BatchArgs& A, int b, uint64_t eval_id, const Lds& L, int skip,
                                                  bool canonical, int lane, int skip_end) {
   // One wave.  Lane l holds gate base+l and draws its Pauli error; everything that does not depend
@@ -683,7 +685,8 @@ __device__ __forceinline__ void patch_noise_wave(const BatchArgs& A, int b, uint
   const int G = A.gate_count[b];
   const int4* gsrc = (const int4*)(A.gates + A.gate_begin[b]);
   {
-    Op* exe = N >= 10 ? L.sched : L.ops;
+    constexpr bool kSched = N >= 10 && !RAW;
+    Op* exe = kSched ? L.sched : L.ops;
     const int kmax = L.meta[0];
     const uint64_t lt_mask = lane ? (~0ull >> (64 - lane)) : 0ull;
     const uint64_t nkey = noise_key(A.noise.seed, (uint64_t)b, eval_id);
@@ -739,7 +742,8 @@ __device__ __forceinline__ void patch_noise_wave(const BatchArgs& A, int b, uint
       }
       auto apply = [&](int pk, int sign, int pauli) {   // pauli < 0: a rotation, kind stays
         if (pk < kmax) {
-          Op* o = exe + L.sidx[pk];
+          Op* o;
+          if constexpr (RAW) o = exe + pk; else o = exe + L.sidx[pk];
           int kd = o->kind;
           if (pauli >= 0) kd = (kd & ~0xff) | ((pauli == 2 || pauli == 3) ? OP_PZ : OP_NOP);
           o->kind = (kd & ~0x100) | (sign << 8);
@@ -751,7 +755,7 @@ __device__ __forceinline__ void patch_noise_wave(const BatchArgs& A, int b, uint
     {
       // jump counts for the run loop: every record learns how many inactive slots follow it (walked from the
       // end in chunks of 64 records, `lead` = inactive records at the head of the chunk behind)
-      const int ns = N >= 10 ? L.meta[4] : kmax;
+      const int ns = kSched ? L.meta[4] : kmax;
       int lead = 0;
       for (int base = ((ns - 1) / 64) * 64; base >= 0; base -= 64) {
         const int k = base + lane;
@@ -768,7 +772,7 @@ __device__ __forceinline__ void patch_noise_wave(const BatchArgs& A, int b, uint
     }
     if (lane == 0) {
       uint32_t cs = c;
-      if (N >= 10 && canonical) {
+      if (kSched && canonical) {
         cs = 0;
         for (int q = 0; q < N; ++q) cs |= (uint32_t)parity32(A.ham.mrow[q] & c) << q;
       }
@@ -781,10 +785,10 @@ __device__ __forceinline__ void patch_noise_wave(const BatchArgs& A, int b, uint
 }
 
 // ... by wave 0 of the workgroup, followed by a barrier.
-template <int N>
+template <int N, bool RAW = false>
 __device__ __forceinline__ void patch_noise(const BatchArgs& A, int b, uint64_t eval_id, const Lds& L, int skip,
                                             bool canonical, int skip_end = 0) {
-  if (threadIdx.x < 64) patch_noise_wave<N>(A, b, eval_id, L, skip, canonical, (int)threadIdx.x, skip_end);
+  if (threadIdx.x < 64) patch_noise_wave<N, RAW>(A, b, eval_id, L, skip, canonical, (int)threadIdx.x, skip_end);
   __syncthreads();
 }
 

@@ -17,6 +17,10 @@
 // lambda[p0 ^ x] += T psi[p0], lambda[p0] += conj(T) psi[p0 ^ x].
 // LAM_GLOBAL: lambda lives in a per-workgroup slice of a global scratch buffer (n = 13, where psi alone takes 128 KiB
 // of LDS, or whenever psi + lambda + the op list do not fit beside each other); the grid is then persistent.
+// NOISY (vqe_set_noise_grad): the mean over T frozen Pauli-noise realisations.  The ops are compiled once
+// per circuit with their noise slots (compile_ops, slots = true); the workgroup then loops over t = 0 .. T-1: the patch
+// of evaluation id eval_base + t (patch_noise<N, true>, the draws of the energy path), the body above, E and the
+// per-parameter sums added in ascending t and divided once.  The noiseless instances carry none of this.
 #pragma once
 #include "vqe_device.h"
 
@@ -30,11 +34,15 @@ struct GradHam {
   const double* tab;
 };
 
-__host__ __device__ inline size_t grad_lds_bytes(int n, bool lam_global, int max_ops, int max_params, int nw) {
+// What the NOISY instances take beside the arguments of the noiseless ones: T, and the rows of gacc - the largest number
+// of ops WITH a parameter in a circuit of the batch (the noise slots take none).  rows < 0: noiseless, a row per op.
+struct NoiseGrad { int n_real, rows; };
+
+__host__ __device__ inline size_t grad_lds_bytes(int n, bool lam_global, int max_ops, int max_params, int nw, int rows = -1) {
   size_t b = (size_t)16 << n;                                  // psi
   if (!lam_global) b += (size_t)16 << n;                       // lambda
   b += (size_t)16 * max_ops + (size_t)16 * max_params;         // ops, (cos, sin)
-  b += (((size_t)8 * max_ops * nw) + 15) & ~(size_t)15;        // per-wave partial gradients of every op
+  b += (((size_t)8 * (rows < 0 ? max_ops : rows) * nw) + 15) & ~(size_t)15;   // per-wave partial gradients of every op
   return b + 128 + 128 + 128 + 32;                             // red, xm, zm, meta
 }
 
@@ -42,9 +50,10 @@ __host__ __device__ inline size_t grad_lds_bytes(int n, bool lam_global, int max
 // forward sweep at theta[0..P), lambda = H psi, and - BACKWARD - the backward sweep and the per-parameter sums into
 // gdst[0..P).  Returns E in every thread.  k_lds_minimize_lbfgs (vqe_lbfgs.h) calls it once per trial point; its body is
 // vqe_grad_body.h, the text k_lds_energy_grad expands in place (see there for why that kernel does not call this).
-template <int N, bool LAM_GLOBAL, bool BACKWARD = true>
+// NOISY: ONE realisation - the ops carry its patch; nz_t of nz_T as vqe_grad_body.h states (adjoint_eval_mean loops).
+template <int N, bool LAM_GLOBAL, bool BACKWARD = true, bool NOISY = false>
 __device__ __forceinline__ double adjoint_eval(const BatchArgs& A, const GradHam& GH, const Lds& L, double2* lam, double* gacc,
-                                               const double* theta, int P, double* gdst) {
+                                               const double* theta, int P, double* gdst, int nz_t = 0, int nz_T = 1) {
   constexpr int NT = Geo<N>::NT;
   constexpr int NW = Geo<N>::NW;
   constexpr uint32_t DIM = 1u << N;
@@ -58,8 +67,24 @@ __device__ __forceinline__ double adjoint_eval(const BatchArgs& A, const GradHam
   return e;
 }
 
-template <int N, bool LAM_GLOBAL>
-__global__ void __launch_bounds__(Geo<N>::NT) k_lds_energy_grad(BatchArgs A, GradHam GH, double* grad, double2* lam_scratch) {
+// E_T and its gradient at theta: the mean over the realisations with evaluation ids id0 .. id0 + T - 1 of circuit b, whose
+// ops were compiled with slots and without the gates [skip, skip_end).  Every thread must have left the previous reader of
+// L.ops behind (the patch rewrites them): the barrier in front of the patch sees to it.
+template <int N, bool LAM_GLOBAL, bool BACKWARD = true>
+__device__ __forceinline__ double adjoint_eval_mean(const BatchArgs& A, const GradHam& GH, const Lds& L, double2* lam, double* gacc,
+                                                    const double* theta, int P, double* gdst, int b, uint64_t id0, int T, int skip,
+                                                    int skip_end) {
+  double esum = 0.0;
+  for (int t = 0; t < T; ++t) {
+    __syncthreads();
+    patch_noise<N, true>(A, b, id0 + (uint64_t)t, L, skip, false, skip_end);
+    esum += adjoint_eval<N, LAM_GLOBAL, BACKWARD, true>(A, GH, L, lam, gacc, theta, P, gdst, t, T);
+  }
+  return esum / (double)T;
+}
+
+template <int N, bool LAM_GLOBAL, bool NOISY = false>
+__global__ void __launch_bounds__(Geo<N>::NT) k_lds_energy_grad(BatchArgs A, GradHam GH, double* grad, double2* lam_scratch, NoiseGrad NG) {
   constexpr int NT = Geo<N>::NT;
   constexpr int NW = Geo<N>::NW;
   constexpr uint32_t DIM = 1u << N;
@@ -76,7 +101,7 @@ __global__ void __launch_bounds__(Geo<N>::NT) k_lds_energy_grad(BatchArgs A, Gra
   if (!LAM_GLOBAL) base += (size_t)16 << N;
   L.ops = (Op*)base; base += (size_t)16 * A.max_ops;
   L.cs = (double2*)base; base += (size_t)16 * A.max_params;
-  double* gacc = (double*)base; base += (((size_t)8 * A.max_ops * NW) + 15) & ~(size_t)15;
+  double* gacc = (double*)base; base += (((size_t)8 * (NOISY ? NG.rows : A.max_ops) * NW) + 15) & ~(size_t)15;
   L.red = (double*)base; base += 128;
   L.xm = (uint32_t*)base; base += 128;
   L.zm = (uint32_t*)base; base += 128;
@@ -87,11 +112,20 @@ __global__ void __launch_bounds__(Geo<N>::NT) k_lds_energy_grad(BatchArgs A, Gra
     double2* lam = LAM_GLOBAL ? lam_scratch + (size_t)blockIdx.x * DIM : lam_lds;
     const int P = A.par_count[b];
     const double* theta = A.theta + A.par_begin[b];
+    if constexpr (NOISY) {
+      compile_ops(A, b, 0, L, -1, true);
+      // (a call here: the noisy instance is bound by its T sweeps, not by the registers of <13, true>)
+      const double e = adjoint_eval_mean<N, LAM_GLOBAL>(A, GH, L, lam, gacc, theta, P, grad + A.par_begin[b], b,
+                                                        A.noise.eval_base, NG.n_real, -1, 0);
+      if (tid == 0) { A.fout[b] = e; if (A.nfev) A.nfev[b] = 1; }
+    } else {
+    constexpr int nz_t = 0, nz_T = 1;             // (names of the NOISY text of the body, which this branch discards)
     compile_ops(A, b, 0, L);                      // (stages the gate records in the psi region; ends with a barrier)
 #define ADJOINT_GRAD_DST(j) grad[A.par_begin[b] + j]
 #include "vqe_grad_body.h"
 #undef ADJOINT_GRAD_DST
     if (tid == 0) { A.fout[b] = e; if (A.nfev) A.nfev[b] = 1; }
+    }
     __syncthreads();                              // the LDS is reused by the next circuit of a persistent grid
   }
 }

@@ -40,8 +40,8 @@ __host__ __device__ inline size_t lbfgs_row(int max_params) { return ((size_t)ma
 __host__ __device__ inline size_t lbfgs_work_doubles(int max_params, int m) {
   return (5 + 2 * (size_t)m) * lbfgs_row(max_params);      // x, g, xt, gt, d, S[m], Y[m]
 }
-__host__ __device__ inline size_t lbfgs_lds_bytes(int n, bool lam_global, int max_ops, int max_params, int nw) {
-  return ((grad_lds_bytes(n, lam_global, max_ops, max_params, nw) + 15) & ~(size_t)15) + 512;   // + sy, yy, alpha [16] each, control words
+__host__ __device__ inline size_t lbfgs_lds_bytes(int n, bool lam_global, int max_ops, int max_params, int nw, int rows = -1) {
+  return ((grad_lds_bytes(n, lam_global, max_ops, max_params, nw, rows) + 15) & ~(size_t)15) + 512;   // + sy, yy, alpha [16] each, control words
 }
 
 // max over the wavefront, NaN wins (a NaN gradient must not pass the gtol test)
@@ -172,8 +172,11 @@ __device__ __forceinline__ bool lbfgs_tell(LbfgsState& state, const LbfgsArgs& O
   return stop;
 }
 
-template <int N, bool LAM_GLOBAL>
-__global__ void __launch_bounds__(Geo<N>::NT) k_lds_minimize_lbfgs(BatchArgs A, GradHam GH, LbfgsArgs O, double2* lam_scratch) {
+// NOISY (vqe_set_noise_grad): every trial point is the mean over the SAME T realisations (evaluation ids
+// eval_base .. eval_base + T - 1, adjoint_eval_mean), a deterministic function the line search is valid on; the closing
+// energy of an environment step is the single trajectory with id eval_base + T on the full circuit.  The update is untouched.
+template <int N, bool LAM_GLOBAL, bool NOISY = false>
+__global__ void __launch_bounds__(Geo<N>::NT) k_lds_minimize_lbfgs(BatchArgs A, GradHam GH, LbfgsArgs O, double2* lam_scratch, NoiseGrad NG) {
   constexpr int NT = Geo<N>::NT;
   constexpr int NW = Geo<N>::NW;
   constexpr uint32_t DIM = 1u << N;
@@ -187,13 +190,13 @@ __global__ void __launch_bounds__(Geo<N>::NT) k_lds_minimize_lbfgs(BatchArgs A, 
   if (!LAM_GLOBAL) base += (size_t)16 << N;
   L.ops = (Op*)base; base += (size_t)16 * A.max_ops;
   L.cs = (double2*)base; base += (size_t)16 * A.max_params;
-  double* gacc = (double*)base; base += (((size_t)8 * A.max_ops * NW) + 15) & ~(size_t)15;
+  double* gacc = (double*)base; base += (((size_t)8 * (NOISY ? NG.rows : A.max_ops) * NW) + 15) & ~(size_t)15;
   L.red = (double*)base; base += 128;
   L.xm = (uint32_t*)base; base += 128;
   L.zm = (uint32_t*)base; base += 128;
   L.meta = (int32_t*)base; base += 32;
   L.sched = L.ops;
-  base = smem + ((grad_lds_bytes(N, LAM_GLOBAL, A.max_ops, A.max_params, NW) + 15) & ~(size_t)15);
+  base = smem + ((grad_lds_bytes(N, LAM_GLOBAL, A.max_ops, A.max_params, NW, NOISY ? NG.rows : -1) + 15) & ~(size_t)15);
   double* sy = (double*)base;                    // [16] s.y of the pair in each slot
   double* yy = sy + kLbfgsMaxHistory;            // [16] y.y
   double* alpha = yy + kLbfgsMaxHistory;         // [16] two-loop recursion
@@ -219,13 +222,17 @@ __global__ void __launch_bounds__(Geo<N>::NT) k_lds_minimize_lbfgs(BatchArgs A, 
     // environment step: the optimiser sees the pre-action circuit (pre_action, vqe_geo.h); the new gate's angle stays in
     // x at its theta0 value and has gradient 0
     const PreAction pa = pre_action(A.gates + A.gate_begin[b], A.gate_count[b], A.new_gate ? A.new_gate[b] : -1);
-    compile_ops(A, b, 0, L, pa.skip, false, pa.skip_end);
+    compile_ops(A, b, 0, L, pa.skip, NOISY, pa.skip_end);
     for (int j = (int)tid; j < P; j += NT) xt[j] = theta0[j];
     __syncthreads();
     // wave 0 only (the other waves count the evaluations and never read the rest)
     LbfgsState st = lbfgs_start();
     for (;;) {
-      const double e = adjoint_eval<N, LAM_GLOBAL, true>(A, GH, L, lam, gacc, xt, P, gt);
+      double e;
+      if constexpr (NOISY)
+        e = adjoint_eval_mean<N, LAM_GLOBAL, true>(A, GH, L, lam, gacc, xt, P, gt, b, A.noise.eval_base, NG.n_real, pa.skip, pa.skip_end);
+      else
+        e = adjoint_eval<N, LAM_GLOBAL, true>(A, GH, L, lam, gacc, xt, P, gt);
       ++st.nfev;
       if (pa.hole >= 0 && (int)tid == pa.hole % NT) gt[pa.hole] = 0.0;    // (the thread that stored it in adjoint_eval)
       if (A.trace && st.nfev <= A.maxfun) {   // diagnostic: the trial point (optimised parameters only) and its value
@@ -251,8 +258,14 @@ __global__ void __launch_bounds__(Geo<N>::NT) k_lds_minimize_lbfgs(BatchArgs A, 
     if (A.env_step) {
       // CircuitEnv.step: float32 round trip, then the energy of the FULL circuit (no gradient wanted)
       __syncthreads();                     // xout complete
-      compile_ops(A, b, 0, L);
-      fret = adjoint_eval<N, LAM_GLOBAL, false>(A, GH, L, lam, gacc, A.xout + p0, P, gt);
+      if constexpr (NOISY) {
+        compile_ops(A, b, 0, L, -1, true);
+        fret = adjoint_eval_mean<N, LAM_GLOBAL, false>(A, GH, L, lam, gacc, A.xout + p0, P, gt, b,
+                                                       A.noise.eval_base + (uint64_t)NG.n_real, 1, -1, 0);
+      } else {
+        compile_ops(A, b, 0, L);
+        fret = adjoint_eval<N, LAM_GLOBAL, false>(A, GH, L, lam, gacc, A.xout + p0, P, gt);
+      }
     }
     if (tid == 0) {                        // (a thread of wave 0: st is its own)
       A.fout[b] = fret;

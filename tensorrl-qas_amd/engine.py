@@ -304,6 +304,24 @@ class VQEEngine:
         self._chk(self._lib.vqe_noise_pauli_info(self._h, out))
         return {"w1": bool(out[0]), "w2": bool(out[1])}
 
+    def set_noise_grad(self, n_real: int, hold: bool = False):
+        """Mode 0 Pauli noise (set_noise p1 / p2 or set_noise_pauli): serve energy_grad* and the device L-BFGS at
+        n <= 13 on the mean over ``n_real`` frozen realisations - the draws batch_run_energy makes for the evaluation
+        ids eval_base .. eval_base + n_real - 1 (1 .. 4096; 0, the default, leaves those calls refused).  A gradient
+        run moves the counter on by n_real unless ``hold``: then it stays, a host optimiser sees one deterministic
+        function, and noise_grad_advance() moves it.  An L-BFGS run always moves it (an env-step by n_real + 1: its
+        closing energy is one more draw).  The definition: include/vqe_hip.h."""
+        self._chk(self._lib.vqe_set_noise_grad(self._h, int(n_real), 1 if hold else 0))
+
+    def noise_grad_advance(self):
+        """Move the evaluation counter on by the n_real of set_noise_grad (fresh realisations for the next run)."""
+        self._chk(self._lib.vqe_noise_grad_advance(self._h))
+
+    def noise_grad_info(self):
+        out = (C.c_int64 * 4)()
+        self._chk(self._lib.vqe_noise_grad_info(self._h, out))
+        return {"n_real": out[0], "hold": bool(out[1]), "eval_base": out[2]}
+
     def set_kraus_traj(self, n_traj: int):
         """Mode 0 under a Kraus override (set_noise_kraus): evaluate an energy as the mean of ``n_traj`` quantum-jump
         trajectories (1 .. 4096; 0, the default, leaves those runs refused).  Served: energy / energy_batch /

@@ -173,17 +173,30 @@ class CircuitEnvBase:
                 self.maxfev = {"maxfev": int(nlo["maxfev"])}
             if "maxfev1" in nlo:
                 self.maxfevs = {k: int(nlo[k]) for k in ("maxfev1", "maxfev2", "maxfev3")}
+            # (not a key of the reference: T frozen Pauli-noise realisations per scipy_optim for a gradient optim_alg)
+            self.noise_realisations = int(nlo["noise_realisations"]) if "noise_realisations" in nlo else None
         else:
             self.global_iters = 0
             self.optim_method = None
+            self.noise_realisations = None
         if self.optim_method not in (None, "scipy_each_step"):
             raise NotImplementedError("only method = scipy_each_step is live in the reference (SURVEY 3.3 quirk 6)")
         self.optimizer_kind = optimizer_kind(self.optim_alg) if self.optim_method else None
         if self._own_engine and self.optimizer_kind == "host_gradient" and n >= 14:
             self.engine.set_stream_grad(True)      # the streaming path computes gradients on request only
-        if self.optimizer_kind not in (None, "device_cobyla") and (self.NOISY or self.phys_noise or self.n_shots):
+        # a noisy class with a scipy gradient method: the gradient of the mean over T frozen realisations as ``jac``
+        # (engine.set_noise_grad with the counter held during a scipy_optim), when the config names T
+        self._frozen_noise = (self.optimizer_kind == "host_gradient" and self.NOISY and not self.n_shots
+                              and self.noise_realisations is not None)
+        if self.optimizer_kind not in (None, "device_cobyla") and (self.NOISY or self.phys_noise or self.n_shots) \
+                and not self._frozen_noise:
             raise NotImplementedError("noisy and finite-shot environments run COBYLA only (the device optimiser); "
-                                      f"optim_alg = {self.optim_alg!r} is refused")
+                                      f"optim_alg = {self.optim_alg!r} is refused (a noisy class without shot noise takes "
+                                      "a scipy gradient method with non_local_opt.noise_realisations = T)")
+        if self._frozen_noise:
+            if not 1 <= self.noise_realisations <= 4096:
+                raise ValueError("non_local_opt.noise_realisations must be in [1, 4096]")
+            self.engine.set_noise_grad(self.noise_realisations, hold=True)
 
     # ---- engine set-up ---------------------------------------------------------------------
     def _make_engine(self, device):
@@ -372,6 +385,12 @@ class CircuitEnvBase:
         p_new = int(circ.pidx[new_idx]) if new_idx >= 0 else -1
         if new_idx >= 0:
             keep = np.arange(len(circ)) != new_idx
+            if self._frozen_noise and new_idx + 1 < len(circ):
+                # the new gate's own noise channel leaves with it (the pre-action rule of the device env-steps)
+                k, kf = int(circ.kind[new_idx]), int(circ.kind[new_idx + 1])
+                if (kf == 4 and 1 <= k <= 3 and circ.q0[new_idx + 1] == circ.q0[new_idx]) or \
+                        (kf == 5 and k == 0 and circ.q0[new_idx + 1] == circ.q0[new_idx] and circ.q1[new_idx + 1] == circ.q1[new_idx]):
+                    keep[new_idx + 1] = False
             pidx = circ.pidx[keep].copy()
             if p_new >= 0:
                 pidx[pidx > p_new] -= 1
@@ -387,6 +406,8 @@ class CircuitEnvBase:
             res = scipy.optimize.minimize(eng.energy_grad if grad else eng.energy, x0, method=self.optim_alg,
                                           jac=True if grad else None, options={"maxiter": self.global_iters})
             x_opt, nfev = np.asarray(res.x, np.float64), int(res.nfev)
+        if self._frozen_noise:
+            eng.noise_grad_advance()      # every evaluation above saw the same T realisations; the next scipy_optim sees fresh ones
         x_full = np.insert(x_opt, p_new, ang[p_new]) if p_new >= 0 else x_opt.copy()
         x_full = x_full.astype(np.float32).astype(np.float64)      # the state tensor's dtype (reference :480)
         eng.set_circuit(circ)

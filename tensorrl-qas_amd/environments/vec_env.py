@@ -95,11 +95,16 @@ class VecCircuitEnv:
     15 of the two-qubit codes: the engine's set_noise_pauli; ``channels.pauli_weights`` and ``channels.pauli_twirl`` make
     them), either of them ``None`` for the depolarising channel.  Noisy classes only.  With noise_channel = "trajectory"
     the fused sampler draws from the tables (native and Python host loop alike), with "exact" the density matrix runs
-    their channel.  A slot takes a table or a Kraus set of ``noise_kraus``, not both."""
+    their channel.  A slot takes a table or a Kraus set of ``noise_kraus``, not both.
+    ``noise_realisations``: T in [1, 4096]; with device_optimizer = "lbfgs" and noise_channel = "trajectory" on a noisy
+    class (with or without ``noise_pauli``) every step's L-BFGS minimises the mean over T frozen Pauli-noise
+    realisations of the pre-action circuit (the engine's set_noise_grad) and the step reports ONE fresh trajectory of the
+    full circuit, as the COBYLA step does.  Without it that combination raises as before."""
 
     def __init__(self, env_cls, conf, device, num_envs: int, seed: int = 0, native: bool | None = None,
                  device_optimizer: str = "cobyla", lbfgs_opts: dict | None = None, noise_channel: str = "trajectory",
-                 noise_kraus=None, kraus_trajectories: int | None = None, noise_pauli=None):
+                 noise_kraus=None, kraus_trajectories: int | None = None, noise_pauli=None,
+                 noise_realisations: int | None = None):
         if not issubclass(env_cls, CircuitEnvBase):
             raise TypeError("env_cls must be one of the CircuitEnv classes of this package")
         if device_optimizer not in ("cobyla", "lbfgs"):
@@ -129,6 +134,14 @@ class VecCircuitEnv:
                 raise ValueError("noise_pauli is a pair (w1, w2)")
             if noise_kraus is not None and any(w is not None and K is not None for w, K in zip(noise_pauli, noise_kraus)):
                 raise ValueError("a noise slot takes a Pauli table (noise_pauli) or a Kraus set (noise_kraus), not both")
+        if noise_realisations is not None:
+            if device_optimizer != "lbfgs" or noise_channel != "trajectory" or noise_kraus is not None:
+                raise ValueError('noise_realisations needs device_optimizer = "lbfgs" and noise_channel = "trajectory" '
+                                 "(Pauli channels: depolarising or noise_pauli)")
+            if not getattr(env_cls, "NOISY", False):
+                raise ValueError("noise_realisations is for the noisy environment classes (a channel behind every gate)")
+            if not 1 <= int(noise_realisations) <= 4096:
+                raise ValueError("noise_realisations must be in [1, 4096]")
         first = env_cls(conf, device, seed=seed)
         if first.optimizer_kind not in (None, "device_cobyla"):
             raise NotImplementedError(f"VecCircuitEnv runs the device COBYLA of batch_run_env_step only; optim_alg = "
@@ -136,10 +149,12 @@ class VecCircuitEnv:
         self.device_optimizer = device_optimizer
         self._lbfgs_opts = None
         if device_optimizer == "lbfgs":
-            if noise_channel != "exact" and (first.NOISY or first.phys_noise or first.n_shots):
+            frozen = noise_realisations is not None and not first.n_shots
+            if noise_channel != "exact" and (first.NOISY or first.phys_noise or first.n_shots) and not frozen:
                 raise NotImplementedError("device_optimizer = 'lbfgs' needs an exact, deterministic energy: noisy and "
                                           "finite-shot configurations are served by the device COBYLA, or by "
-                                          "noise_channel = 'exact' (the channel itself, a density matrix)")
+                                          "noise_channel = 'exact' (the channel itself, a density matrix), or - Pauli "
+                                          "noise without shot noise - on frozen draws (noise_realisations = T)")
             self._lbfgs_opts = {"maxfun": int(first.global_iters), **(lbfgs_opts or {})}
         self.engine = first.engine
         self.noise_channel = noise_channel
@@ -159,6 +174,8 @@ class VecCircuitEnv:
                 self.engine.set_stream_kraus_traj(-1)    # the streaming path runs trajectories on request only
         if noise_pauli is not None:                      # (after the constructor's set_noise, which leaves tables alone)
             self.engine.set_noise_pauli(noise_pauli[0], noise_pauli[1])
+        if noise_realisations is not None:               # (the counter stays where the constructor's runs left it)
+            self.engine.set_noise_grad(int(noise_realisations))
         if device_optimizer == "lbfgs" and first.num_qubits >= 14:
             self.engine.set_stream_lbfgs(True)           # the streaming path runs the device L-BFGS on request only
         self._proto = first

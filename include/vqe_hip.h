@@ -251,7 +251,8 @@ int vqe_noise_pauli_info(vqe_t* h, int32_t out[2]);
  * n_real = T, 0 <= T <= 4096.  T = 0 is off, which is the default.  It is refused on an amplitude-sharded handle with
  * VQE_ESTATE.  That matches vqe_set_noise_pauli.
  * While on, with mode 0 and Pauli noise installed (depolarising p1 / p2 or a vqe_set_noise_pauli table), the gradient and
- * L-BFGS entry points are served at n <= 13 instead of refused.  The value they differentiate is
+ * L-BFGS entry points are served at n <= 13 instead of refused (at 14 <= n <= 20 after vqe_set_stream_noise_grad, below).
+ * The value they differentiate is
  *   E_T(theta) = (1/T) sum_{t=0}^{T-1} E(theta; draws of (seed, stream b, evaluation id eval_base + t)),
  * summed in ascending t.  The draws are exactly those that vqe_batch_run_energy uses for evaluation id eval_base + t of
  * batch position b.  Noise gates are numbered by position in the executed gate list.  The gradient is
@@ -265,7 +266,7 @@ int vqe_noise_pauli_info(vqe_t* h, int32_t out[2]);
  *    closing energy of the full circuit is a single trajectory with id eval_base + T (the COBYLA env-step also reports
  *    one draw there).  Afterwards eval_base += T + 1.
  * Still refused, with the codes they had: shot noise, Kraus sets without a Pauli form and vqe_set_kraus_traj runs (their
- * probabilities depend on theta), n >= 14, L-BFGS on a term shard.  A term-sharded handle gets its partial E_T and its
+ * probabilities depend on theta), L-BFGS on a term shard.  A term-sharded handle gets its partial E_T and its
  * partial gradient, as without noise; every rank draws the same errors.  A refused call changes nothing.
  * With the switch off, every call answers as before.  With the switch on and p1 = p2 = 0 and no table, the noiseless
  * kernels run and their bits are unchanged.  VQE_EINVAL, handle unchanged, for T outside [0, 4096]. */
@@ -274,6 +275,21 @@ int vqe_set_noise_grad(vqe_t* h, int n_real, int hold);
 int vqe_noise_grad_advance(vqe_t* h);
 /* out[0] T, [1] hold, [2] the current eval_base, [3] 0 */
 int vqe_noise_grad_info(vqe_t* h, int64_t out[4]);
+/* The same gradients on the streaming path (14 <= n <= 20, csrc/vqe_stream_grad.h), opt-in per handle.
+ * max_resident: 0 (default) off - a handle with n >= 14 answers every call as before, code and text; -1 on, with as many
+ * (circuit, realisation) states resident as fit into a quarter of the free device memory at the first run (at least 1,
+ * at most batch x T); R >= 1 on, with at most R resident; < -1 VQE_EINVAL, handle unchanged.  VQE_ESTATE on an
+ * amplitude-sharded handle.  Accepted with no effect at n <= 13.  Touches neither seed, counter, tables nor the resident
+ * batch.  With the switch on, mode 0, Pauli noise installed and vqe_set_noise_grad(T >= 1), the entry points
+ * vqe_set_noise_grad lists are served with its E_T, word for word, and its counter rules; the gradient calls need
+ * vqe_set_stream_grad beside it, the L-BFGS calls vqe_set_stream_lbfgs, and without those their own refusals stay, in
+ * the existing order.  The batch x T pairs run as streams of one set of launches, max_resident at a time; a pair holds
+ * two states of 16 * 2^n bytes.  The results have the same bits for the same (seed, eval_base, batch position, T),
+ * whatever max_resident and whatever else is in the batch.  The refusals of vqe_set_noise_grad stay. */
+int vqe_set_stream_noise_grad(vqe_t* h, int max_resident);
+/* out[0] max_resident as set, [1] pairs resident per chunk in the last served run, [2] chunks of that run (per
+ * evaluation), [3] 0 */
+int vqe_stream_noise_grad_info(vqe_t* h, int64_t out[4]);
 /* Mode 0 under a Kraus override (vqe_set_noise_kraus): evaluate an energy as the mean of n_traj quantum-jump
  * trajectories.  0 (default): those runs are refused with VQE_ESTATE as before.  1 .. 4096.  Accepted on any handle;
  * takes effect in mode 0 while an override is installed, 1 <= n <= 13, unsharded handles.  Touches neither seed,

@@ -75,6 +75,8 @@ SIGNATURES = {
     "vqe_set_noise_grad": (C.c_int, [vp, C.c_int, C.c_int]),
     "vqe_noise_grad_advance": (C.c_int, [vp]),
     "vqe_noise_grad_info": (C.c_int, [vp, c_i64p]),
+    "vqe_set_stream_noise_grad": (C.c_int, [vp, C.c_int]),
+    "vqe_stream_noise_grad_info": (C.c_int, [vp, c_i64p]),
     "vqe_set_kraus_traj": (C.c_int, [vp, C.c_int]),
     "vqe_kraus_traj_info": (C.c_int, [vp, c_i64p]),
     "vqe_batch_fetch_traj": (C.c_int, [vp, c_f64p]),

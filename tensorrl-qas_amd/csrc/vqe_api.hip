@@ -182,6 +182,13 @@ struct vqe_handle {
   // and whether a gradient run leaves eval_base where it is (a host optimiser's one deterministic function)
   int noise_grad_T = 0;
   bool noise_grad_hold = false;
+  // ... on the streaming path (vqe_set_stream_noise_grad): max_resident (0: refused as before, -1 a quarter
+  // of the free memory, R >= 1), the (circuit, realisation) pairs that fit (fixed at the first run), the expanded batch
+  // and per-pair results, {max_resident, resident pairs, chunks, 0} of the last served run
+  int sng_resident = 0;
+  size_t sng_auto_cap = 0;
+  int64_t sng_info[4] = {0, 0, 0, 0};
+  StreamNoiseWork snw;
   int kraus_traj = 0;
   uint64_t qj_ver = 0, qj_tab_ver = ~0ull;
   DevBuf<double> qj_K1, qj_W1, qj_K2, qj_W2, qj_e;
@@ -1502,10 +1509,13 @@ int build_grad_tables(vqe_t* h) {
 // Checked before anything is loaded, so a refused call leaves the handle as it was.
 // noise_grad_on: the run is the mean over frozen Pauli-noise realisations (after grad_state_refusal let it through).
 // (grad_state_refusal: everything but the path test - the device L-BFGS has a switch of its own for n >= 14)
+constexpr int kStreamNoiseGradMaxQubits = 20;      // the sizes the streaming form of the noisy gradient is served at
 NoiseGradVerdict noise_grad_state(const vqe_t* h) {
-  return noise_grad_verdict(NoiseGradState{h->noise_grad_T, h->noise_mode, pauli_noise_on(h), h->lds_path});
+  return noise_grad_verdict(NoiseGradState{h->noise_grad_T, h->noise_mode, pauli_noise_on(h), h->lds_path,
+                                           !h->lds_path && h->n <= kStreamNoiseGradMaxQubits && h->sng_resident != 0});
 }
 bool noise_grad_on(const vqe_t* h) { return noise_grad_state(h) == NG_SERVED; }
+bool noise_grad_stream(const vqe_t* h) { return noise_grad_state(h) == NG_SERVED_STREAM; }      // (n >= 14: vqe_set_stream_noise_grad)
 NoiseGrad noise_grad_args(const vqe_t* h) {
   return noise_grad_on(h) ? NoiseGrad{h->noise_grad_T, std::max(1, h->max_rot)} : NoiseGrad{0, -1};
 }
@@ -1588,11 +1598,47 @@ int launch_grad(vqe_t* h, const BatchArgs& A) {
                            too_large, h->d_grad.p, prepare);
 }
 
-// Streaming path (n >= 14, vqe_set_stream_grad): forward sweeps, lambda = H psi, backward sweeps (vqe_stream_grad.h)
+// The resident (circuit, realisation) pairs a noisy streaming gradient may hold: max_resident as set, or with -1 what a
+// quarter of the free device memory takes (psi, lambda and the backward sweep's partials per pair), fixed at the first run.
+int stream_noise_cap(vqe_t* h, const BatchArgs& A, int64_t* cap) {
+  if (h->sng_resident < 0 && !h->sng_auto_cap) {
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(h, hipMemGetInfo(&free_b, &total_b));
+    const size_t dim = (size_t)1 << h->n;
+    const size_t gblk = ((dim >> kGradOpsPerSweep) + kThreads - 1) / kThreads;
+    const size_t per_pair = 2 * dim * sizeof(double2) + (size_t)A.max_ops * gblk * sizeof(double);
+    h->sng_auto_cap = std::max<size_t>(1, (free_b / 4) / per_pair);
+  }
+  *cap = h->sng_resident > 0 ? (int64_t)h->sng_resident : (int64_t)h->sng_auto_cap;
+  return VQE_OK;
+}
+
+// One evaluation of E_T and its gradient on the streaming path (vqe_stream_grad.h: stream_noise_energy_grad): the
+// realisations eval_base .. eval_base + T - 1 of the batch A describes at A.theta, E_T into A.fout, the gradient into d_grad.
+int stream_noise_grad_eval(vqe_t* h, const BatchArgs& A) {
+  int64_t cap = 1;
+  VQE_TRY(stream_noise_cap(h, A, &cap));
+  int used = 0, chunks = 0;
+  VQE_TRY(stream_noise_energy_grad(h->sw, h->snw, A, h->stream, h->noise.eval_base, h->noise_grad_T, cap, h->d_grad.p, h->err,
+                                   h->gen, &used, &chunks));
+  h->sng_info[0] = h->sng_resident;
+  h->sng_info[1] = used;
+  h->sng_info[2] = chunks;
+  h->sng_info[3] = 0;
+  return VQE_OK;
+}
+
+// Streaming path (n >= 14, vqe_set_stream_grad): forward sweeps, lambda = H psi, backward sweeps (vqe_stream_grad.h);
+// under Pauli noise (vqe_set_stream_noise_grad) the mean over the frozen realisations, the counter as at n <= 13
 int stream_grad(vqe_t* h, const BatchArgs& A) {
   HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
   h->stream_states_undone = true;
-  VQE_TRY(stream_energy_grad(h->sw, A, h->stream, h->noise.eval_base, h->d_grad.p, h->err, h->gen));
+  if (noise_grad_stream(h)) {
+    VQE_TRY(stream_noise_grad_eval(h, A));
+    h->noise.eval_base += noise_grad_consumed(NoiseGradRun::Gradient, h->noise_grad_T, h->noise_grad_hold);
+  } else {
+    VQE_TRY(stream_energy_grad(h->sw, A, h->stream, h->noise.eval_base, h->d_grad.p, h->err, h->gen));
+  }
   HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
   return VQE_OK;
 }
@@ -1670,7 +1716,10 @@ int stream_lbfgs(vqe_t* h, BatchArgs& A, const vqe_lbfgs_opts_t& o, std::vector<
   const LbfgsArgs O{o.history, o.maxiter, o.maxfun, o.max_ls, o.gtol, o.ftol, o.c1, h->lb_work.p, h->lb_nit.p, h->lb_status.p};
   h->stream_states_undone = true;
   return lockstep_run(h, "L-BFGS", o.maxfun, x, f, nfev,
-                      [&](uint64_t it) { return stream_energy_grad(h->sw, A, h->stream, h->noise.eval_base + it, h->d_grad.p, h->err, h->gen); },
+                      [&](uint64_t it) {      // (frozen realisations: the same T ids at every trial point)
+                        if (noise_grad_stream(h)) return stream_noise_grad_eval(h, A);
+                        return stream_energy_grad(h->sw, A, h->stream, h->noise.eval_base + it, h->d_grad.p, h->err, h->gen);
+                      },
                       [&](uint64_t it) {
                         hipLaunchKernelGGL(it == 1 ? k_sl_step<true> : k_sl_step<false>, dim3((unsigned)B), dim3(64), 0, h->stream, T, O);
                       });
@@ -1686,7 +1735,9 @@ int stream_run_lbfgs(vqe_t* h, bool env_step, const vqe_lbfgs_opts_t& o) {
   h->lb_batch = 0;
   std::vector<int32_t> nfev;
   HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
-  const uint64_t eval_id = h->noise.eval_base + (uint64_t)o.maxfun + 1;
+  // (frozen realisations: the closing energy of an env-step is the single trajectory with id eval_base + T)
+  const bool frozen = noise_grad_stream(h);
+  const uint64_t eval_id = h->noise.eval_base + (frozen ? (uint64_t)h->noise_grad_T : (uint64_t)o.maxfun + 1);
   VQE_TRY(minimize_or_env_step(h, env_step, A, nfev,
       [&](BatchArgs& a, const PreActionBatch*, std::vector<double>& x, std::vector<double>& f, std::vector<int32_t>& nf) {
         return stream_lbfgs(h, a, o, x, f, nf);
@@ -1695,6 +1746,8 @@ int stream_run_lbfgs(vqe_t* h, bool env_step, const vqe_lbfgs_opts_t& o) {
   if (env_step) h->stream_states_undone = false;      // (the last launch was an energy: the states are those of the full circuits)
   HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
   h->lb_batch = h->batch;
+  if (frozen)
+    h->noise.eval_base += noise_grad_consumed(env_step ? NoiseGradRun::EnvStepLbfgs : NoiseGradRun::Lbfgs, h->noise_grad_T, h->noise_grad_hold);
   return VQE_OK;
 }
 
@@ -2192,6 +2245,22 @@ int vqe_set_noise_grad(vqe_t* h, int n_real, int hold) {
   if (h->amp_world > 1) return fail(h, VQE_ESTATE, "gradients of frozen noise realisations (vqe_set_noise_grad) take no amplitude-sharded handle");
   h->noise_grad_T = n_real;
   h->noise_grad_hold = hold != 0;
+  return VQE_OK;
+}
+
+int vqe_set_stream_noise_grad(vqe_t* h, int max_resident) {
+  if (!h) return VQE_EINVAL;
+  if (max_resident < -1) return fail(h, VQE_EINVAL, "max_resident: 0 (off), -1 (a quarter of the free device memory) or R >= 1");
+  if (h->amp_world > 1) return fail(h, VQE_ESTATE, "gradients of frozen noise realisations (vqe_set_stream_noise_grad) take no amplitude-sharded handle");
+  h->sng_resident = max_resident;      // (n <= 13: the LDS-resident kernel serves every noisy gradient; nothing to switch)
+  h->sng_auto_cap = 0;
+  return VQE_OK;
+}
+
+int vqe_stream_noise_grad_info(vqe_t* h, int64_t out[4]) {
+  if (!h || !out) return VQE_EINVAL;
+  out[0] = h->sng_resident;
+  std::copy(h->sng_info + 1, h->sng_info + 4, out + 1);
   return VQE_OK;
 }
 

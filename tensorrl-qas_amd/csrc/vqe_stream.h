@@ -55,10 +55,11 @@ struct StreamWork {
   DevBufExact<double> gpart;        // [batch][max_ops][blocks of k_sg_back]
 };
 
-// one thread per stream: gate list -> ops (+ zm rows, needed to move the Pauli masks)
-__global__ void k_s_compile(BatchArgs A, Op* ops, uint32_t* masks, int32_t* meta, uint64_t eval_id) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= A.batch) return;
+// one thread per stream: gate list -> ops (+ zm rows, needed to move the Pauli masks).  The draws of stream b are
+// those of (seed, key_b, eval_id): key_b = b for a resident batch (k_s_compile), the circuit's batch position and the
+// realisation's evaluation id for a (circuit, realisation) pair of the noisy gradient (k_s_compile_keyed).
+__device__ __forceinline__ void s_compile(const BatchArgs& A, Op* ops, uint32_t* masks, int32_t* meta, const int b,
+                                          const uint64_t key_b, const uint64_t eval_id) {
   const int n = A.n;
   uint32_t* xm = masks + (size_t)b * 64;
   uint32_t* zm = xm + 32;
@@ -93,10 +94,10 @@ __global__ void k_s_compile(BatchArgs A, Op* ops, uint32_t* masks, int32_t* meta
                        rot2_op(r.kind) | (int)((((c >> r.q0) ^ (c >> r.q1)) & 1u) << 8)};
       ++nops;
     } else if (r.kind == G_DEPOL1) {
-      const double u = noise_uniform(A.noise.seed, (uint64_t)b, eval_id, (uint64_t)i);
+      const double u = noise_uniform(A.noise.seed, key_b, eval_id, (uint64_t)i);
       if (u < A.noise.p1) pauli(r.q0, noise_slot_code(A.noise.pauli, A.noise.p1, false, u));
     } else if (r.kind == G_DEPOL2) {
-      const double u = noise_uniform(A.noise.seed, (uint64_t)b, eval_id, (uint64_t)i);
+      const double u = noise_uniform(A.noise.seed, key_b, eval_id, (uint64_t)i);
       if (u < A.noise.p2) {
         const int idx = noise_slot_code(A.noise.pauli, A.noise.p2, true, u);
         pauli(r.q0, idx & 3);
@@ -108,6 +109,17 @@ __global__ void k_s_compile(BatchArgs A, Op* ops, uint32_t* masks, int32_t* meta
   m[0] = nops < A.max_ops ? nops : A.max_ops;
   m[1] = (int32_t)c;
   m[2] = phase;
+}
+__global__ void k_s_compile(BatchArgs A, Op* ops, uint32_t* masks, int32_t* meta, uint64_t eval_id) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= A.batch) return;
+  s_compile(A, ops, masks, meta, b, (uint64_t)b, eval_id);
+}
+// keys: [batch][2] = (batch position whose draws stream b takes, evaluation id)
+__global__ void k_s_compile_keyed(BatchArgs A, Op* ops, uint32_t* masks, int32_t* meta, const uint64_t* keys) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= A.batch) return;
+  s_compile(A, ops, masks, meta, b, keys[2 * (size_t)b], keys[2 * (size_t)b + 1]);
 }
 
 __global__ void k_s_sincos(BatchArgs A, double2* cs) {
@@ -411,8 +423,9 @@ inline bool stream_tiled(int n_groups, int n_terms) {
 // call), or both
 enum class StreamWant { Circuit, Energy, Both };
 
+// keys: NULL, or the draw keys of every stream ([batch][2], k_s_compile_keyed) in eval_id's place
 inline int stream_evaluate(StreamWork& sw, const BatchArgs& A, hipStream_t st, uint64_t eval_id, StreamWant want,
-                           std::string& err, uint64_t generation) {
+                           std::string& err, uint64_t generation, const uint64_t* keys = nullptr) {
   const bool want_circuit = want != StreamWant::Energy, want_energy = want != StreamWant::Circuit;
   const int n_terms = A.ham.n_terms;
   const size_t dim = (size_t)1 << A.n;
@@ -470,7 +483,8 @@ inline int stream_evaluate(StreamWork& sw, const BatchArgs& A, hipStream_t st, u
     if (want_circuit) {
       hipLaunchKernelGGL(k_s_sincos, dim3((A.max_params + 63) / 64, B), dim3(64), 0, st, A, sw.cs.p);
       if (!sw.plan_ops_ok) {
-        hipLaunchKernelGGL(k_s_compile, dim3((B + 63) / 64), dim3(64), 0, st, A, sw.ops.p, sw.masks.p, sw.meta.p, eval_id);
+        if (keys) hipLaunchKernelGGL(k_s_compile_keyed, dim3((B + 63) / 64), dim3(64), 0, st, A, sw.ops.p, sw.masks.p, sw.meta.p, keys);
+        else hipLaunchKernelGGL(k_s_compile, dim3((B + 63) / 64), dim3(64), 0, st, A, sw.ops.p, sw.masks.p, sw.meta.p, eval_id);
         const bool with_groups = want_energy && fuse_on;      // (the Pauli masks follow the layout the circuit leaves: sw.masks)
         if (with_groups)
           hipLaunchKernelGGL(k_s_terms, dim3((m_terms + 63) / 64, B), dim3(64), 0, st, A, sw.masks.p, sw.meta.p, n_terms, sw.gxp.p,
@@ -530,7 +544,8 @@ inline int stream_evaluate(StreamWork& sw, const BatchArgs& A, hipStream_t st, u
   HIP_TRY(err, sw.partial.reserve((size_t)B * eblk));
 
   if (want_circuit) {
-    hipLaunchKernelGGL(k_s_compile, dim3((B + 63) / 64), dim3(64), 0, st, A, sw.ops.p, sw.masks.p, sw.meta.p, eval_id);
+    if (keys) hipLaunchKernelGGL(k_s_compile_keyed, dim3((B + 63) / 64), dim3(64), 0, st, A, sw.ops.p, sw.masks.p, sw.meta.p, keys);
+    else hipLaunchKernelGGL(k_s_compile, dim3((B + 63) / 64), dim3(64), 0, st, A, sw.ops.p, sw.masks.p, sw.meta.p, eval_id);
     hipLaunchKernelGGL(k_s_sincos, dim3((A.max_params + 63) / 64, B), dim3(64), 0, st, A, sw.cs.p);
     hipLaunchKernelGGL(k_s_init, dim3((unsigned)(dim / kThreads), B), dim3(kThreads), 0, st, A, sw.states.p);
     for (int o = 0; o < A.max_ops; o += kOpsPerSweep)

@@ -12,10 +12,16 @@
 //  4. k_sg_reduce: grad[j] = sum over the ops with parameter j, each summed over its blocks, in one fixed order
 //     (bitwise reproducible, no atomics; exactly 0 for a parameter no op uses).
 // After a gradient sw.states holds the INITIAL state again (every op undone) and sw.lam the pulled-back lambda.
-// Noise is refused before this path is entered (vqe_api.hip: grad_refusal), so ops other than rotations do not occur;
-// an op of any other kind is skipped.
+// The noiseless instances see rotations only (noise without vqe_set_stream_noise_grad is refused before this path is
+// entered, vqe_api.hip: grad_refusal) and skip an op of any other kind.
+// NOISY (vqe_set_stream_noise_grad): the mean over T frozen Pauli-noise realisations.  The B * T (circuit,
+// realisation) pairs are virtual streams of an expanded batch (k_sn_expand: the gates of circuit b, a theta slot and a
+// gradient row of their own, the draw key (b, eval_base + t)), `resident` of them per chunk through the same launches;
+// the backward sweep is the <K, PZ = true> instance, which applies the OP_PZ records of the drawn Z / Y errors to psi and
+// lambda (a +-1 diagonal: its own inverse, no gradient row); k_sg_mean closes the run after the last chunk.
 #pragma once
 #include "vqe_stream.h"
+#include "noise_grad_host.h"
 
 namespace vqe {
 
@@ -23,8 +29,9 @@ constexpr int kGradOpsPerSweep = 3;   // K of k_sg_back: the largest that compil
 constexpr int kLambdaApt = 2;         // amplitudes a thread of k_sg_lambda owns
 
 // s_apply_k with the angle given as (cos, sin) instead of read from the parameter table, and with the dependent-mask
-// case spelled out per flip code (static register indices only: no scratch).  Ops that are no rotation are skipped.
-template <int K>
+// case spelled out per flip code (static register indices only: no scratch).  Ops that are no rotation are skipped;
+// PZ: the record of a drawn Z error, (-1)^(parity(idx & zm) ^ inv), is applied (OP_NOP stays skipped).
+template <int K, bool PZ = false>
 __device__ __forceinline__ void s_apply_k_cs(double2 (&v)[1 << K], const uint32_t (&idx)[1 << K], const Op op,
                                              const double2 c, const int flip) {
   constexpr int E = 1 << K;
@@ -57,6 +64,10 @@ __device__ __forceinline__ void s_apply_k_cs(double2 (&v)[1 << K], const uint32_
       const double2 a = v[e];
       v[e] = make_double2(c.x * a.x - sg * a.y, c.x * a.y + sg * a.x);
     }
+  } else if (PZ && kind == OP_PZ) {
+#pragma unroll
+    for (int e = 0; e < E; ++e)
+      if (parity32(idx[e] & op.zm) ^ inv) v[e] = make_double2(-v[e].x, -v[e].y);
   }
 }
 
@@ -145,10 +156,11 @@ __global__ void __launch_bounds__(kThreads) k_sg_lambda(BatchArgs A, const doubl
 }
 
 // Backward sweep over the ops [o, o + K) of every stream: the slot-and-coset construction of k_s_opk (same reduce /
-// push / flip basis), the thread's 2^K amplitudes of psi and of lambda in registers.
-template <int K>
-__global__ void __launch_bounds__(kThreads) k_sg_back(BatchArgs A, double2* states, double2* lambda, const Op* ops,
-                                                      const int32_t* meta, const double2* cs, double* gpart, int o) {
+// push / flip basis), the thread's 2^K amplitudes of psi and of lambda in registers.  PZ: the streams hold OP_PZ records
+// (a diagonal: no partner mask, so it sits in a filler slot as any op that is no pair op).
+template <int K, bool PZ>
+__device__ __forceinline__ void sg_back(const BatchArgs& A, double2* states, double2* lambda, const Op* ops,
+                                        const int32_t* meta, const double2* cs, double* gpart, const int o) {
   constexpr int E = 1 << K;
   __shared__ double redsm[8];
   const int b = blockIdx.y;
@@ -260,6 +272,9 @@ __global__ void __launch_bounds__(kThreads) k_sg_back(BatchArgs A, double2* stat
       const double2 ci = make_double2(c.x, -c.y);                           // U^-1
       s_apply_k_cs<K>(v, idx, op[j], ci, flip[j]);
       s_apply_k_cs<K>(l, idx, op[j], ci, flip[j]);
+    } else if (PZ && j < cnt && kind == OP_PZ) {
+      s_apply_k_cs<K, true>(v, idx, op[j], make_double2(1.0, 0.0), 0);
+      s_apply_k_cs<K, true>(l, idx, op[j], make_double2(1.0, 0.0), 0);
     }
   }
   if (live) {
@@ -274,6 +289,16 @@ __global__ void __launch_bounds__(kThreads) k_sg_back(BatchArgs A, double2* stat
       if (threadIdx.x == 0) gout[(size_t)j * gridDim.x] = tot;
     }
   }
+}
+template <int K>
+__global__ void __launch_bounds__(kThreads) k_sg_back(BatchArgs A, double2* states, double2* lambda, const Op* ops,
+                                                      const int32_t* meta, const double2* cs, double* gpart, int o) {
+  sg_back<K, false>(A, states, lambda, ops, meta, cs, gpart, o);
+}
+template <int K>
+__global__ void __launch_bounds__(kThreads) k_sg_back_pz(BatchArgs A, double2* states, double2* lambda, const Op* ops,
+                                                         const int32_t* meta, const double2* cs, double* gpart, int o) {
+  sg_back<K, true>(A, states, lambda, ops, meta, cs, gpart, o);
 }
 
 // grad[par_begin[b] + j]: one workgroup per (parameter, stream).  Thread i adds the partials i, i + 256, ... of every op
@@ -297,10 +322,12 @@ __global__ void __launch_bounds__(kThreads) k_sg_reduce(BatchArgs A, const Op* o
 }
 
 // E (A.fout) and dE/dtheta (grad, the layout of the batch's theta) of every resident stream.
+// keys: NULL, or the draw keys of the streams of a noisy chunk (stream_evaluate); the backward sweeps are then the
+// instance that knows the OP_PZ record.
 inline int stream_energy_grad(StreamWork& sw, const BatchArgs& A, hipStream_t st, uint64_t eval_id, double* grad,
-                              std::string& err, uint64_t generation) {
+                              std::string& err, uint64_t generation, const uint64_t* keys = nullptr) {
   constexpr int K = kGradOpsPerSweep;
-  VQE_TRY(stream_evaluate(sw, A, st, eval_id, StreamWant::Circuit, err, generation));
+  VQE_TRY(stream_evaluate(sw, A, st, eval_id, StreamWant::Circuit, err, generation, keys));
   const int n_terms = A.ham.n_terms;
   const size_t dim = (size_t)1 << A.n;
   const int B = A.batch;
@@ -315,11 +342,98 @@ inline int stream_energy_grad(StreamWork& sw, const BatchArgs& A, hipStream_t st
   hipLaunchKernelGGL(k_sg_lambda, dim3(lblk, B), dim3(kThreads), 0, st, A, (const double2*)sw.states.p, n_terms,
                      (const uint32_t*)sw.gxp.p, (const uint32_t*)sw.tzp.p, (const double*)sw.tsg.p, sw.lam.p, sw.partial.p);
   hipLaunchKernelGGL(k_s_reduce, dim3(B), dim3(kThreads), 0, st, sw.partial.p, lblk, A.fout, A.noise, eval_id, 0);
+  const auto back = keys ? k_sg_back_pz<K> : k_sg_back<K>;
   for (int o = ((A.max_ops - 1) / K) * K; o >= 0; o -= K)      // the op groups of the forward sweeps, last first
-    hipLaunchKernelGGL(k_sg_back<K>, dim3(gblk, B), dim3(kThreads), 0, st, A, sw.states.p, sw.lam.p, (const Op*)sw.ops.p,
+    hipLaunchKernelGGL(back, dim3(gblk, B), dim3(kThreads), 0, st, A, sw.states.p, sw.lam.p, (const Op*)sw.ops.p,
                        (const int32_t*)sw.meta.p, (const double2*)sw.cs.p, sw.gpart.p, o);
   hipLaunchKernelGGL(k_sg_reduce, dim3(A.max_params, B), dim3(kThreads), 0, st, A, (const Op*)sw.ops.p,
                      (const int32_t*)sw.meta.p, (const double*)sw.gpart.p, gblk, grad);
+  HIP_TRY(err, hipGetLastError());
+  return 0;
+}
+
+// ---- the mean over frozen Pauli-noise realisations (vqe_set_stream_noise_grad) ------------------------
+// Buffers of the expanded batch of a chunk (sized by the resident count) and the per-pair results of a run (B * T rows).
+struct StreamNoiseWork {
+  DevBufExact<int64_t> gbeg, pbeg;      // [resident] gate range of the pair's circuit; its theta slot i * max_params
+  DevBufExact<int32_t> gcnt, pcnt;      // [resident]
+  DevBufExact<uint64_t> keys;           // [resident][2] (b, eval_base + t)
+  DevBufExact<double> theta;            // [resident][max_params]
+  DevBufExact<double> pair_e, pair_g;   // [B * T], [B * T][max_params]
+};
+
+// The index arrays of the pairs v0 .. v0 + cnt - 1 (v = b * T + t): one thread per pair.
+__global__ void k_sn_expand(BatchArgs A, int T, int64_t v0, int cnt, uint64_t eval_base, int64_t* gbeg, int32_t* gcnt,
+                            int64_t* pbeg, int32_t* pcnt, uint64_t* keys) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= cnt) return;
+  const int64_t v = v0 + i;
+  const int b = (int)(v / T), t = (int)(v % T);
+  gbeg[i] = A.gate_begin[b];
+  gcnt[i] = A.gate_count[b];
+  pbeg[i] = (int64_t)i * A.max_params;
+  pcnt[i] = A.par_count[b];
+  keys[2 * (size_t)i] = (uint64_t)b;
+  keys[2 * (size_t)i + 1] = eval_base + (uint64_t)t;
+}
+// theta of circuit b to the slot of each of its pairs in the chunk (at every evaluation: an optimiser moves theta)
+__global__ void k_sn_theta(BatchArgs A, int T, int64_t v0, double* theta_x) {
+  const int i = blockIdx.y;
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  const int b = (int)((v0 + i) / T);
+  if (j >= A.par_count[b]) return;
+  theta_x[(size_t)i * A.max_params + j] = A.theta[A.par_begin[b] + j];
+}
+// E_T[b] (thread j == max_params) and grad[par_begin[b] + j]: the T per-pair values added in ascending t, divided once.
+__global__ void k_sg_mean(BatchArgs A, int T, const double* pair_e, const double* pair_g, double* fout, double* grad) {
+  const int b = blockIdx.y;
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t v = (size_t)b * T;
+  if (j == A.max_params) {
+    double acc = 0.0;
+    for (int t = 0; t < T; ++t) acc += pair_e[v + t];
+    fout[b] = acc / (double)T;
+  } else if (j < A.par_count[b]) {
+    double acc = 0.0;
+    for (int t = 0; t < T; ++t) acc += pair_g[(v + t) * A.max_params + j];
+    grad[A.par_begin[b] + j] = acc / (double)T;
+  }
+}
+
+// E_T (A.fout) and its gradient (grad, the layout of the batch's theta) of the batch A describes, at A.theta: the pairs of
+// every chunk as streams of one stream_energy_grad, then the mean.  cap: resident pairs asked for; *used / *chunks: out.
+inline int stream_noise_energy_grad(StreamWork& sw, StreamNoiseWork& nw, const BatchArgs& A, hipStream_t st, uint64_t eval_base,
+                                    int T, int64_t cap, double* grad, std::string& err, uint64_t generation, int* used,
+                                    int* chunks) {
+  const NoiseGradChunks P = noise_grad_chunks(A.batch, T, cap);
+  const int R = P.resident, mp = A.max_params;
+  *used = R;
+  *chunks = P.chunks;
+  HIP_TRY(err, nw.gbeg.reserve(R));
+  HIP_TRY(err, nw.pbeg.reserve(R));
+  HIP_TRY(err, nw.gcnt.reserve(R));
+  HIP_TRY(err, nw.pcnt.reserve(R));
+  HIP_TRY(err, nw.keys.reserve((size_t)2 * R));
+  HIP_TRY(err, nw.theta.reserve((size_t)R * std::max(mp, 1)));
+  HIP_TRY(err, nw.pair_e.reserve((size_t)std::max<int64_t>(P.pairs, 1)));
+  HIP_TRY(err, nw.pair_g.reserve((size_t)std::max<int64_t>(P.pairs, 1) * std::max(mp, 1)));
+  for (int c = 0; c < P.chunks; ++c) {
+    int64_t lo, hi;
+    noise_grad_chunk_range(P, c, &lo, &hi);
+    const int cnt = (int)(hi - lo);
+    hipLaunchKernelGGL(k_sn_expand, dim3((cnt + 63) / 64), dim3(64), 0, st, A, T, lo, cnt, eval_base, nw.gbeg.p, nw.gcnt.p,
+                       nw.pbeg.p, nw.pcnt.p, nw.keys.p);
+    hipLaunchKernelGGL(k_sn_theta, dim3((std::max(mp, 1) + 63) / 64, cnt), dim3(64), 0, st, A, T, lo, nw.theta.p);
+    BatchArgs C = A;
+    C.batch = cnt;
+    C.gate_begin = nw.gbeg.p; C.gate_count = nw.gcnt.p;
+    C.par_begin = nw.pbeg.p; C.par_count = nw.pcnt.p;
+    C.theta = nw.theta.p;
+    C.fout = nw.pair_e.p + lo;
+    VQE_TRY(stream_energy_grad(sw, C, st, eval_base, nw.pair_g.p + (size_t)lo * mp, err, generation, (const uint64_t*)nw.keys.p));
+  }
+  hipLaunchKernelGGL(k_sg_mean, dim3((mp + 1 + 63) / 64, A.batch), dim3(64), 0, st, A, T, (const double*)nw.pair_e.p,
+                     (const double*)nw.pair_g.p, A.fout, grad);
   HIP_TRY(err, hipGetLastError());
   return 0;
 }

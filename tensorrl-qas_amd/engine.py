@@ -306,7 +306,7 @@ class VQEEngine:
 
     def set_noise_grad(self, n_real: int, hold: bool = False):
         """Mode 0 Pauli noise (set_noise p1 / p2 or set_noise_pauli): serve energy_grad* and the device L-BFGS at
-        n <= 13 on the mean over ``n_real`` frozen realisations - the draws batch_run_energy makes for the evaluation
+        n <= 13 (at 14 <= n <= 20 after set_stream_noise_grad) on the mean over ``n_real`` frozen realisations - the draws batch_run_energy makes for the evaluation
         ids eval_base .. eval_base + n_real - 1 (1 .. 4096; 0, the default, leaves those calls refused).  A gradient
         run moves the counter on by n_real unless ``hold``: then it stays, a host optimiser sees one deterministic
         function, and noise_grad_advance() moves it.  An L-BFGS run always moves it (an env-step by n_real + 1: its
@@ -321,6 +321,21 @@ class VQEEngine:
         out = (C.c_int64 * 4)()
         self._chk(self._lib.vqe_noise_grad_info(self._h, out))
         return {"n_real": out[0], "hold": bool(out[1]), "eval_base": out[2]}
+
+    def set_stream_noise_grad(self, max_resident: int = -1):
+        """The gradients of set_noise_grad at 14 <= n <= 20 (the streaming path), opt-in per handle: every (circuit,
+        realisation) pair is a stream of the adjoint sweeps (two states of 16 * 2^n bytes), ``max_resident`` of them
+        at a time (-1: as many as fit into a quarter of the free device memory at the first run; 0: off, the calls are
+        refused as before).  energy_grad* also needs set_stream_grad, the L-BFGS calls set_stream_lbfgs.  The bits of a
+        result do not depend on it.  No effect at n <= 13."""
+        self._chk(self._lib.vqe_set_stream_noise_grad(self._h, int(max_resident)))
+
+    def stream_noise_grad_info(self):
+        """max_resident as set, and of the last noisy gradient / L-BFGS run on the streaming path (0 before one) the
+        pairs resident per chunk and the chunks per evaluation."""
+        out = (C.c_int64 * 4)()
+        self._chk(self._lib.vqe_stream_noise_grad_info(self._h, out))
+        return {"max_resident": out[0], "resident": out[1], "chunks": out[2]}
 
     def set_kraus_traj(self, n_traj: int):
         """Mode 0 under a Kraus override (set_noise_kraus): evaluate an energy as the mean of ``n_traj`` quantum-jump

@@ -197,6 +197,8 @@ class CircuitEnvBase:
             if not 1 <= self.noise_realisations <= 4096:
                 raise ValueError("non_local_opt.noise_realisations must be in [1, 4096]")
             self.engine.set_noise_grad(self.noise_realisations, hold=True)
+            if self._own_engine and n >= 14:
+                self.engine.set_stream_noise_grad(-1)      # the streaming path runs the noisy gradients on request only
 
     # ---- engine set-up ---------------------------------------------------------------------
     def _make_engine(self, device):

@@ -99,7 +99,8 @@ class VecCircuitEnv:
     ``noise_realisations``: T in [1, 4096]; with device_optimizer = "lbfgs" and noise_channel = "trajectory" on a noisy
     class (with or without ``noise_pauli``) every step's L-BFGS minimises the mean over T frozen Pauli-noise
     realisations of the pre-action circuit (the engine's set_noise_grad) and the step reports ONE fresh trajectory of the
-    full circuit, as the COBYLA step does.  Without it that combination raises as before."""
+    full circuit, as the COBYLA step does (at 14 qubits and more the engine's set_stream_noise_grad is switched on for
+    it).  Without it that combination raises as before."""
 
     def __init__(self, env_cls, conf, device, num_envs: int, seed: int = 0, native: bool | None = None,
                  device_optimizer: str = "cobyla", lbfgs_opts: dict | None = None, noise_channel: str = "trajectory",
@@ -176,6 +177,8 @@ class VecCircuitEnv:
             self.engine.set_noise_pauli(noise_pauli[0], noise_pauli[1])
         if noise_realisations is not None:               # (the counter stays where the constructor's runs left it)
             self.engine.set_noise_grad(int(noise_realisations))
+            if first.num_qubits >= 14:
+                self.engine.set_stream_noise_grad(-1)    # the streaming path runs the noisy gradients on request only
         if device_optimizer == "lbfgs" and first.num_qubits >= 14:
             self.engine.set_stream_lbfgs(True)           # the streaming path runs the device L-BFGS on request only
         self._proto = first

@@ -145,6 +145,24 @@ int vqe_set_stream_grad(vqe_t* h, int enable);
  * path (a second state-sized buffer per resident stream, as vqe_set_stream_grad).  0 (default): VQE_EINVAL as before,
  * whatever vqe_set_stream_grad says.  n <= 13: accepted, no effect.  Independent of vqe_set_stream_grad. */
 int vqe_set_stream_lbfgs(vqe_t* h, int enable);
+/* Paired env-step launches (10 <= n <= 13).  1 (default): vqe_batch_run_minimize / vqe_batch_run_env_step put two
+ * environments of the batch into one workgroup (neighbours in the launch order) where the launch is the plain
+ * noiseless minimiser - no depolarising or shot noise, at most 64 parameters per circuit, no evaluation trace -, the
+ * batch has at least five parameters per circuit on average (below, pairing measured slower) and the larger LDS
+ * footprint leaves the workgroups per CU unchanged: both are evaluated in turn, then their two COBYLA
+ * updates run at the same time on two wavefronts.  Every environment's result is, bit for bit, that of the unpaired
+ * launch.  0: every launch is unpaired.  Other sizes and runs: accepted, no effect. */
+int vqe_set_env_pairing(vqe_t* h, int enable);
+/* What the last launch of an LDS-resident kernel (n <= 13) on this handle did: out[0] = 1 if it was the paired
+ * kernel, out[1] = workgroups with two environments, out[2] = workgroups of the paired kernel with one environment
+ * (the tail of the launch order), out[3] = dynamic LDS bytes per workgroup.  An unpaired launch: 0, 0, 0, bytes. */
+int vqe_last_env_pairing(vqe_t* h, int64_t out[4]);
+/* Host only: the LDS layout of a paired launch with these batch sizes (10 <= n_qubits <= 13).  out[0..7]: byte offsets
+ * of the second environment's sched, lay, cs, xm, zm, meta, sb, sidx regions; out[8]: offset of the two 64-byte
+ * environment records; out[9]: dynamic LDS bytes of the paired launch; out[10]: those of the unpaired launch (the
+ * first environment's regions and the shared ones lie below it); out[11]: bytes of the state region, which starts at
+ * offset 0. */
+int vqe_pair_lds_plan(int n_qubits, int max_ops, int max_pair, int max_params, int n_groups, int64_t out[12]);
 /* The one collective of the term-sharded sum as a library call (RCCL over xGMI; librccl is opened lazily).  Rank 0
  * makes the 128-byte id (vqe_comm_unique_id) and hands it to the other ranks by any means; every rank calls
  * vqe_comm_init on its handle; vqe_comm_allreduce_energy sums the batch's energy array (float64[batch], what

@@ -91,6 +91,9 @@ SIGNATURES = {
     "vqe_set_amplitude_shard": (C.c_int, [vp, C.c_int, C.c_int]),
     "vqe_set_stream_grad": (C.c_int, [vp, C.c_int]),
     "vqe_set_stream_lbfgs": (C.c_int, [vp, C.c_int]),
+    "vqe_set_env_pairing": (C.c_int, [vp, C.c_int]),
+    "vqe_last_env_pairing": (C.c_int, [vp, c_i64p]),
+    "vqe_pair_lds_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_i64p]),
     "vqe_term_owner": (C.c_int, [C.c_int, C.c_int, c_u64p, C.c_int, c_i32p]),
     "vqe_set_noise": (C.c_int, [vp, C.c_double, C.c_double, C.c_uint64]),
     "vqe_set_shot_noise": (C.c_int, [vp, C.c_double, C.c_uint64]),

@@ -60,6 +60,11 @@ struct vqe_handle {
   int n = 0, dev = 0;
   bool lds_path = true;
   int cu_count = 0, lds_per_cu = 0, last_wg_per_cu = 0;
+  // paired env-step launches (k_lds_minimize_pair): the switch (vqe_set_env_pairing) and what the last launch of an
+  // LDS-resident kernel did (vqe_last_env_pairing)
+  bool env_pairing = true;
+  int last_pairs = 0, last_singles = 0;
+  size_t last_lds = 0;
   hipStream_t own_stream = nullptr, stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   float last_ms = 0.f;
@@ -354,6 +359,44 @@ void report_placement(int n, int max_ops, int max_pair, int max_params, int n_gr
   out[7] = lds_launch_refusal(n, lds, max_ops, lds_per_cu) == nullptr;
 }
 
+// Paired launch (k_lds_minimize_pair): how many workgroups of a batch carry two environments.  Pairing halves the
+// rounds of workgroups a CU sees, and with them doubles the weight of the launch tail; single environments at the end
+// of the LPT order could fill it, but measured they cost more than they give (4096 environments on 512 slots: 282.5 ms
+// with none, 289.0 with 512, 286.6 with 1024; the episode's batches of 2048 likewise): every environment
+// is paired, an odd one is left over.  VQE_PAIR_SINGLES=k sets k singles aside for such measurements.
+constexpr int kPairMinMeanParams = 5;
+int env_pair_count(int batch, int /*slots*/) {
+  static const long singles = [] { const char* e = std::getenv("VQE_PAIR_SINGLES"); return e ? std::atol(e) : 0L; }();   // measurement knob
+  const int ns = (int)std::min<long>(std::max<long>(singles, 0), batch);
+  return (batch - ns) / 2;
+}
+
+template <int N>
+int launch_lds_pair(vqe_t* h, const BatchArgs& A, size_t lds, int n_pairs) {
+  if constexpr (N >= 10 && N <= 13) {
+    void (*const kernel)(BatchArgs, int) = k_lds_minimize_pair<N>;
+    const void* fn = (const void*)kernel;
+    HIP_TRY(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    {   // the unit loop addresses the state region absolutely (unit_lds_read): the dynamic LDS must start at 0
+      hipFuncAttributes fa;
+      HIP_TRY(h, hipFuncGetAttributes(&fa, fn));
+      if (fa.sharedSizeBytes != 0) return fail(h, VQE_ESTATE, "LDS-resident kernel was built with static LDS");
+    }
+    h->last_wg_per_cu = std::max(1, std::min(8, (int)(h->lds_per_cu / lds)));
+    h->last_pairs = n_pairs;
+    h->last_singles = A.batch - 2 * n_pairs;
+    h->last_lds = lds;
+    HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
+    const dim3 grid(A.batch - n_pairs), block(Geo<N>::NT);
+    hipLaunchKernelGGL(kernel, grid, block, lds, h->stream, A, n_pairs);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
+    return VQE_OK;
+  } else {
+    return fail(h, VQE_ESTATE, "no paired kernel at this size");
+  }
+}
+
 template <int N>
 int launch_lds(vqe_t* h, Run mode, BatchArgs A) {
   if (mode == Run::EnvStep) set_env_step(h, A);
@@ -366,6 +409,8 @@ int launch_lds(vqe_t* h, Run mode, BatchArgs A) {
   if (lds_pad > 0) lds += (size_t)lds_pad;
   if (const char* why = lds_launch_refusal(N, lds, A.max_ops, (size_t)h->lds_per_cu)) return fail(h, VQE_EINVAL, why);
   const bool noisy = A.noise.p1 > 0.0 || A.noise.p2 > 0.0;
+  h->last_pairs = h->last_singles = 0;
+  h->last_lds = lds;
   constexpr bool kW = false;     // up to 64 parameters per circuit: the instantiation without the workgroup-wide update
   void (*const kernel)(BatchArgs) =
       mode == Run::Energy ? k_lds_energy<N>
@@ -378,6 +423,29 @@ int launch_lds(vqe_t* h, Run mode, BatchArgs A) {
     hipFuncAttributes fa;
     HIP_TRY(h, hipFuncGetAttributes(&fa, fn));
     if (fa.sharedSizeBytes != 0) return fail(h, VQE_ESTATE, "LDS-resident kernel was built with static LDS");
+  }
+  // Two environments per workgroup: the plain noiseless minimiser on four-wave workgroups, and only where the larger
+  // LDS footprint leaves the workgroups per CU what they are (registers and LDS together: the runtime's own count)
+  static const bool pair_on = [] { const char* e = std::getenv("VQE_ENV_PAIRING"); return !(e && e[0] == '0'); }();   // A/B knob
+  if constexpr (N >= 10) {
+    // ... and from kPairMinMeanParams variables per environment on average: below, the optimiser step is shorter than what
+    // a round of the paired kernel spends on reloading an environment's scalars (measured, DESIGN 4.1: +4 % at a mean
+    // of 4 variables, -10 % at 6)
+    if (minimize && pair_on && h->env_pairing && !noisy && !wide && A.trace == nullptr && A.noise.shot_sigma == 0.0 &&
+        lds_pad <= 0 && A.batch >= 1 && h->total_params >= (int64_t)kPairMinMeanParams * A.batch) {
+      const size_t plds = pair_lds_plan(N, A.max_ops, A.max_params, A.ham.n_groups, A.max_pair).bytes;
+      int occ_single = 0, occ_pair = -1;
+      if (plds <= (size_t)h->lds_per_cu) {
+        HIP_TRY(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_single, fn, Geo<N>::NT, lds));
+        void (*const pk)(BatchArgs, int) = k_lds_minimize_pair<N>;
+        HIP_TRY(h, hipFuncSetAttribute((const void*)pk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)plds));
+        HIP_TRY(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_pair, (const void*)pk, Geo<N>::NT, plds));
+      }
+      if (occ_pair == occ_single && occ_pair > 0) {
+        const int n_pairs = env_pair_count(A.batch, occ_pair * h->cu_count);
+        if (n_pairs > 0 || A.batch == 1) return launch_lds_pair<N>(h, A, plds, n_pairs);
+      }
+    }
   }
   h->last_wg_per_cu = std::max(1, std::min(8, (int)(h->lds_per_cu / lds)));
   HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
@@ -2098,6 +2166,33 @@ int vqe_set_amplitude_shard(vqe_t* h, int rank, int world) {
 int vqe_set_stream_grad(vqe_t* h, int enable) {
   if (!h) return VQE_EINVAL;
   h->stream_grad = enable != 0;      // (n <= 13: the LDS-resident kernel serves every gradient; nothing to switch)
+  return VQE_OK;
+}
+
+int vqe_set_env_pairing(vqe_t* h, int enable) {
+  if (!h) return VQE_EINVAL;
+  h->env_pairing = enable != 0;
+  return VQE_OK;
+}
+
+int vqe_last_env_pairing(vqe_t* h, int64_t out[4]) {
+  if (!h || !out) return VQE_EINVAL;
+  out[0] = h->last_pairs > 0 || h->last_singles > 0;
+  out[1] = h->last_pairs;
+  out[2] = h->last_singles;
+  out[3] = (int64_t)h->last_lds;
+  return VQE_OK;
+}
+
+int vqe_pair_lds_plan(int n_qubits, int max_ops, int max_pair, int max_params, int n_groups, int64_t out[12]) {
+  if (!out || n_qubits < 10 || n_qubits > 13 || max_ops < 1 || max_pair < 0 || max_pair > max_ops || max_params < 1 || n_groups < 0)
+    return VQE_EINVAL;
+  const PairLdsPlan p = pair_lds_plan(n_qubits, max_ops, max_params, n_groups, max_pair);
+  out[0] = (int64_t)p.sched; out[1] = (int64_t)p.lay; out[2] = (int64_t)p.cs; out[3] = (int64_t)p.xm;
+  out[4] = (int64_t)p.zm; out[5] = (int64_t)p.meta; out[6] = (int64_t)p.sb; out[7] = (int64_t)p.sidx;
+  out[8] = (int64_t)p.rec; out[9] = (int64_t)p.bytes;
+  out[10] = (int64_t)lds_bytes(n_qubits, max_ops, max_params, n_groups, max_pair, false);   // the single launch
+  out[11] = (int64_t)((size_t)16 << n_qubits);      // the state region: [0, out[11])
   return VQE_OK;
 }
 

@@ -483,6 +483,32 @@ __host__ __device__ inline size_t lds_bytes(int n, int max_ops, int max_params, 
   return ((lds_bytes_base(n, max_ops, max_params, n_groups, max_pair) + 15) & ~(size_t)15) + r + cobyla_tile_bytes(n, max_params, wide);
 }
 
+// Paired launch (k_lds_minimize_pair, n >= 10, not WIDE): a workgroup carries two environments.  The records of the
+// compiled circuit exist once per environment - environment 0 keeps the places of the single layout, environment 1
+// has a second set behind it - and everything else (state region, Hamiltonian records, red) is shared.
+struct PairLdsPlan {
+  // byte offsets of environment 1's regions from the start of the dynamic LDS
+  size_t sched, lay, cs, xm, zm, meta, sb, sidx;
+  size_t rec;      // kPairRecBytes per environment: the scalars of the environment that is not being evaluated
+  size_t bytes;    // dynamic LDS of the paired launch
+};
+constexpr size_t kPairRecBytes = 64;
+__host__ __device__ inline PairLdsPlan pair_lds_plan(int n, int max_ops, int max_params, int n_groups, int max_pair) {
+  PairLdsPlan p;
+  size_t o = (lds_bytes_base(n, max_ops, max_params, n_groups, max_pair) + 15) & ~(size_t)15;
+  p.sched = o; o += (size_t)16 * (max_ops + max_pair + 2);
+  p.lay = o; o += (size_t)32 * (max_pair + 2);
+  p.cs = o; o += (size_t)16 * max_params;
+  p.xm = o; o += 128;
+  p.zm = o; o += 128;
+  p.meta = o; o += 32;
+  p.sb = o; o += 64;
+  p.sidx = o; o += ((size_t)2 * max_ops + 15) & ~(size_t)15;
+  p.rec = o; o += 2 * kPairRecBytes;
+  p.bytes = o;
+  return p;
+}
+
 // Where the optimiser's arrays of ONE circuit live and which context of cobyla_m0.h updates them: the decision of
 // StagedCobyla::init, which vqe_cobyla_placement reports to the tests from this very function.
 //   n: qubits; wide: the launch runs the WIDE variant of k_lds_minimize; resident: the launch has an LDS region for
@@ -531,7 +557,7 @@ __host__ __device__ __forceinline__ CobPlacement cobyla_placement(int n, bool wi
 }
 
 __device__ __forceinline__ Lds carve(unsigned char* base, int n, int max_ops, int max_params, int n_groups, int max_pair,
-                                     bool wide = false) {
+                                     bool wide = false, int env = 0) {
   const int ng = n_groups > 0 ? n_groups : 1;
   Lds l;
   l.psi = (double2*)base; base += (size_t)16 << n;
@@ -561,6 +587,18 @@ __device__ __forceinline__ Lds carve(unsigned char* base, int n, int max_ops, in
                ? (double*)((unsigned char*)l.psi + ((lds_bytes_base(n, max_ops, max_params, n_groups, max_pair) + 15) & ~(size_t)15) +
                            cobyla_resident_bytes(n, max_ops, max_params, n_groups, max_pair))
                : nullptr;
+  if (env) {      // paired launch: the second environment's records of the compiled circuit (pair_lds_plan)
+    const PairLdsPlan p = pair_lds_plan(n, max_ops, max_params, n_groups, max_pair);
+    unsigned char* const b0 = (unsigned char*)l.psi;
+    l.sched = (Op*)(b0 + p.sched);
+    l.lay = (LayoutRec*)(b0 + p.lay);
+    l.cs = (double2*)(b0 + p.cs);
+    l.xm = (uint32_t*)(b0 + p.xm);
+    l.zm = (uint32_t*)(b0 + p.zm);
+    l.meta = (int32_t*)(b0 + p.meta);
+    l.sb = (uint32_t*)(b0 + p.sb);
+    l.sidx = (uint16_t*)(b0 + p.sidx);
+  }
   return l;
 }
 
@@ -1962,6 +2000,235 @@ __global__ void __launch_bounds__(Geo<N>::NT, Geo<N>::WPS) k_lds_minimize(BatchA
     }
   }
   if (threadIdx.x == 0) { A.fout[b] = fret; A.nfev[b] = nfev; }
+}
+
+// ---- paired form: a workgroup carries two environments ------------------------------------------------------------
+// The scalars of an environment, parked in LDS (PairLdsPlan::rec) while the other one is evaluated.  Every decision
+// that leads to a barrier is taken from these words, read behind a barrier - never from a wave's own variables.
+enum PairRecWord {
+  PR_B = 0, PR_P, PR_HOLE, PR_SKIP, PR_SKIP_END,
+  PR_PHASE,         // 0 = single evaluation, 1 = COBYLA loop, 2 = post-action evaluation, 3 = finished
+  PR_COMPILE,       // the coming evaluation compiles its circuit first
+  PR_WANT, PR_NFVALS,   // published by the wave that ran the optimiser
+  PR_WORDS, PR_STAGED,  // cobyla_placement of this circuit
+  PR_FLAST = 12,    // (a double: words 12, 13) the value of the last evaluation
+};
+__device__ __forceinline__ int pair_rec_get(const int* rec, int w) { return __builtin_amdgcn_readfirstlane(rec[w]); }
+template <class T>
+__device__ __forceinline__ T* pair_uniform_ptr(T* p) {      // a pointer every lane holds alike, as scalar registers
+  const uint64_t v = (uint64_t)(uintptr_t)p;
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+  return (T*)(uintptr_t)(((uint64_t)hi << 32) | lo);
+}
+
+// Copy na double2 from sa to da and nb from sb to db (either may be 0), every load of a chunk issued before its first
+// store (StagedCobyla::in).  No barrier.
+template <int NT, class SA, class DA>
+__device__ __forceinline__ void pair_stage_copy(const SA* sa, DA* da, int na, const SA* sb, DA* db, int nb) {
+  constexpr int kStage = 6;
+  const int nw = na + nb;
+  for (int i0 = threadIdx.x; i0 < nw; i0 += kStage * NT) {
+    double2 v[kStage];
+#pragma unroll
+    for (int k = 0; k < kStage; ++k) {
+      int i = i0 + k * NT;
+      i = i < nw ? i : nw - 1;
+      v[k] = i < na ? sa[i] : sb[i - na];
+    }
+#pragma unroll
+    for (int k = 0; k < kStage; ++k) asm volatile("" : "+v"(v[k].x), "+v"(v[k].y));
+#pragma unroll
+    for (int k = 0; k < kStage; ++k) {
+      const int i = i0 + k * NT;
+      if (i < na) da[i] = v[k];
+      else if (i < nw) db[i - na] = v[k];
+    }
+  }
+}
+
+// Workgroup i < n_pairs runs circuits order[2i] and order[2i + 1] (neighbours in the LPT ranking); workgroup
+// i >= n_pairs runs the single circuit order[n_pairs + i].  A round: evaluate environment 0, evaluate environment 1
+// (the state region serves one at a time), then ONE optimiser step for both - their arrays staged into the two halves
+// of the dead state region, wave 0 updating the lower half while wave 1 updates the upper one, each with the code, the
+// order and the bits of the single kernel.  Arrays that do not fit a half are updated one environment after the other
+// through the whole region (or in the global scratch), as the single kernel does.
+// Noiseless, not WIDE, no trace, no shot noise (launch_lds).
+template <int N>
+__global__ void __launch_bounds__(Geo<N>::NT, Geo<N>::WPS) k_lds_minimize_pair(BatchArgs A, int n_pairs) {
+  constexpr int kThreads = Geo<N>::NT;
+  static_assert(N >= 10 && kThreads >= 256, "two optimiser waves and two spare ones");
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const PairLdsPlan plan = pair_lds_plan(N, A.max_ops, A.max_params, A.ham.n_groups, A.max_pair);
+  int* const recs = (int*)(smem + plan.rec);
+  constexpr int kRecWords = (int)(kPairRecBytes / sizeof(int));
+  const int wg = blockIdx.x;
+  const int nenv = wg < n_pairs ? 2 : 1;
+  const int first = wg < n_pairs ? 2 * wg : n_pairs + wg;
+  constexpr int kHalfDoubles = (int)(((size_t)16 << N) / 16);
+  {
+    const Lds L = carve(smem, N, A.max_ops, A.max_params, A.ham.n_groups, A.max_pair);
+    stage_groups(A.ham, L);
+    stage_cls<N>(A.ham, L);
+    // start(): one environment after the other, through the single kernel's path
+    for (int e = 0; e < nenv; ++e) {
+      const int b = __builtin_amdgcn_readfirstlane(A.order[first + e]);
+      const int P = A.par_count[b];
+      const PreAction pa = pre_action(A.gates + A.gate_begin[b], A.gate_count[b], A.new_gate ? A.new_gate[b] : -1);
+      const int p_hole = pa.hole;
+      const int Popt = P - (p_hole >= 0);
+      int* const rec = recs + e * kRecWords;
+      int want = 0, nfvals = 0, words = 0, staged = 0;
+      if (Popt > 0) {
+        StagedCobyla<N, false> sc;
+        sc.cs_ready = false;
+        sc.init(pair_uniform_ptr(A.scratch + A.scratch_begin[b]), L, __builtin_amdgcn_readfirstlane(Popt));
+        const double* theta = A.theta + A.par_begin[b];
+        for (int j = threadIdx.x; j < P; j += kThreads)
+          if (j != p_hole) sc.x()[j - (p_hole >= 0 && j > p_hole)] = theta[j];
+        __syncthreads();
+        want = sc.start(A.rhobeg, A.rhoend, A.maxfun, false);   // always asks for f(x0)
+        nfvals = sc.nfvals;
+        words = sc.words;
+        staged = sc.staged;
+      }
+      if (threadIdx.x == 0) {
+        rec[PR_B] = b; rec[PR_P] = P; rec[PR_HOLE] = p_hole; rec[PR_SKIP] = pa.skip; rec[PR_SKIP_END] = pa.skip_end;
+        rec[PR_PHASE] = Popt > 0 ? 1 : 0;
+        rec[PR_COMPILE] = 1;
+        rec[PR_WANT] = want; rec[PR_NFVALS] = nfvals; rec[PR_WORDS] = words; rec[PR_STAGED] = staged;
+      }
+    }
+    if (nenv == 1 && threadIdx.x == 0) {      // a lone environment: the second record is a finished one
+      int* const rec = recs + kRecWords;
+      rec[PR_PHASE] = 3; rec[PR_COMPILE] = 0; rec[PR_WANT] = 0; rec[PR_WORDS] = 0; rec[PR_STAGED] = 0;
+    }
+    __syncthreads();
+  }
+  for (;;) {
+    // ---- the evaluations, one environment at a time: ONE call site, the scalars reloaded from the record
+    for (int e = 0; e < 2; ++e) {
+      int* const rec = recs + e * kRecWords;
+      const int phase = pair_rec_get(rec, PR_PHASE);
+      if (phase == 3) continue;
+      const int b = pair_rec_get(rec, PR_B);
+      const int P = pair_rec_get(rec, PR_P);
+      const int p_hole = pair_rec_get(rec, PR_HOLE);
+      const double* theta = A.theta + A.par_begin[b];
+      double* xout = A.xout + A.par_begin[b];
+      const Lds L = carve(smem, N, A.max_ops, A.max_params, A.ham.n_groups, A.max_pair, false, e);
+      const double* th = phase == 0 ? theta : (phase == 1 ? A.scratch + A.scratch_begin[b] : xout);
+      const int ph = phase == 2 ? -1 : p_hole;
+      if (pair_rec_get(rec, PR_COMPILE)) {
+        const int sk = phase == 2 ? -1 : pair_rec_get(rec, PR_SKIP);
+        const int ske = phase == 2 ? 0 : pair_rec_get(rec, PR_SKIP_END);
+        compile_all<N>(A, b, 0, L, sk, true, false, ske);
+      }
+      const double ev = lds_evaluate<N, false>(A, L, th, P, ph);
+      // (the barriers of the evaluation lie between the reads of the record above and the writes below)
+      int next = phase;
+      if (phase == 0) {
+        for (int j = threadIdx.x; j < P; j += kThreads) {
+          xout[j] = A.env_step ? (double)(float)theta[j] : theta[j];
+          A.xraw[A.par_begin[b] + j] = theta[j];
+        }
+        next = A.env_step ? 2 : 3;
+        if (threadIdx.x == 0) { A.nfev[b] = 1; if (next == 3) A.fout[b] = ev; }
+      } else if (phase == 2) {
+        next = 3;
+        if (threadIdx.x == 0) A.fout[b] = ev;      // (nfev: written when the optimiser finished)
+      }
+      if (threadIdx.x == 0) {
+        if (phase == 1) *(double*)(rec + PR_FLAST) = ev;
+        rec[PR_PHASE] = next;
+        rec[PR_COMPILE] = next == 2;
+      }
+    }
+    __syncthreads();      // records and xout visible
+    // ---- the optimiser step of every environment in its COBYLA loop
+    const bool t0 = pair_rec_get(recs, PR_PHASE) == 1;
+    const bool t1 = pair_rec_get(recs + kRecWords, PR_PHASE) == 1;
+    if (!t0 && !t1) {
+      const bool live0 = pair_rec_get(recs, PR_PHASE) != 3;
+      const bool live1 = pair_rec_get(recs + kRecWords, PR_PHASE) != 3;
+      if (!live0 && !live1) break;
+      continue;      // post-action evaluations are left
+    }
+    const int w0 = pair_rec_get(recs, PR_WORDS), w1 = pair_rec_get(recs + kRecWords, PR_WORDS);
+    const bool joint = t0 && t1 && pair_rec_get(recs, PR_STAGED) && pair_rec_get(recs + kRecWords, PR_STAGED) &&
+                       w0 <= kHalfDoubles && w1 <= kHalfDoubles;
+    const int npass = joint ? 1 : 2;
+#ifdef VQE_STAMPS
+    const long long tt0 = clock64();
+#endif
+    for (int pass = 0; pass < npass; ++pass) {
+      if (!joint && !(pass == 0 ? t0 : t1)) continue;
+      // environments of this pass: ea on wave 0 (arrays at the bottom of the state region) and, joint, eb = 1 on wave 1
+      const int ea = joint ? 0 : pass;
+      int* const ra = recs + ea * kRecWords;
+      int* const rb = recs + kRecWords;
+      const int ba = pair_rec_get(ra, PR_B);
+      double* const ga = A.scratch + A.scratch_begin[ba];
+      double* const gb = joint ? A.scratch + A.scratch_begin[pair_rec_get(rb, PR_B)] : ga;
+      const int wa = pair_rec_get(ra, PR_WORDS);
+      const bool sa = pair_rec_get(ra, PR_STAGED) != 0;
+      const int nwa = sa ? (wa + 1) / 2 : 0, nwb = joint ? (w1 + 1) / 2 : 0;
+      double* const la = (double*)smem;
+      double* const lb = la + kHalfDoubles;
+      if (sa) {
+        pair_stage_copy<kThreads>((const double2*)ga, (double2*)la, nwa, (const double2*)gb, (double2*)lb, nwb);
+        __syncthreads();
+      }
+      const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+      if (wave < (joint ? 2 : 1)) {
+        int* const r = wave ? rb : ra;
+        const int P = pair_rec_get(r, PR_P);
+        const double f = *(const double*)(r + PR_FLAST);
+        StagedCobyla<N, false> sc;
+        sc.n = __builtin_amdgcn_readfirstlane(P - (pair_rec_get(r, PR_HOLE) >= 0));
+        sc.red = nullptr; sc.tile = nullptr;
+        // (the half of a wave is wave-uniform: a scalar register, as call() asks)
+        const uint32_t half = (uint32_t)__builtin_amdgcn_readfirstlane(wave ? kHalfDoubles * (int)sizeof(double) : 0);
+        lds_double* const lmem = (lds_double*)(uintptr_t)half;      // the state region starts at LDS address 0
+        if (sa) sc.template call<false, typename StagedCobyla<N, false>::CobL>(lmem, f, 0.0, 0.0, 0);
+        else sc.template call<false, typename StagedCobyla<N, false>::CobG>(pair_uniform_ptr(ga), f, 0.0, 0.0, 0);
+        if ((threadIdx.x & 63) == 0) { r[PR_WANT] = sc.want; r[PR_NFVALS] = sc.nfvals; }
+      }
+      __syncthreads();      // want / nfvals published; the arrays are final
+      if (sa) {
+        pair_stage_copy<kThreads>((const double2*)la, (double2*)ga, nwa, (const double2*)lb, (double2*)gb, nwb);
+        __syncthreads();
+      }
+    }
+#ifdef VQE_STAMPS   // the optimiser step of the workgroup: once per round, for one or two environments
+    if (threadIdx.x == 0) atomicAdd(A.dbg + 3, (unsigned long long)(clock64() - tt0));
+#endif
+    // ---- environments whose optimiser has finished: the result, then (env_step) the post-action evaluation
+    for (int e = 0; e < 2; ++e) {
+      int* const rec = recs + e * kRecWords;
+      if (!(e == 0 ? t0 : t1) || pair_rec_get(rec, PR_WANT)) continue;
+      const int b = pair_rec_get(rec, PR_B);
+      const int P = pair_rec_get(rec, PR_P);
+      const int p_hole = pair_rec_get(rec, PR_HOLE);
+      const double* theta = A.theta + A.par_begin[b];
+      double* xout = A.xout + A.par_begin[b];
+      const double* g = A.scratch + A.scratch_begin[b];
+      for (int j = threadIdx.x; j < P; j += kThreads) {
+        const double v = (j == p_hole) ? theta[j] : g[j - (p_hole >= 0 && j > p_hole)];
+        xout[j] = A.env_step ? (double)(float)v : v;
+        A.xraw[A.par_begin[b] + j] = v;
+      }
+      if (threadIdx.x == 0) {
+        const double* st = g + pair_rec_get(rec, PR_WORDS) - cby::kStateDoubles;
+        const double fret = ((int)st[11] == cby::DONE_RHOEND && (int)st[10] == 1) ? *(const double*)(rec + PR_FLAST) : st[4];
+        A.nfev[b] = rec[PR_NFVALS];
+        if (!A.env_step) A.fout[b] = fret;
+        rec[PR_PHASE] = A.env_step ? 2 : 3;
+        rec[PR_COMPILE] = A.env_step != 0;
+      }
+    }
+    __syncthreads();      // xout and the records visible to the whole workgroup
+  }
 }
 
 }  // namespace vqe

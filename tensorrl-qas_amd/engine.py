@@ -73,6 +73,16 @@ def cobyla_placement(n_qubits, max_ops, max_pair, max_params, n_groups, n_params
     return _placement(out)
 
 
+def pair_lds_plan(n_qubits, max_ops, max_pair, max_params, n_groups):
+    """vqe_pair_lds_plan (host only): the LDS layout of a paired minimiser launch with these batch sizes."""
+    out = (C.c_int64 * 12)()
+    rc = _lib.load().vqe_pair_lds_plan(int(n_qubits), int(max_ops), int(max_pair), int(max_params), int(n_groups), out)
+    if rc != 0:
+        raise ValueError("vqe_pair_lds_plan: argument out of range")
+    names = ("sched", "lay", "cs", "xm", "zm", "meta", "sb", "sidx", "rec", "bytes", "single_bytes", "state_bytes")
+    return {k: int(v) for k, v in zip(names, out)}
+
+
 class VQEEngine:
     """One handle = one (n_qubits, initial state, Hamiltonian) problem on one GPU."""
 
@@ -229,6 +239,18 @@ class VQEEngine:
         resident stream).  Off by default: those calls then raise at n >= 14, whatever set_stream_grad says.  No
         effect at n <= 13."""
         self._chk(self._lib.vqe_set_stream_lbfgs(self._h, 1 if enable else 0))
+
+    def set_env_pairing(self, enable: bool = True):
+        """10 <= n <= 13: let batch_run_minimize / batch_run_env_step put two environments into one workgroup where
+        the launch allows it (vqe_set_env_pairing).  On by default; the results are those of the unpaired launch, bit
+        for bit."""
+        self._chk(self._lib.vqe_set_env_pairing(self._h, 1 if enable else 0))
+
+    def last_env_pairing(self):
+        """What the last launch of an LDS-resident kernel did (vqe_last_env_pairing)."""
+        out = (C.c_int64 * 4)()
+        self._chk(self._lib.vqe_last_env_pairing(self._h, out))
+        return {"paired": bool(out[0]), "pairs": int(out[1]), "singles": int(out[2]), "lds_bytes": int(out[3])}
 
     def set_noise(self, p1: float, p2: float, seed: int):
         self._chk(self._lib.vqe_set_noise(self._h, float(p1), float(p2), C.c_uint64(int(seed) & (2 ** 64 - 1))))

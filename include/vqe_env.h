@@ -88,8 +88,15 @@ int vqe_vecenv_opt_ang(vqe_vecenv_t* v, int32_t env, double* out, int32_t* n);
  * The reference has no counterpart: its optimiser is the config's optim_alg, one environment at a time.  Refused
  * (VQE_ESTATE) between step_begin and step_end, and for VQE_ENV_OPT_LBFGS on a noisy batch unless the engine is in the
  * exact channel mode (vqe_set_noise_mode 1; its steps then need vqe_set_dm_batched and vqe_set_dm_grad). */
-enum { VQE_ENV_OPT_COBYLA = 0, VQE_ENV_OPT_LBFGS = 1 };
+enum { VQE_ENV_OPT_COBYLA = 0, VQE_ENV_OPT_LBFGS = 1, VQE_ENV_OPT_SPSA = 2 };
 int vqe_vecenv_set_optimizer(vqe_vecenv_t* v, int kind, const vqe_lbfgs_opts_t* opts);
+/* VQE_ENV_OPT_SPSA: every following step launches vqe_batch_run_env_step_spsa with `opts` (not NULL: VQE_EINVAL; start
+ * from vqe_spsa_default_opts and set maxiter to half the config's maxfun to keep nfev within COBYLA's budget).  It has
+ * options of another type, hence an entry point of its own; vqe_vecenv_set_optimizer(v, VQE_ENV_OPT_SPSA, ...) is
+ * VQE_EINVAL.  Noiseless and noisy batches (Pauli trajectories, shot noise) alike; what the engine refuses (exact
+ * channel mode, Kraus channels, n >= 14, bad options) it refuses at the step.  Refused (VQE_ESTATE) between step_begin
+ * and step_end.  The reference has no counterpart. */
+int vqe_vecenv_set_optimizer_spsa(vqe_vecenv_t* v, const vqe_spsa_opts_t* opts);
 /* kernel time of the last launch (HIP events) */
 int vqe_vecenv_last_kernel_ms(vqe_vecenv_t* v, float* ms);
 

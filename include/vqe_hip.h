@@ -504,6 +504,47 @@ int vqe_batch_run_minimize_lbfgs(vqe_t* h, const vqe_lbfgs_opts_t* opts);
 int vqe_batch_run_env_step_lbfgs(vqe_t* h, const vqe_lbfgs_opts_t* opts);
 /* replaces: result.nit / result.status of those scipy calls (status numbered as above); either pointer may be NULL */
 int vqe_batch_fetch_lbfgs_info(vqe_t* h, int32_t* nit /* batch */, int32_t* status /* batch */);
+/* ---- device Adam-SPSA: a two-evaluation optimiser for stochastic energies -------------------------
+ * replaces: nothing in the reference - its configs carry the [non_local_opt] keys a, alpha, c, gamma, lamda, beta_1,
+ * beta_2, but no code path of it reads them.  Simultaneous-perturbation gradient estimates fed to Adam, the whole loop
+ * in one launch, one workgroup per circuit (csrc/vqe_spsa.h; the update of an element and the schedule: csrc/spsa_m0.h;
+ * DESIGN 4.22).  With K = maxiter, P parameters and `hole` the new gate's angle of an env-step (or none):
+ *   x = x0;  m = v = 0;  b1p = b2p = 1
+ *   for k = 0 .. K-1:
+ *       a_k = a / (k + 1 + stability)^alpha;   c_k = c / (k + 1)^gamma
+ *       key = noise_key(seed, b, k)                              (the engine's counter RNG; b = position in the batch)
+ *       D_j = +1 if noise_uniform_k(key, j) < 0.5 else -1        (j = 0 .. P-1; D_hole = 0)
+ *       f+ = E(x + c_k D), evaluation id eval_base + 2k;   f- = E(x - c_k D), evaluation id eval_base + 2k + 1
+ *       g_j = (f+ - f-) / (2 c_k) * D_j
+ *       b1k = beta_1 / (k + 1)^lamda
+ *       m = b1k m + (1 - b1k) g;   v = beta_2 v + (1 - beta_2) g*g;   b1p *= b1k;   b2p *= beta_2
+ *       x_j -= a_k * (m_j / (1 - b1p)) / (sqrt(v_j / (1 - b2p)) + eps)
+ * E is the handle's mode 0 energy: noiseless, or one draw of the Pauli errors (vqe_set_noise / vqe_set_noise_pauli) keyed
+ * by the evaluation id, plus the shot-noise term of vqe_set_shot_noise - what the device COBYLA evaluates.  `seed` is the
+ * seed of the perturbations alone (not the noise seed): the optimiser runs on a handle without noise.
+ * Plain minimise: one more evaluation f = E(x_K), id eval_base + 2K; nfev = 2K + 1; x and xopt are x_K.
+ * Env-step: the loop runs on the circuit WITHOUT gate new_gate[b], the new rotation keeps its theta0 value, x is x_K
+ * rounded through float32 and f the energy of the FULL circuit there, id eval_base + 2K; nfev = 2K (the closing
+ * evaluation is not counted, as with the other two optimisers).
+ * K = 0, or a circuit without an optimised parameter: that closing evaluation alone, id eval_base, nfev = 1.
+ * After a run eval_base has advanced by 2K + 1.  The results have the same bits for the same (seed, b, noise seed,
+ * eval_base), whatever the batch size and the other circuits.
+ * VQE_EINVAL before anything is launched (the handle stays usable): a non-finite option, maxiter < 0, a <= 0, c <= 0,
+ * eps <= 0, alpha / gamma / lamda / stability < 0, beta_1 or beta_2 outside [0, 1); n_qubits >= 14.
+ * VQE_ESTATE: the exact channel mode (vqe_set_noise_mode 1), a Kraus override (with or without vqe_set_kraus_traj),
+ * term- and amplitude-sharded handles.  A refused call changes nothing, eval_base included.
+ * opts == NULL on vqe_minimize_spsa / vqe_batch_run_*_spsa: VQE_EINVAL (the shipped configs carry no usable defaults;
+ * start from vqe_spsa_default_opts). */
+typedef struct { int32_t maxiter; double a, alpha, stability, c, gamma, beta_1, beta_2, lamda, eps;
+                 uint64_t seed; } vqe_spsa_opts_t;
+int vqe_spsa_default_opts(vqe_spsa_opts_t* o);             /* 100, 0.1, 0.602, 0, 0.1, 0.101, 0.9, 0.999, 0, 1e-8, 0 */
+/* one such run on the circuit of vqe_set_circuit; nfev may be NULL */
+int vqe_minimize_spsa(vqe_t* h, const double* x0, const vqe_spsa_opts_t* opts, double* x, double* f, int32_t* nfev);
+/* B such runs on the resident batch from x0 = theta0.  vqe_batch_fetch, vqe_batch_fetch_xopt, vqe_batch_energy_devptr,
+ * vqe_batch_copy_energy, vqe_last_kernel_ms and - after vqe_batch_set_trace(1) - vqe_batch_fetch_trace serve these
+ * launches as they serve COBYLA's; the trace holds 2K + 1 rows (evaluation e in row e; an env-step leaves row 2K zero). */
+int vqe_batch_run_minimize_spsa(vqe_t* h, const vqe_spsa_opts_t* opts);
+int vqe_batch_run_env_step_spsa(vqe_t* h, const vqe_spsa_opts_t* opts);
 /* ---- device Lanczos: the extreme eigenpair of the Hamiltonian ------------------------------------
  * The lowest (which = 0) or highest (which = 1) eigenvalue of the handle's Hamiltonian and its eigenvector, by Lanczos
  * on the device: a stored basis of at most max_basis vectors (complex128[2^n] each, in global memory; fewer when 2^n

@@ -30,6 +30,13 @@ class LbfgsOpts(C.Structure):
                 ("gtol", C.c_double), ("ftol", C.c_double), ("c1", C.c_double)]
 
 
+class SpsaOpts(C.Structure):
+    """vqe_spsa_opts_t of include/vqe_hip.h"""
+    _fields_ = [("maxiter", C.c_int32), ("a", C.c_double), ("alpha", C.c_double), ("stability", C.c_double),
+                ("c", C.c_double), ("gamma", C.c_double), ("beta_1", C.c_double), ("beta_2", C.c_double),
+                ("lamda", C.c_double), ("eps", C.c_double), ("seed", C.c_uint64)]
+
+
 class LanczosOpts(C.Structure):
     """vqe_lanczos_opts_t of include/vqe_hip.h"""
     _fields_ = [("which", C.c_int32), ("max_basis", C.c_int32), ("max_matvec", C.c_int32), ("check_every", C.c_int32),
@@ -118,6 +125,10 @@ SIGNATURES = {
     "vqe_batch_run_minimize_lbfgs": (C.c_int, [vp, C.POINTER(LbfgsOpts)]),
     "vqe_batch_run_env_step_lbfgs": (C.c_int, [vp, C.POINTER(LbfgsOpts)]),
     "vqe_batch_fetch_lbfgs_info": (C.c_int, [vp, c_i32p, c_i32p]),
+    "vqe_spsa_default_opts": (C.c_int, [C.POINTER(SpsaOpts)]),
+    "vqe_minimize_spsa": (C.c_int, [vp, c_f64p, C.POINTER(SpsaOpts), c_f64p, c_f64p, c_i32p]),
+    "vqe_batch_run_minimize_spsa": (C.c_int, [vp, C.POINTER(SpsaOpts)]),
+    "vqe_batch_run_env_step_spsa": (C.c_int, [vp, C.POINTER(SpsaOpts)]),
     "vqe_lanczos_default_opts": (C.c_int, [C.POINTER(LanczosOpts)]),
     "vqe_lanczos": (C.c_int, [vp, C.POINTER(LanczosOpts), c_f64p, c_f64p, c_f64p]),
     "vqe_lanczos_dev": (C.c_int, [vp, C.POINTER(LanczosOpts), c_f64p, vp, c_f64p]),
@@ -166,6 +177,7 @@ SIGNATURES.update({
     "vqe_vecenv_opt_ang": (C.c_int, [vp, C.c_int32, c_f64p, c_i32p]),
     "vqe_vecenv_last_kernel_ms": (C.c_int, [vp, C.POINTER(C.c_float)]),
     "vqe_vecenv_set_optimizer": (C.c_int, [vp, C.c_int, C.POINTER(LbfgsOpts)]),
+    "vqe_vecenv_set_optimizer_spsa": (C.c_int, [vp, C.POINTER(SpsaOpts)]),
 })
 
 class ResidentOpts(C.Structure):

@@ -65,6 +65,7 @@ struct vqe_vecenv {
   bool pending = false;
   int optimizer = VQE_ENV_OPT_COBYLA;      // vqe_vecenv_set_optimizer
   vqe_lbfgs_opts_t lbfgs{};
+  vqe_spsa_opts_t spsa{};                  // vqe_vecenv_set_optimizer_spsa
   // flat batch description (reused)
   std::vector<int64_t> gate_off, par_off;
   std::vector<int32_t> kind, q0, q1, pidx, new_gate, nfev;
@@ -321,9 +322,9 @@ int vqe_vecenv_step_begin(vqe_vecenv_t* v, const int32_t* actions) {
   int rc = vqe_batch_load(v->eng, B, v->gate_off.data(), v->kind.data(), v->q0.data(), v->q1.data(), v->pidx.data(),
                           v->par_off.data(), v->theta.data());
   if (!rc) rc = vqe_batch_set_new_gate(v->eng, v->new_gate.data());
-  if (!rc) rc = v->optimizer == VQE_ENV_OPT_LBFGS
-                    ? vqe_batch_run_env_step_lbfgs(v->eng, &v->lbfgs)
-                    : vqe_batch_run_env_step(v->eng, 1.0, 1e-4, v->cfg.maxfun);   // scipy 1.15 COBYLA defaults (:478)
+  if (!rc) rc = v->optimizer == VQE_ENV_OPT_LBFGS  ? vqe_batch_run_env_step_lbfgs(v->eng, &v->lbfgs)
+                : v->optimizer == VQE_ENV_OPT_SPSA ? vqe_batch_run_env_step_spsa(v->eng, &v->spsa)
+                : vqe_batch_run_env_step(v->eng, 1.0, 1e-4, v->cfg.maxfun);   // scipy 1.15 COBYLA defaults (:478)
   if (rc) return fail(v, rc, std::string("engine: ") + vqe_last_error(v->eng));
   v->pending = true;
   return VQE_OK;
@@ -446,6 +447,7 @@ int vqe_vecenv_opt_ang(vqe_vecenv_t* v, int32_t b, double* out, int32_t* n) {
 
 int vqe_vecenv_set_optimizer(vqe_vecenv_t* v, int kind, const vqe_lbfgs_opts_t* opts) {
   if (!v) return VQE_EINVAL;
+  if (kind == VQE_ENV_OPT_SPSA) return fail(v, VQE_EINVAL, "VQE_ENV_OPT_SPSA is set with its own options: vqe_vecenv_set_optimizer_spsa");
   if (kind != VQE_ENV_OPT_COBYLA && kind != VQE_ENV_OPT_LBFGS) return fail(v, VQE_EINVAL, "unknown optimiser kind");
   if (v->pending) return fail(v, VQE_ESTATE, "set_optimizer between step_begin and step_end");
   if (kind == VQE_ENV_OPT_LBFGS) {
@@ -462,6 +464,16 @@ int vqe_vecenv_set_optimizer(vqe_vecenv_t* v, int kind, const vqe_lbfgs_opts_t* 
     v->lbfgs = *opts;
   }
   v->optimizer = kind;
+  return VQE_OK;
+}
+
+int vqe_vecenv_set_optimizer_spsa(vqe_vecenv_t* v, const vqe_spsa_opts_t* opts) {
+  if (!v) return VQE_EINVAL;
+  if (v->pending) return fail(v, VQE_ESTATE, "set_optimizer between step_begin and step_end");
+  if (!opts) return fail(v, VQE_EINVAL, "VQE_ENV_OPT_SPSA needs its options");
+  // (the options and the handle's state are checked by the engine at every step, before it loads anything)
+  v->spsa = *opts;
+  v->optimizer = VQE_ENV_OPT_SPSA;
   return VQE_OK;
 }
 

@@ -9,6 +9,7 @@
 #include "vqe_dm_grad.h"
 #include "vqe_grad.h"
 #include "vqe_lbfgs.h"
+#include "vqe_spsa.h"
 #include "vqe_stream_lbfgs.h"
 #include "vqe_lanczos.h"
 #include "vqe_qjump.h"
@@ -174,6 +175,9 @@ struct vqe_handle {
   DevBuf<double> lb_work;
   DevBuf<int32_t> lb_nit, lb_status;
   int lb_batch = 0;      // circuits of the last L-BFGS run on the resident batch (0: none)
+  // device Adam-SPSA (vqe_spsa.h): per-workgroup slices of x, m, v and the trial point; the options of the run
+  DevBuf<double> spsa_work;
+  DevBuf<SpsaOpts> spsa_opts;
   // adjoint gradient of the streaming path (vqe_stream_grad.h): opt-in (vqe_set_stream_grad); its backward sweep undoes
   // the circuit in place, so the states it leaves are not those a reduction-only launch may take
   bool stream_grad = false, stream_states_undone = false;
@@ -1843,6 +1847,75 @@ int run_lbfgs(vqe_t* h, bool env_step, const vqe_lbfgs_opts_t& o) {
   return VQE_OK;
 }
 
+// ---- device Adam-SPSA (vqe_spsa.h) -----------------------------------------------------------
+// Everything a run of k_lds_minimize_spsa can be refused for, checked before anything is loaded or launched; *o
+// receives the options.
+int spsa_check(vqe_t* h, const vqe_spsa_opts_t* opts, SpsaOpts* o) {
+  if (!opts) return fail(h, VQE_EINVAL, "Adam-SPSA options are NULL (start from vqe_spsa_default_opts)");
+  *o = SpsaOpts{opts->maxiter, opts->a, opts->alpha, opts->stability, opts->c, opts->gamma, opts->beta_1, opts->beta_2,
+                opts->lamda, opts->eps, opts->seed};
+  if (const char* why = spsa_bad_option(*o)) return fail(h, VQE_EINVAL, why);
+  if (h->amp_world > 1) return fail(h, VQE_ESTATE, "the device Adam-SPSA takes no amplitude shard");      // (only n >= 14 can hold one)
+  if (!h->lds_path)
+    return fail(h, VQE_EINVAL, "the device Adam-SPSA runs for n_qubits <= 13 (LDS-resident path) only");
+  if (h->noise_mode == 1)
+    return fail(h, VQE_ESTATE, "the device Adam-SPSA optimises mode 0 energies: refused in the exact channel noise mode (vqe_set_noise_mode 1)");
+  if (h->kraus.any())
+    return fail(h, VQE_ESTATE, "the device Adam-SPSA has no quantum-jump form: refused while a Kraus channel (vqe_set_noise_kraus, "
+                               "vqe_set_kraus_traj) is installed");
+  if (h->shard_world > 1)
+    return fail(h, VQE_ESTATE, "term-sharded handles hold partial energies: the device Adam-SPSA needs the full energy");
+  return VQE_OK;
+}
+
+template <int N>
+int launch_spsa(vqe_t* h, const BatchArgs& A, const SpsaOpts& o) {
+  const size_t lds = spsa_lds_bytes(N, A.max_ops, A.max_params, A.ham.n_groups, A.max_pair);
+  if (const char* why = lds_launch_refusal(N, lds, A.max_ops, (size_t)h->lds_per_cu)) return fail(h, VQE_EINVAL, why);
+  const bool noisy = A.noise.p1 > 0.0 || A.noise.p2 > 0.0;
+  void (*const kernel)(BatchArgs, SpsaArgs) = noisy ? k_lds_minimize_spsa<N, true> : k_lds_minimize_spsa<N, false>;
+  const void* fn = (const void*)kernel;
+  HIP_TRY(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  {   // the unit loop addresses the state region absolutely (unit_lds_read): the dynamic LDS must start at 0
+    hipFuncAttributes fa;
+    HIP_TRY(h, hipFuncGetAttributes(&fa, fn));
+    if (fa.sharedSizeBytes != 0) return fail(h, VQE_ESTATE, "LDS-resident kernel was built with static LDS");
+  }
+  HIP_TRY(h, h->spsa_work.reserve((size_t)A.batch * spsa_work_doubles(A.max_params)));
+  VQE_TRY(upload(h, h->spsa_opts, &o, 1));
+  HIP_TRY(h, hipStreamSynchronize(h->stream));      // (the caller's options go out of scope)
+  const SpsaArgs S{h->spsa_opts.p, h->spsa_work.p};
+  h->last_pairs = h->last_singles = 0;
+  h->last_lds = lds;
+  h->last_wg_per_cu = std::max(1, std::min(8, (int)(h->lds_per_cu / lds)));
+  HIP_TRY(h, hipEventRecord(h->ev0, h->stream));
+  hipLaunchKernelGGL(kernel, dim3(A.batch), dim3(Geo<N>::NT), lds, h->stream, A, S);
+  HIP_TRY(h, hipGetLastError());
+  HIP_TRY(h, hipEventRecord(h->ev1, h->stream));
+  return VQE_OK;
+}
+
+// o: options that passed spsa_check
+int run_spsa(vqe_t* h, bool env_step, const SpsaOpts& o) {
+  HIP_TRY(h, hipSetDevice(h->dev));
+  BatchArgs A = make_args(h);
+  const int evals = 2 * o.maxiter + 1;      // ids eval_base .. eval_base + 2K; the rows of the trace
+  A.maxfun = evals;
+  if (env_step) set_env_step(h, A);
+  {   // the launch's own refusal, before the trace and the info of the previous run are given up
+    const size_t lds = spsa_lds_bytes(h->n, A.max_ops, A.max_params, A.ham.n_groups, A.max_pair);
+    if (const char* why = lds_launch_refusal(h->n, lds, A.max_ops, (size_t)h->lds_per_cu)) return fail(h, VQE_EINVAL, why);
+  }
+  if (h->trace_on) VQE_TRY(arm_trace(h, A, evals));
+  h->last_run_dm = false;
+  h->lb_batch = 0;
+  h->qj_traj_batch = 0;
+  VQE_TRY(dispatch_n(h, "the device Adam-SPSA serves n_qubits <= 13 (LDS-resident path) only",
+                     [&](auto n) -> int { return launch_spsa<decltype(n)::value>(h, A, o); }, LdsSizes{}));
+  h->noise.eval_base += (uint64_t)evals;
+  return VQE_OK;
+}
+
 }  // namespace
 
 // =========================================================================================
@@ -2639,6 +2712,44 @@ int vqe_batch_fetch_lbfgs_info(vqe_t* h, int32_t* nit, int32_t* status) {
   if (status) HIP_TRY(h, hipMemcpyAsync(status, h->lb_status.p, (size_t)h->batch * 4, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(h, hipStreamSynchronize(h->stream));
   return VQE_OK;
+}
+
+int vqe_spsa_default_opts(vqe_spsa_opts_t* o) {
+  if (!o) return VQE_EINVAL;
+  const SpsaOpts d = spsa_default_opts();
+  *o = vqe_spsa_opts_t{d.maxiter, d.a, d.alpha, d.stability, d.c, d.gamma, d.beta_1, d.beta_2, d.lamda, d.eps, d.seed};
+  return VQE_OK;
+}
+
+int vqe_minimize_spsa(vqe_t* h, const double* x0, const vqe_spsa_opts_t* opts, double* x, double* f, int32_t* nfev) {
+  if (!h) return VQE_EINVAL;
+  SpsaOpts o;
+  int rc;
+  if ((rc = spsa_check(h, opts, &o))) return rc;
+  if (!f || (h->circ_params > 0 && (!x0 || !x))) return fail(h, VQE_EINVAL, "x0 / x / f is NULL");
+  HIP_TRY(h, hipSetDevice(h->dev));
+  if ((rc = load_single(h, 1, x0))) return rc;
+  if ((rc = ready(h))) return rc;
+  if ((rc = run_spsa(h, false, o))) return rc;
+  return vqe_batch_fetch(h, x, f, nfev);
+}
+
+int vqe_batch_run_minimize_spsa(vqe_t* h, const vqe_spsa_opts_t* opts) {
+  if (!h) return VQE_EINVAL;
+  SpsaOpts o;
+  int rc;
+  if ((rc = spsa_check(h, opts, &o))) return rc;
+  if ((rc = ready(h))) return rc;
+  return run_spsa(h, false, o);
+}
+
+int vqe_batch_run_env_step_spsa(vqe_t* h, const vqe_spsa_opts_t* opts) {
+  if (!h) return VQE_EINVAL;
+  SpsaOpts o;
+  int rc;
+  if ((rc = spsa_check(h, opts, &o))) return rc;
+  if ((rc = ready(h))) return rc;
+  return run_spsa(h, true, o);
 }
 
 int vqe_batch_fetch(vqe_t* h, double* x, double* f, int32_t* nfev) {

@@ -499,6 +499,31 @@ class VQEEngine:
                                                C.byref(nfev), C.byref(nit), C.byref(st)))
         return x, f.value, nfev.value, nit.value, st.value
 
+    # -- device Adam-SPSA: two evaluations per iteration, for stochastic energies and many variables ------
+    def spsa_opts(self, **opts):
+        """vqe_spsa_opts_t with the library's defaults (maxiter 100, a 0.1, alpha 0.602, stability 0, c 0.1, gamma 0.101,
+        beta_1 0.9, beta_2 0.999, lamda 0, eps 1e-8, seed 0) and the given fields replaced."""
+        o = _lib.SpsaOpts()
+        self._chk(self._lib.vqe_spsa_default_opts(C.byref(o)))
+        names = {f[0] for f in _lib.SpsaOpts._fields_}
+        for k, v in opts.items():
+            if k not in names:
+                raise TypeError(f"unknown Adam-SPSA option {k!r} (known: {sorted(names)})")
+            setattr(o, k, int(v) if k in ("maxiter", "seed") else float(v))
+        return o
+
+    def minimize_spsa(self, x0, **opts):
+        """Minimise E from x0 with the device Adam-SPSA (one launch, 2 maxiter + 1 evaluations).  Returns (x, f, nfev)."""
+        x0 = _f64(x0)
+        if x0.size != self._P:
+            raise ValueError("x0 has the wrong length")
+        o = self.spsa_opts(**opts)
+        x = np.empty_like(x0)
+        f = C.c_double()
+        nfev = C.c_int32()
+        self._chk(self._lib.vqe_minimize_spsa(self._h, _p(x0, c_f64p), C.byref(o), _p(x, c_f64p), C.byref(f), C.byref(nfev)))
+        return x, f.value, nfev.value
+
     # -- device Lanczos: extreme eigenpair of the Hamiltonian (no circuit involved) ----------------------
     LANCZOS_STATUS = {0: "converged", 1: "breakdown", 2: "budget"}
 
@@ -657,6 +682,16 @@ class VQEEngine:
         """batch_run_env_step with the device L-BFGS in COBYLA's place (honours batch_set_new_gate)."""
         o = self.lbfgs_opts(**opts)
         self._chk(self._lib.vqe_batch_run_env_step_lbfgs(self._h, C.byref(o)))
+
+    def batch_run_minimize_spsa(self, **opts):
+        """The device Adam-SPSA on every circuit of the resident batch, one launch (results: batch_fetch)."""
+        o = self.spsa_opts(**opts)
+        self._chk(self._lib.vqe_batch_run_minimize_spsa(self._h, C.byref(o)))
+
+    def batch_run_env_step_spsa(self, **opts):
+        """batch_run_env_step with the device Adam-SPSA in COBYLA's place (honours batch_set_new_gate)."""
+        o = self.spsa_opts(**opts)
+        self._chk(self._lib.vqe_batch_run_env_step_spsa(self._h, C.byref(o)))
 
     def batch_fetch_lbfgs_info(self):
         """(nit, status) per circuit of the last device L-BFGS run."""

@@ -179,8 +179,18 @@ class CircuitEnvBase:
             self.global_iters = 0
             self.optim_method = None
             self.noise_realisations = None
-        if self.optim_method not in (None, "scipy_each_step"):
-            raise NotImplementedError("only method = scipy_each_step is live in the reference (SURVEY 3.3 quirk 6)")
+        if self.optim_method not in (None, "scipy_each_step", "adam_spsa_each_step"):
+            raise NotImplementedError("only method = scipy_each_step is live in the reference (SURVEY 3.3 quirk 6); "
+                                      "adam_spsa_each_step is this package's own")
+        self._spsa_opts = None
+        if self.optim_method == "adam_spsa_each_step":
+            # The device Adam-SPSA (engine.batch_run_env_step_spsa) once per step, on the config's own [non_local_opt]
+            # keys - the ones no code path of the reference reads, so there is no counterpart and no parity claim.
+            # optim_alg is not consulted.
+            self.optimizer_kind = "device_spsa"
+            self._spsa_opts = self._spsa_options_from_config(n)
+            self._frozen_noise = False
+            return
         self.optimizer_kind = optimizer_kind(self.optim_alg) if self.optim_method else None
         if self._own_engine and self.optimizer_kind == "host_gradient" and n >= 14:
             self.engine.set_stream_grad(True)      # the streaming path computes gradients on request only
@@ -199,6 +209,23 @@ class CircuitEnvBase:
             self.engine.set_noise_grad(self.noise_realisations, hold=True)
             if self._own_engine and n >= 14:
                 self.engine.set_stream_noise_grad(-1)      # the streaming path runs the noisy gradients on request only
+
+    def _spsa_options_from_config(self, n):
+        """Options of VQEEngine.spsa_opts from the config: a, alpha, c, gamma, lamda, beta_1, beta_2 as they stand,
+        maxiter = maxfev // 2 when maxfev > 0, else global_iters // 2 (two evaluations per iteration)."""
+        opts = getattr(self, "options", None)
+        if not opts:
+            raise ValueError("method = adam_spsa_each_step needs the [non_local_opt] keys a, alpha, c, gamma, beta_1, beta_2")
+        for key in ("a", "c"):
+            if not float(opts[key]) > 0.0:
+                raise ValueError(f"method = adam_spsa_each_step needs non_local_opt.{key} > 0 (the config has {opts[key]!r})")
+        if n >= 14:
+            raise NotImplementedError("method = adam_spsa_each_step runs for n_qubits <= 13 (the LDS-resident path) only")
+        maxfev = int(getattr(self, "maxfev", {}).get("maxfev", 0))
+        out = {k: float(v) for k, v in opts.items()}
+        out["maxiter"] = (maxfev if maxfev > 0 else int(self.global_iters)) // 2
+        self.engine.spsa_opts(**out)      # (a name the engine does not know raises here)
+        return out
 
     # ---- engine set-up ---------------------------------------------------------------------
     def _make_engine(self, device):
@@ -367,6 +394,11 @@ class CircuitEnvBase:
         eng = self.engine
         eng.batch_load([circ], [ang])
         eng.batch_set_new_gate([new_idx])
+        if self.optim_method == "adam_spsa_each_step":
+            eng.batch_run_env_step_spsa(**self._spsa_opts)
+            x, f, nfev = eng.batch_fetch()
+            x_opt = self._strip_new(circ, new_idx, eng.batch_fetch_xopt())
+            return self._post_step(next_state, circ, x, x_opt, float(f[0]), int(nfev[0]), action, train_flag)
         if self.optim_method == "scipy_each_step" and self.optimizer_kind != "device_cobyla":
             return self._step_host_optimizer(next_state, circ, ang, new_idx, action, train_flag)
         if self.optim_method == "scipy_each_step":

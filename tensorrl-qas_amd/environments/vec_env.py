@@ -81,6 +81,11 @@ class VecCircuitEnv:
     with noise_channel = "exact" - set_dm_grad on top of the two switches below; NOT scipy's
     L-BFGS-B; at 14 qubits and more the engine's set_stream_lbfgs is switched on for it).  ``lbfgs_opts``: options of VQEEngine.lbfgs_opts; ``maxfun`` defaults to the config's global_iters so
     that nfev stays comparable with COBYLA's budget.
+    "spsa": batch_run_env_step_spsa, the device Adam-SPSA (two evaluations per iteration, energies only): noiseless
+    classes, and the noisy classes with noise_channel = "trajectory" and no noise_kraus - depolarising, ``noise_pauli``
+    and shot noise; refused with noise_channel = "exact", ``noise_kraus``, ``noise_realisations`` and at 14 qubits and
+    more.  ``spsa_opts``: options of VQEEngine.spsa_opts; ``maxiter`` defaults to global_iters // 2, so nfev stays
+    within COBYLA's budget.  The reference has no counterpart.
     ``noise_channel``: how the noisy environment classes evaluate their depolarising channels - "trajectory" (default:
     one Pauli trajectory per evaluation, as the reference's qulacs circuits do) or "exact" (the channel those draws
     sample from: the engine's exact channel mode on the batched lock-step path, set_noise_mode(1) + set_dm_batched(-1);
@@ -105,11 +110,20 @@ class VecCircuitEnv:
     def __init__(self, env_cls, conf, device, num_envs: int, seed: int = 0, native: bool | None = None,
                  device_optimizer: str = "cobyla", lbfgs_opts: dict | None = None, noise_channel: str = "trajectory",
                  noise_kraus=None, kraus_trajectories: int | None = None, noise_pauli=None,
-                 noise_realisations: int | None = None):
+                 noise_realisations: int | None = None, spsa_opts: dict | None = None):
         if not issubclass(env_cls, CircuitEnvBase):
             raise TypeError("env_cls must be one of the CircuitEnv classes of this package")
-        if device_optimizer not in ("cobyla", "lbfgs"):
-            raise ValueError('device_optimizer must be "cobyla" or "lbfgs"')
+        if device_optimizer not in ("cobyla", "lbfgs", "spsa"):
+            raise ValueError('device_optimizer must be "cobyla", "lbfgs" or "spsa"')
+        if spsa_opts is not None and device_optimizer != "spsa":
+            raise ValueError('spsa_opts needs device_optimizer = "spsa"')
+        if device_optimizer == "spsa":
+            if noise_channel == "exact":
+                raise NotImplementedError('device_optimizer = "spsa" optimises trajectory energies: noise_channel = "exact" is '
+                                          "served by the device COBYLA and the device L-BFGS")
+            if noise_kraus is not None:
+                raise NotImplementedError('device_optimizer = "spsa" has no quantum-jump form: noise_kraus is served by the '
+                                          "device COBYLA")
         if lbfgs_opts is not None and device_optimizer != "lbfgs":
             raise ValueError('lbfgs_opts needs device_optimizer = "lbfgs"')
         if noise_channel not in ("trajectory", "exact"):
@@ -149,6 +163,12 @@ class VecCircuitEnv:
                                       f"{first.optim_alg!r} is served by CircuitEnv")
         self.device_optimizer = device_optimizer
         self._lbfgs_opts = None
+        self._spsa_opts = None
+        if device_optimizer == "spsa":
+            if first.num_qubits >= 14:
+                raise NotImplementedError('device_optimizer = "spsa" runs for n_qubits <= 13 (the LDS-resident path) only')
+            self._spsa_opts = {"maxiter": int(first.global_iters) // 2, **(spsa_opts or {})}
+            first.engine.spsa_opts(**self._spsa_opts)      # (unknown names raise here, not at the first step)
         if device_optimizer == "lbfgs":
             frozen = noise_realisations is not None and not first.n_shots
             if noise_channel != "exact" and (first.NOISY or first.phys_noise or first.n_shots) and not frozen:
@@ -236,6 +256,9 @@ class VecCircuitEnv:
         if self._lbfgs_opts is not None:
             o = self.engine.lbfgs_opts(**self._lbfgs_opts)
             self._chk(lib.vqe_vecenv_set_optimizer(self._h, 1, C.byref(o)))
+        if self._spsa_opts is not None:
+            o = self.engine.spsa_opts(**self._spsa_opts)
+            self._chk(lib.vqe_vecenv_set_optimizer_spsa(self._h, C.byref(o)))
         self._base_obs = base_obs.to(self.device)
         self._obs = self._base_obs.repeat(B, 1)
         self._cache = {}
@@ -354,6 +377,8 @@ class VecCircuitEnv:
         eng.batch_set_new_gate([p[3] for p in pre])
         if self._lbfgs_opts is not None:
             eng.batch_run_env_step_lbfgs(**self._lbfgs_opts)
+        elif self._spsa_opts is not None:
+            eng.batch_run_env_step_spsa(**self._spsa_opts)
         else:
             eng.batch_run_env_step(1.0, 1e-4, int(self.envs[0].global_iters))
         self._pending = (pre, actions)
